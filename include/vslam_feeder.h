@@ -1,7 +1,7 @@
 /*
  * vslam_feeder.h -- synthetic frame feeder: the stand-in for the Android camera / Java plumbing of the
  * reference (src/vision/ar/monoslam/MainActivity.java:113-136 -> jni/jni_part.cpp:132-145), which is out of
- * scope.  Host C++ only (no GPU work); part of libvslam_hip.so so tests and bench.py share one scene.
+ * scope.  Host C++ (plus one device renderer for bench.py's set-up); part of libvslam_hip.so so tests and bench.py share one scene.
  *
  * Scene: a textured plane z = 0 (seeded random rectangles + low-amplitude value noise) seen by the
  * reference's ATAN/FOV camera (jni/ATANCamera.cc:20-24) on a smooth seeded trajectory.  Because the map
@@ -29,6 +29,12 @@ int vslam_feeder_render(const vslam_feeder* f, int first, int count, uint8_t* fr
                         size_t frame_stride, int n_threads);
 int vslam_feeder_render_pose(const vslam_feeder* f, const double pose12[12], uint64_t noise_key, uint8_t* frame,
                              size_t stride);
+/* the same on the device, synchronously: frame j of feeder i = vslam_feeder_render_pose(feeders[i], poses[i][j], keys[i][j])
+ * byte for byte, written to device memory frames + i * feeder_stride + j * frame_stride (rows of `width` bytes).  The n
+ * feeders share width, height, camera, noise and rectangle count.  poses [n][count][12] and keys [n][count] are host arrays;
+ * both NULL: frame j of feeder i = frame first + j of vslam_feeder_render(feeders[i], ...). */
+int vslam_feeder_render_device(const vslam_feeder* const* feeders, int n, int first, int count, const double* poses,
+                               const uint64_t* keys, uint8_t* frames, size_t feeder_stride, size_t frame_stride, int device);
 /* ground-truth map point for corner (cx, cy) of pyramid level `level` of a keyframe at pose12 */
 int vslam_feeder_make_point(const vslam_feeder* f, const double pose12[12], int level, int cx, int cy,
                             double pos[3], double pix_right[3], double pix_down[3]);

@@ -5,53 +5,11 @@
 #include <cstring>
 #include <thread>
 #include <vector>
+#include "feeder_internal.h"
 
-namespace {
+using namespace feeder_detail;
 
-struct Rng {  // xorshift64*
-  uint64_t s;
-  explicit Rng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 0x1234567ull) { if (!s) s = 1; }
-  uint64_t next() { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s * 0x2545F4914F6CDD1Dull; }
-  double uni() { return (next() >> 11) * (1.0 / 9007199254740992.0); }
-  int range(int lo, int hi) { return lo + (int)(uni() * (hi - lo)); }
-};
-
-inline uint32_t hash32(uint64_t x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return (uint32_t)x;
-}
-
-constexpr int TEX = 4096;          // texels per side
-constexpr double TEX_M = 4.0;      // metres per side: plane patch [-2,2]^2
-constexpr double PPM = TEX / TEX_M;
-
-}  // namespace
-
-struct vslam_feeder {
-  int w, h, noise;
-  uint64_t seed;
-  double focal[2], center[2], inv_focal[2], ww, winv, two_tan, one_over_2tan;
-  std::vector<uint8_t> tex;
-  std::vector<float> rays;   // per pixel: z = 1 plane coordinates of the (distorted) pixel
-  // trajectory parameters
-  double radius, height, dtheta, phase, wob_a, wob_b;
-
-  // ATAN/FOV camera (jni/ATANCamera.cc:133-164, ATANCamera.h:136-150)
-  void unproject(double ix, double iy, double out[2]) const {
-    const double dx = (ix - center[0]) * inv_focal[0], dy = (iy - center[1]) * inv_focal[1];
-    const double dr = std::sqrt(dx * dx + dy * dy);
-    const double r = ww == 0.0 ? dr : std::tan(dr * ww) * one_over_2tan;
-    const double f = dr > 0.01 ? r / dr : 1.0;
-    out[0] = dx * f; out[1] = dy * f;
-  }
-  void project(double cx, double cy, double im[2]) const {
-    const double r = std::sqrt(cx * cx + cy * cy);
-    const double fac = (r < 0.001 || ww == 0.0) ? 1.0 : winv * std::atan(r * two_tan) / r;
-    im[0] = center[0] + focal[0] * (cx * fac); im[1] = center[1] + focal[1] * (cy * fac);
-  }
-};
-
-static void pose_at(const vslam_feeder* f, double t, double P[12]) {
+void pose_at(const vslam_feeder* f, double t, double P[12]) {
   // camera centre on a circle above the plane, optical axis along +Z (plane at depth ~height), small wobble
   const double th = f->phase + f->dtheta * t;
   const double C[3] = {f->radius * std::cos(th), f->radius * std::sin(th), -(f->height + 0.04 * std::sin(0.013 * t + f->wob_a))};
@@ -63,6 +21,28 @@ static void pose_at(const vslam_feeder* f, double t, double P[12]) {
                        -sy, cy * sx, cy * cx};
   for (int i = 0; i < 9; i++) P[i] = R[i];
   for (int i = 0; i < 3; i++) P[9 + i] = -(R[i * 3 + 0] * C[0] + R[i * 3 + 1] * C[1] + R[i * 3 + 2] * C[2]);
+}
+
+static void feeder_texture(const vslam_feeder* cf) {
+  vslam_feeder* f = const_cast<vslam_feeder*>(cf);
+  std::call_once(f->tex_once, [f] {
+    f->tex.assign((size_t)TEX * TEX, 0);
+    const int G = LAT;
+    const std::vector<float>& lat = f->lat;
+    for (int y = 0; y < TEX; y++)
+      for (int x = 0; x < TEX; x++) {
+        const double gx = (double)x * G / TEX, gy = (double)y * G / TEX;
+        const int ix = (int)gx, iy = (int)gy;
+        const double fx = gx - ix, fy = gy - iy;
+        const double n = (1 - fy) * ((1 - fx) * lat[iy * (G + 1) + ix] + fx * lat[iy * (G + 1) + ix + 1]) +
+                         fy * ((1 - fx) * lat[(iy + 1) * (G + 1) + ix] + fx * lat[(iy + 1) * (G + 1) + ix + 1]);
+        f->tex[(size_t)y * TEX + x] = (uint8_t)(128 + 18 * n);
+      }
+    for (size_t i = 0; i + 5 <= f->rects.size(); i += 5) {
+      const int x0 = f->rects[i], y0 = f->rects[i + 1], rw = f->rects[i + 2], rh = f->rects[i + 3], g = f->rects[i + 4];
+      for (int y = y0; y < y0 + rh; y++) memset(&f->tex[(size_t)y * TEX + x0], g, rw);
+    }
+  });
 }
 
 static void render_one(const vslam_feeder* f, const double P[12], uint64_t noise_key, uint8_t* out, size_t stride) {
@@ -103,29 +83,17 @@ extern "C" int vslam_feeder_create(int width, int height, const double cam[5], u
   if (f->ww != 0.0) { f->two_tan = 2.0 * std::tan(f->ww / 2.0); f->one_over_2tan = 1.0 / f->two_tan; f->winv = 1.0 / f->ww; }
   else { f->two_tan = 0; f->one_over_2tan = 0; f->winv = 0; }
   Rng rng(seed);
-  // texture: mid-grey value noise + rectangles (corners of rectangles are the FAST features)
-  f->tex.assign((size_t)TEX * TEX, 0);
-  {
-    const int G = 64;  // coarse lattice for value noise
-    std::vector<float> lat((size_t)(G + 1) * (G + 1));
-    for (auto& v : lat) v = (float)(rng.uni() * 2 - 1);
-    for (int y = 0; y < TEX; y++)
-      for (int x = 0; x < TEX; x++) {
-        const double gx = (double)x * G / TEX, gy = (double)y * G / TEX;
-        const int ix = (int)gx, iy = (int)gy;
-        const double fx = gx - ix, fy = gy - iy;
-        const double n = (1 - fy) * ((1 - fx) * lat[iy * (G + 1) + ix] + fx * lat[iy * (G + 1) + ix + 1]) +
-                         fy * ((1 - fx) * lat[(iy + 1) * (G + 1) + ix] + fx * lat[(iy + 1) * (G + 1) + ix + 1]);
-        f->tex[(size_t)y * TEX + x] = (uint8_t)(128 + 18 * n);
-      }
-    int nrect = 1000;   // ~1000 FAST-10 corners per 640x480 frame at level 0 (BASELINE.json configs[1])
-    if (const char* e = getenv("VSLAM_FEEDER_NRECT")) nrect = atoi(e);
-    for (int i = 0; i < nrect; i++) {
-      const int rw = rng.range(20, 160), rh = rng.range(20, 160);
-      const int x0 = rng.range(0, TEX - rw), y0 = rng.range(0, TEX - rh);
-      const int g = rng.range(20, 236);
-      for (int y = y0; y < y0 + rh; y++) memset(&f->tex[(size_t)y * TEX + x0], g, rw);
-    }
+  // texture: mid-grey value noise + rectangles (corners of rectangles are the FAST features); the draws are made here, the
+  // texels on the first host render (feeder_texture) or on the device (vslam_feeder_render_device)
+  f->lat.resize((size_t)(LAT + 1) * (LAT + 1));
+  for (auto& v : f->lat) v = (float)(rng.uni() * 2 - 1);
+  int nrect = 1000;   // ~1000 FAST-10 corners per 640x480 frame at level 0 (BASELINE.json configs[1])
+  if (const char* e = getenv("VSLAM_FEEDER_NRECT")) nrect = atoi(e);
+  for (int i = 0; i < nrect; i++) {
+    const int rw = rng.range(20, 160), rh = rng.range(20, 160);
+    const int x0 = rng.range(0, TEX - rw), y0 = rng.range(0, TEX - rh);
+    const int g = rng.range(20, 236);
+    f->rects.insert(f->rects.end(), {x0, y0, rw, rh, g});
   }
   f->rays.resize((size_t)2 * width * height);
   for (int y = 0; y < height; y++)
@@ -148,6 +116,7 @@ extern "C" int vslam_feeder_pose(const vslam_feeder* f, double t, double pose12[
 
 extern "C" int vslam_feeder_render_pose(const vslam_feeder* f, const double pose12[12], uint64_t noise_key, uint8_t* frame, size_t stride) {
   if (!f || !frame) return -1;
+  feeder_texture(f);
   render_one(f, pose12, noise_key ^ (f->seed << 20), frame, stride);
   return 0;
 }
@@ -155,6 +124,7 @@ extern "C" int vslam_feeder_render_pose(const vslam_feeder* f, const double pose
 extern "C" int vslam_feeder_render(const vslam_feeder* f, int first, int count, uint8_t* frames, size_t stride, size_t frame_stride, int n_threads) {
   if (!f || !frames || count < 0) return -1;
   if (n_threads < 1) n_threads = 1;
+  feeder_texture(f);
   auto work = [&](int tid) {
     for (int i = tid; i < count; i += n_threads) {
       double P[12]; pose_at(f, first + i, P);

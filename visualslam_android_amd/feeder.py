@@ -16,6 +16,8 @@ FEEDER_SYMBOLS = {
     "vslam_feeder_pose": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "vslam_feeder_render": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]),
     "vslam_feeder_render_pose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]),
+    "vslam_feeder_render_device": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_size_t, C.c_size_t, C.c_int]),
     "vslam_feeder_make_point": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vslam_feeder_project": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double)]),
 }
@@ -88,6 +90,26 @@ class Feeder:
         depth = C.c_double(0)
         ok = self.lib.vslam_feeder_project(self.h_, p.ctypes.data, x.ctypes.data, border, im.ctypes.data, C.byref(depth))
         return ok == 1, im, depth.value
+
+
+def render_device(feeders, poses, keys, out_ptr, feeder_stride, frame_stride, device=0, first=0, count=None):
+    """Frame j of feeder i = feeders[i].render_pose(poses[i, j], keys[i, j]), byte for byte, rendered on the device into device
+    memory at out_ptr + i * feeder_stride + j * frame_stride (the caller owns that memory and sizes it).  poses = keys = None:
+    frame j = frame first + j of feeders[i].render(...), count frames.  Synchronous."""
+    lib = _lib()
+    n = len(feeders)
+    if poses is None:
+        pp = kp = None
+    else:
+        p = np.ascontiguousarray(poses, np.float64)
+        k = np.ascontiguousarray(keys, np.uint64)
+        count = p.shape[1]
+        assert p.shape == (n, count, 12) and k.shape == (n, count)
+        pp, kp = p.ctypes.data, k.ctypes.data
+    hs = (C.c_void_p * n)(*[f.h_.value for f in feeders])
+    rc = lib.vslam_feeder_render_device(hs, n, int(first), int(count), pp, kp, out_ptr, feeder_stride, frame_stride, device)
+    if rc:
+        raise capi.VslamError("feeder_render_device failed (%d)" % rc)
 
 
 def se3_perturb(pose12, rng, trans_sigma, rot_sigma):
