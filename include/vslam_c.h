@@ -340,7 +340,14 @@ int vslam_bundle_adjust_all(vslam_system* sys);
  * Needs a tracked current frame. */
 int vslam_add_keyframe(vslam_system* sys, int stream);
 
-/* ---- stand-alone Bundle (jni/Bundle.h:111-121), batched: n_problems independent problems ---- */
+/* ---- stand-alone Bundle (jni/Bundle.h:111-121), batched: n_problems independent problems ----
+ * Capacity per problem: 1..128 cameras, 1..4096 points, 1..65536 measurements (vslam_bundle_create refuses more with
+ * VSLAM_E_INVALID; an add_* or set_problem call past the problem's capacity returns VSLAM_E_CAPACITY and changes nothing).
+ * At most 64 of a problem's cameras may be adjustable: a problem with more is not adjusted -- vslam_bundle_get_result reports
+ * accepted = -1 and its cameras and points stay as added.
+ * Duplicates: a problem holds at most one measurement per (camera, point) pair.  The reference accepts a second one (both enter
+ * the U / V sums, GenerateMeasLUTs keeps the last for the reduced system); here vslam_bundle_add_meas and
+ * vslam_bundle_set_problem refuse it with VSLAM_E_INVALID and the problem stays as it was. */
 typedef struct vslam_bundle vslam_bundle;
 int vslam_bundle_create(const vslam_params* p, int n_problems, int max_cameras, int max_points, int max_meas,
                         vslam_bundle** out);

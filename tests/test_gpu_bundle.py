@@ -63,7 +63,8 @@ def test_config3_local_ba_5x300_reference_order_is_bit_exact(max_it, n_fixed):
 
 def test_reference_order_batched_shuffled_lists_and_window_sizes():
     """The parity mode over everything the fast mode's tests cover: several problems in one launch, 1 to 9 adjustable cameras (the
-    register, LDS and global forms of the solve), fixed cameras interleaved, and measurement lists in a SHUFFLED AddMeas order (the
+    register, LDS and global forms of the solve), one or three fixed cameras at the head of the camera list (ba_scene fixes a prefix;
+    fixed cameras elsewhere in the list: test_gpu_bundle_paths.py), and measurement lists in a SHUFFLED AddMeas order (the
     reference's sums follow the list, not the camera or point index)."""
     rng = np.random.default_rng(7)
     scs = [ba_scene(n_cams=4, n_pts=80, seed=11), ba_scene(n_cams=6, n_pts=200, pixel_noise=0.3, seed=12),

@@ -11,6 +11,7 @@
 #define BA_MAX_KF 128        // keyframes per stream = cameras of a bundle-adjustment problem (8-bit camera field of a slot: < 256)
 #include <string.h>
 #include <stdlib.h>
+#include <unordered_set>
 
 struct BaPool {            // device arrays for N problems
   int N, max_cams, max_pts, max_meas, max_free;
@@ -196,7 +197,11 @@ static BaConfig make_cfg(const TrackParams& tp) {
 // =================================================================================================================
 // stand-alone batched Bundle
 // =================================================================================================================
-struct HostProblem { std::vector<Pose> cams; std::vector<int> fixed; std::vector<double> pts; std::vector<int> mp, mc; std::vector<double> mfound, msin; };
+struct HostProblem {
+  std::vector<Pose> cams; std::vector<int> fixed; std::vector<double> pts; std::vector<int> mp, mc; std::vector<double> mfound, msin;
+  std::unordered_set<unsigned long long> pairs;   // (camera, point) of every measurement: a second one is refused (vslam_c.h)
+};
+static inline unsigned long long meas_key(int cam, int point) { return ((unsigned long long)(unsigned)cam << 32) | (unsigned)point; }
 
 struct vslam_bundle {
   BaPool pool; std::vector<void*> allocs; hipStream_t stream; BaConfig cfg; TrackParams tp;
@@ -274,7 +279,9 @@ extern "C" int vslam_bundle_add_meas(vslam_bundle* b, int n, int cam, int point,
   BCHECK(b && n >= 0 && n < b->pool.N && pos, "bad measurement argument");
   HostProblem& h = b->host[n];
   BCHECK(cam >= 0 && cam < (int)h.cams.size() && point >= 0 && point < (int)h.pts.size() / 3, "measurement refers to an unknown camera/point");   // asserts :107-108
+  BCHECK(!h.pairs.count(meas_key(cam, point)), "a second measurement of the same (camera, point) pair");
   if ((int)h.mp.size() >= b->pool.max_meas) { vslam_set_error("bundle: measurement capacity"); return VSLAM_E_CAPACITY; }
+  h.pairs.insert(meas_key(cam, point));
   h.mp.push_back(point); h.mc.push_back(cam); h.mfound.push_back(pos[0]); h.mfound.push_back(pos[1]);
   h.msin.push_back(sqrt(1.0 / sigma_squared));   // :115
   b->dirty = true;
@@ -288,9 +295,7 @@ extern "C" int vslam_bundle_set_problem(vslam_bundle* b, int n, int n_cams, cons
   BCHECK(b && n >= 0 && n < b->pool.N && n_cams >= 0 && n_pts >= 0 && n_meas >= 0, "set_problem: bad argument");
   BCHECK((n_cams == 0 || (pose12 && fixed)) && (n_pts == 0 || pos3) && (n_meas == 0 || (cam && point && xy && sigma_squared)), "set_problem: null array");
   if (n_cams > b->pool.max_cams || n_pts > b->pool.max_pts || n_meas > b->pool.max_meas) { vslam_set_error("bundle: set_problem exceeds the capacity"); return VSLAM_E_CAPACITY; }
-  HostProblem& h = b->host[n];
-  h = HostProblem();
-  b->dirty = true;
+  HostProblem h;                                     // built aside: a refused call leaves the problem as it was
   for (int c = 0; c < n_cams; c++) { Pose p; for (int i = 0; i < 9; i++) p.R[i] = pose12[12 * c + i]; for (int i = 0; i < 3; i++) p.t[i] = pose12[12 * c + 9 + i]; h.cams.push_back(p); h.fixed.push_back(fixed[c] ? 1 : 0); }
   for (int i = 0; i < n_pts; i++) {
     double q[3] = {pos3[3 * i], pos3[3 * i + 1], pos3[3 * i + 2]};
@@ -299,9 +304,12 @@ extern "C" int vslam_bundle_set_problem(vslam_bundle* b, int n, int n_cams, cons
   }
   for (int i = 0; i < n_meas; i++) {
     BCHECK(cam[i] >= 0 && cam[i] < n_cams && point[i] >= 0 && point[i] < n_pts, "measurement refers to an unknown camera/point");
+    BCHECK(h.pairs.insert(meas_key(cam[i], point[i])).second, "a second measurement of the same (camera, point) pair");
     h.mp.push_back(point[i]); h.mc.push_back(cam[i]); h.mfound.push_back(xy[2 * i]); h.mfound.push_back(xy[2 * i + 1]);
     h.msin.push_back(sqrt(1.0 / sigma_squared[i]));
   }
+  b->host[n] = std::move(h);
+  b->dirty = true;
   return VSLAM_OK;
 }
 
