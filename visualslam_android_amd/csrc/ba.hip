@@ -67,14 +67,13 @@ __host__ __device__ inline BaOrdView ba_ord_view(const BaPool& b, int n) {
   return o;
 }
 
-#ifndef VSLAM_BA_WPE
-#define VSLAM_BA_WPE 2
-#endif
-__global__ __launch_bounds__(BA_THREADS) __attribute__((amdgpu_waves_per_eu(VSLAM_BA_WPE, VSLAM_BA_WPE))) void k_ba_compute(BaPool pool, BaConfig cfg, int slot, int lrec /* record of the launch in pool.lstat, or -1 */) {
-  // slot < 0: one workgroup per problem of the pool (synchronous map-maker, stand-alone Bundle); slot >= 0: the grid walks the
-  // work list of one frame (asynchronous map-maker)
-  // (the persistent workgroups of an asynchronous launch draw their next list entry from a counter: the long and the short
-  // adjustments of a batch balance themselves instead of leaving the workgroups that drew two long ones alone at the end)
+// One launch of Bundle::Compute; Sums: BaFastSums or BaOrdSums (vslam_params.ba_sum_order).
+// slot < 0: one workgroup per problem of the pool (synchronous map-maker, stand-alone Bundle); slot >= 0: the grid walks the
+// work list of one frame (asynchronous map-maker)
+// (the persistent workgroups of an asynchronous launch draw their next list entry from a counter: the long and the short
+// adjustments of a batch balance themselves instead of leaving the workgroups that drew two long ones alone at the end)
+template <class Sums>
+DEVFN void ba_compute_grid(const BaPool& pool, const BaConfig& cfg, int slot, int lrec /* record of the launch in pool.lstat, or -1 */) {
   const int count = slot < 0 ? pool.N : pool.work_n[slot];
   __shared__ int s_next;
   int i = blockIdx.x;
@@ -82,7 +81,7 @@ __global__ __launch_bounds__(BA_THREADS) __attribute__((amdgpu_waves_per_eu(VSLA
     const int n = slot < 0 ? i : pool.work[(size_t)slot * pool.N + i];
     const BaView v = ba_view(pool, n);
     if (v.res->active && !v.res->computed) {
-      ba_compute(v, cfg);
+      ba_lm<Sums>(v, cfg, Sums::ordered ? ba_ord_view(pool, n) : BaOrdView{});
       if (threadIdx.x == 0) {
         v.res->computed = 1;
         if (lrec >= 0 && pool.lstat) {                                // the work this launch did, for the roofline of THIS launch
@@ -102,41 +101,14 @@ __global__ __launch_bounds__(BA_THREADS) __attribute__((amdgpu_waves_per_eu(VSLA
   }
 }
 
-// The same launch in the parity mode (vslam_params.ba_sum_order = 1): every sum in the reference's order (ba_ordered.h).  A kernel of
-// its own, so that its registers and LDS do not weigh on the fast path's.
-// (the same register bound as k_ba_compute: the two kernels share the out-of-line phase functions, which are compiled once)
-__global__ __launch_bounds__(BA_THREADS) __attribute__((amdgpu_waves_per_eu(VSLAM_BA_WPE, VSLAM_BA_WPE))) void k_ba_compute_ordered(BaPool pool, BaConfig cfg, int slot, int lrec) {
-  const int count = slot < 0 ? pool.N : pool.work_n[slot];
-  __shared__ int s_next;
-  int i = blockIdx.x;
-  while (i < count) {
-    const int n = slot < 0 ? i : pool.work[(size_t)slot * pool.N + i];
-    const BaView v = ba_view(pool, n);
-    if (v.res->active && !v.res->computed) {
-      ba_compute_ordered(v, cfg, ba_ord_view(pool, n));
-      if (threadIdx.x == 0) {
-        v.res->computed = 1;
-        if (lrec >= 0 && pool.lstat) {
-          unsigned long long* L = pool.lstat + (size_t)lrec * BA_LSTAT_N;
-          const unsigned long long t = (unsigned long long)v.res->trials, nf = (unsigned long long)v.res->n_free;
-          atomicAdd(&L[0], 1ull); atomicAdd(&L[1], t);
-          atomicAdd(&L[2], t * (unsigned long long)v.res->n_meas); atomicAdd(&L[3], t * (unsigned long long)v.res->n_cams); atomicAdd(&L[4], t * (unsigned long long)v.res->n_pts);
-          atomicAdd(&L[5], t * (unsigned long long)v.res->n_pts * (nf * (nf > 0 ? nf - 1 : 0) / 2)); atomicAdd(&L[6], t * (6 * nf) * (6 * nf) * (6 * nf));
-        }
-      }
-    }
-    if (slot < 0) break;
-    __syncthreads();
-    if (threadIdx.x == 0) s_next = (int)gridDim.x + atomicAdd(&pool.work_n[pool.work_slots + slot], 1);
-    __syncthreads();
-    i = s_next;
-  }
-}
+// Two kernels, so that the registers and the LDS of the parity mode do not weigh on the fast path's
+// (the same register bound: the two kernels share the out-of-line phase functions, which are compiled once)
+__global__ __launch_bounds__(BA_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_ba_compute(BaPool pool, BaConfig cfg, int slot, int lrec) { ba_compute_grid<BaFastSums>(pool, cfg, slot, lrec); }
+__global__ __launch_bounds__(BA_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_ba_compute_ordered(BaPool pool, BaConfig cfg, int slot, int lrec) { ba_compute_grid<BaOrdSums>(pool, cfg, slot, lrec); }
 
 static void ba_launch_compute(const BaPool& pool, const BaConfig& cfg, int grid, hipStream_t st, int slot, int lrec) {
-  static const int dyn_lds = getenv("VSLAM_BA_DYN_LDS") ? atoi(getenv("VSLAM_BA_DYN_LDS")) : 0;   // diagnostic: extra LDS per workgroup, to lower the workgroups per CU
   if (cfg.sum_order) hipLaunchKernelGGL(k_ba_compute_ordered, dim3(grid), dim3(BA_THREADS), 0, st, pool, cfg, slot, lrec);
-  else hipLaunchKernelGGL(k_ba_compute, dim3(grid), dim3(BA_THREADS), dyn_lds, st, pool, cfg, slot, lrec);
+  else hipLaunchKernelGGL(k_ba_compute, dim3(grid), dim3(BA_THREADS), 0, st, pool, cfg, slot, lrec);
 }
 
 // The arrays of a pool are carved out of ONE device allocation (256-byte aligned each): some forty separate allocations, most of them
@@ -818,8 +790,7 @@ static int ba_launch_batch(vslam_system* sys) {
   { int rr = ba_next_launch_record(sys, sys->ba_stream, &lrec, &lord); if (rr) return rr; }
   prof_mark(sys, 12);                                  // the batch's assemblies precede on this very stream
   // one workgroup per problem up to two per compute unit; the grid walks the batch's work list
-  static const int per_cu_x2 = getenv("VSLAM_BA_WG_PER_CU_X2") ? atoi(getenv("VSLAM_BA_WG_PER_CU_X2")) : 4;   // diagnostic: background workgroups per CU, in halves
-  const int cap = per_cu_x2 * (sys->n_cu > 0 ? sys->n_cu : 256) / 2;
+  const int cap = 2 * (sys->n_cu > 0 ? sys->n_cu : 256);
   const int ba_grid = sys->S < cap ? sys->S : cap;
   ba_launch_compute(ws->pool, cfg, ba_grid, sys->ba_stream, slot, lrec);
   prof_mark(sys, PROF_BA_END);

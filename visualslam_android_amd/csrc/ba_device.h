@@ -25,25 +25,13 @@
 #pragma once
 #include "dev_math.h"
 
-#ifndef VSLAM_BA_WPE
-#define VSLAM_BA_WPE 2
-#endif
-// the phases of Bundle::Compute are out-of-line functions with their own register allocation (VSLAM_BA_INLINE_PHASES: diagnostic,
-// everything in the kernel's allocation so that amdgpu_waves_per_eu bounds it)
-#ifdef VSLAM_BA_INLINE_PHASES
-#define BA_PHASE_FN __device__ __forceinline__
-#else
+// the phases of Bundle::Compute are out-of-line functions with their own register allocation
 #define BA_PHASE_FN __device__ __attribute__((noinline))
-#endif
-#ifndef BA_THREADS
 #define BA_THREADS 256
-#endif
 // 4 waves; with amdgpu_waves_per_eu(2,2) on the kernel two problems share a CU (measured: 512 x 1 -4 %, 128 x 4 -4 %)
 #define BA_LDS_N 60      // reduced camera systems up to 60 x 60 (10 adjustable cameras) are solved in LDS
 #define BA_WAVES (BA_THREADS / 64)
-#ifndef BA_ILP_PROJ
 #define BA_ILP_PROJ 4   // projection passes: 4 measurements in flight (1 -> 4: -31 % on FindNewError once the view pointers were global and scalar; 6 spills: 5x slower)
-#endif
 #define BA_ILP_S 1      // Schur-complement tasks: 36 accumulators + two 6x3 blocks per lane leave no registers for a second point
 #define BA_ILP 4        // independent measurements per thread and loop trip: the loops are memory-latency bound at 2 waves/SIMD
 #define BA_ILP_C 4      // fused weight / derivative pass after an accepted step
@@ -140,7 +128,7 @@ DEVFN void ba_store_pose(Pose AS1* p, const Pose& T) {
   _Pragma("unroll") for (int k = 0; k < 3; k++) p->t[k] = T.t[k];
 }
 
-// Diagnostic build only (-DVSLAM_BA_PROF): clock64() stamps of block 0 / lane 0 per phase of ba_compute, accumulated in
+// Diagnostic build only (-DVSLAM_BA_PROF): clock64() stamps of block 0 / lane 0 per phase of ba_lm<BaFastSums>, accumulated in
 // g_ba_prof[phase]; read with vslam_debug_ba_prof().  Never compiled into the product library.
 #ifdef VSLAM_BA_PROF
 __device__ unsigned long long g_ba_prof[32];
@@ -280,7 +268,10 @@ DEVFN bool ba_block_solve(double* S, double* E, int n, int* ired) {
 }
 
 // The same solve with the augmented system held in LDS (n <= BA_LDS_N): pivot search by wave shuffles, elimination by
-// the whole workgroup, back-substitution by wave 0.  A: LDS [n][n+1].
+// the whole workgroup (every element independently: the same multiply / subtract per element as lu_solve, whatever thread does
+// it).  Back-substitution: wave 0 sums a row's products across its lanes, or (ORDERED, the reference-order mode) one lane
+// subtracts them in ascending column order.  A: LDS [n][n+1].
+template <bool ORDERED>
 DEVFN bool ba_block_solve_lds(const double* S, double* E, int n, double* A, int* ired) {
   const int ld = n + 1, lane = threadIdx.x & 63;
   for (int t = threadIdx.x; t < n * ld; t += blockDim.x) { const int r = t / ld, c = t - r * ld; A[t] = c < n ? S[(size_t)r * n + c] : E[r]; }
@@ -309,7 +300,14 @@ DEVFN bool ba_block_solve_lds(const double* S, double* E, int n, double* A, int*
     }
     __syncthreads();
   }
-  if (threadIdx.x < 64) {
+  if (ORDERED) {
+    if (threadIdx.x == 0)
+      for (int k = n - 1; k >= 0; k--) {
+        double s = A[k * ld + n];
+        for (int c = k + 1; c < n; c++) s -= A[k * ld + c] * A[c * ld + n];
+        A[k * ld + n] = s / A[k * ld + k];
+      }
+  } else if (threadIdx.x < 64) {
     for (int k = n - 1; k >= 0; k--) {
       double s = 0.0;
       for (int c = k + 1 + lane; c < n; c += 64) s += A[k * ld + c] * A[c * ld + n];
@@ -330,10 +328,7 @@ DEVFN bool ba_block_solve_lds(const double* S, double* E, int n, double* A, int*
 // Same pivoting rule (first row of maximal |A[r][k]|) and the same multiply / subtract per element as ba_block_solve, the
 // back-substitution sums in ascending column order like lu_solve_n.  Every index is a compile-time constant after
 // unrolling.  Called by wavefront 0 only; returns false if singular.  Writes the solution to E.
-#define BA_WSOLVE_N 30
-#ifndef VSLAM_BA_WSOLVE
-#define VSLAM_BA_WSOLVE 1   // measured (tools/ba_phase_profile*.py, 512 problems): 30 x 30 solve 116 kcycles by one wavefront in registers, 160 by the workgroup in LDS; 24 x 24: 103 / 108
-#endif
+#define BA_WSOLVE_N 30      // measured (tools/ba_phase_profile*.py, 512 problems): 30 x 30 solve 116 kcycles by one wavefront in registers, 160 by the workgroup in LDS; 24 x 24: 103 / 108
 DEVFN double ba_readlane_d(double v, int l) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
@@ -890,9 +885,7 @@ BA_PHASE_FN void ba_task_pair(const BaView& v_, int task, int np, int nS, double
 // staged k-major in LDS and multiplied by v_mfma_f64_16x16x4_f64
 // (operand layout: tools/probes/mfma_f64_layout.hip; a = A[l%16][l/16], b = B[l/16][l%16], d[v] = D[l/16+4v][l%16]).
 // Wave partials are added in wave order, the lower triangle is mirrored as the reference mirrors it (:431-434).
-#ifndef BA_MFMA_PPC
 #define BA_MFMA_PPC 12                                  // points per wavefront and trip: 12 x 5 cameras = 60 lanes, K = 36
-#endif
 #define BA_MFMA_K (3 * BA_MFMA_PPC)
 #define BA_MFMA_STAGE (4 * BA_MFMA_K * 16)              // doubles per wavefront: Y rows 0-15 / 16-31, W columns 0-15 / 16-31, each [K][16]
 static_assert(BA_MFMA_STAGE >= 32 * 32 && BA_MFMA_K % 4 == 0, "a wavefront's staging area also holds its 32 x 32 partial product");
@@ -1223,20 +1216,101 @@ BA_PHASE_FN int ba_erase_outliers(const BaView& v_, int M, int nm, int nout, uns
   return base;
 }
 
-// Bundle::Compute.  Called by all BA_THREADS threads of one workgroup.
-DEVFN void ba_compute(const BaView& v_, const BaConfig& cfg) {
+// Bundle::Compute is stated once, in ba_lm<Sums> below; what differs between the two modes of vslam_params.ba_sum_order is HOW THE
+// SUMS ARE TAKEN, and a Sums type supplies exactly that.  BaFastSums: per-wavefront partial sums, tree reductions, matrix cores
+// (BaOrdSums, ba_ordered.h: every sum in the reference's order).  A result that is one value per workgroup is valid in thread 0.
+// The LDS arrays are static members and the problem's sizes arguments, not members set once: the out-of-line phases are compiled
+// with what their call sites show as constants and ranges.
+struct BaOrdView;
+struct BaFastSums {
+  static constexpr bool ordered = false;
+  static constexpr int LDS_MFMA = BA_WAVES * BA_MFMA_STAGE, LDS_SOLVE = BA_LDS_N * (BA_LDS_N + 1);
+  static constexpr int LDS_SWEEP = BA_WAVES * 64 * BA_SWEEP_STAGE + 12 * BA_MAX_CAMS_LDS + 6 * BA_FAST_FREE;
+  static constexpr int LDS_LAYOUT = (2 * 4097 * (int)sizeof(int) + 7) / 8;
+  static constexpr int LDS_A = LDS_MFMA > LDS_SOLVE ? LDS_MFMA : LDS_SOLVE, LDS_B = LDS_SWEEP > LDS_LAYOUT ? LDS_SWEEP : LDS_LAYOUT;
+  static constexpr int LDS_DOUBLES = LDS_A > LDS_B ? LDS_A : LDS_B;
+  const BaView& v_; const BaViewG& v; const BaConfig& cfg;
+  double* red; int* ired;                                              // the driver's reduction scratch
+  static __shared__ double lds[LDS_DOUBLES];                           // one phase at a time
+#ifdef VSLAM_BA_PROF
+  unsigned long long ba_t0 = clock64();
+#endif
+  DEVFN BaFastSums(const BaView& v_, const BaViewG& v, const BaConfig& cfg, const BaOrdView&, double* red, int* ired) : v_(v_), v(v), cfg(cfg), red(red), ired(ired) {}
+  DEVFN void stamp(int id) { BA_STAMP(id); }
+  DEVFN void begin(int, int) {}                                        // (no table of its own behind the layout)
+  // pass 1 (:209-215): the squared errors of the measurements still in the list, for the median; their number
+  DEVFN int count_valid(int M, int) { return ba_block_sum_i(ba_find_new_error(v_, cfg, M, 1.0, 0, lds).nvalid, ired); }
+  // passes 1 + 2 (:209-321) in one sweep: weights, objective, V / epsilon_b, U / epsilon_a; A, B, W are re-derived by their consumers
+  DEVFN double step(int M, int nc, int np, int nfree, double sigma2) {
+    double* stg = lds; double* ured = nullptr; double* camsL = lds + BA_WAVES * 64 * BA_SWEEP_STAGE;
+    for (int t = threadIdx.x; t < nc * 12; t += BA_THREADS) camsL[t] = ((const double AS1*)v.cam_pose)[t];   // Pose = R[9], t[3]
+    __syncthreads();
+    double cur = ba_step_sweep(v_, cfg, 0, sigma2, nfree, stg, ured, camsL);
+    __syncthreads();
+    if (nfree <= BA_FAST_FREE) {
+      for (int t = threadIdx.x; t < nfree * 27; t += BA_THREADS) {     // wave partials in wave order
+        const int f = t / 27, q = t - 27 * f, j = v.free_cams[f];
+        double x = 0.0;
+        for (int w = 0; w < BA_WAVES; w++) x += lds[w * 64 * BA_SWEEP_STAGE + f * 27 + q];
+        if (q < 21) { int r = 0, qq = q; while (qq > r) { qq -= r + 1; r++; } v.cam_U[36 * j + r * 6 + qq] = x; }
+        else v.cam_ea[6 * j + (q - 21)] = x;
+      }
+      __syncthreads();                                                 // the sums sit in the staging areas the next sweep writes
+    }
+    BA_STAMP(3);
+    cur += ba_step_sweep(v_, cfg, 1, sigma2, nfree, stg, ured, camsL);
+    cur = ba_block_sum(cur, red);
+    BA_STAMP(4);
+    if (nfree > BA_FAST_FREE) { ba_accum_U_generic(v_, nfree, np); __syncthreads(); }
+    BA_STAMP(5);
+    return cur;
+  }
+  // S: diagonal blocks + E (:362-396) and off-diagonal blocks (:400-426); V*^-1 (:329-347) is formed where it is used
+  DEVFN void reduced_system(int np, int nfree, double lambda) {
+    const int nS = nfree * 6;
+    if (nfree == 0) { }                                                // only fixed cameras: no camera unknowns, the points move alone
+    else if (nfree <= BA_MFMA_FREE) ba_schur_mfma<true>(v_, np, nS, lambda, lds, 0, nfree, 0, nfree);
+    else if (nfree <= 2 * BA_MFMA_FREE) {                             // two groups of cameras: two diagonal blocks and the block between them
+      const int g0 = (nfree + 1) / 2, g1 = nfree - g0;
+      ba_schur_mfma<true>(v_, np, nS, lambda, lds, 0, g0, 0, g0);
+      ba_schur_mfma<true>(v_, np, nS, lambda, lds, g0, g1, g0, g1);
+      ba_schur_mfma<false>(v_, np, nS, lambda, lds, g0, g1, 0, g0);
+    }
+    else {
+      for (int t = threadIdx.x; t < nS * nS; t += BA_THREADS) v.S[t] = 0.0;
+      __syncthreads();
+      const int ntask = nfree + nfree * (nfree - 1) / 2;
+      for (int task = threadIdx.x >> 6; task < ntask; task += BA_WAVES) {
+        if (task < nfree) ba_task_diag(v_, task, np, nS, lambda);
+        else ba_task_pair(v_, task - nfree, np, nS, lambda);
+      }
+    }
+    __syncthreads();
+  }
+  // map updates (:440-462) and dSumSquaredUpdate (:467-470)
+  DEVFN double map_update(int np, int nfree, int nS, double lambda) {
+    double ssq = ba_map_update(v_, nfree, np, lambda, lds);
+    for (int t = threadIdx.x; t < nS; t += BA_THREADS) ssq += v.cam_up[t] * v.cam_up[t];
+    return ba_block_sum(ssq, red);
+  }
+  // FindNewError (:537-561) at the trial state: dNewError to *new_err, returns the measurements that stay (ssq is map_update's)
+  DEVFN int new_error(int M, int, int, int, double sigma2, double&, double* new_err) {
+    const BaNewError fne = ba_find_new_error(v_, cfg, M, sigma2, 1, lds);
+    const double ne = ba_block_sum(fne.ne, red);
+    if (threadIdx.x == 0) *new_err = ne;
+    return ba_block_sum_i(fne.nvalid, ired);
+  }
+};
+
+// Bundle::Compute (jni/Bundle.cc:136-178) with Do_LM_Step (:202-532) inside.  Called by all BA_THREADS threads of one workgroup.
+template <class Sums>
+DEVFN void ba_lm(const BaView& v_, const BaConfig& cfg, const BaOrdView& o) {
   const BaViewG v = ba_g(v_);
   __shared__ double red[BA_WAVES];
   __shared__ int ired[BA_WAVES];
   __shared__ int hist[768];
   __shared__ unsigned long long sel[1];
   __shared__ double sh_lambda, sh_factor, sh_sigma2, sh_cur_err, sh_new_err;
-  constexpr int LDS_MFMA = BA_WAVES * BA_MFMA_STAGE, LDS_SOLVE = BA_LDS_N * (BA_LDS_N + 1);
-  constexpr int LDS_SWEEP = BA_WAVES * 64 * BA_SWEEP_STAGE + 12 * BA_MAX_CAMS_LDS + 6 * BA_FAST_FREE;
-  constexpr int LDS_LAYOUT = (2 * 4097 * (int)sizeof(int) + 7) / 8;
-  constexpr int LDS_A = LDS_MFMA > LDS_SOLVE ? LDS_MFMA : LDS_SOLVE, LDS_B = LDS_SWEEP > LDS_LAYOUT ? LDS_SWEEP : LDS_LAYOUT;
-  __shared__ double lds_buf[LDS_A > LDS_B ? LDS_A : LDS_B];
-  double* lds_A = lds_buf;
   __shared__ int sh_converged, sh_hitmax, sh_counter, sh_accepted, sh_error, sh_nout, sh_cache_valid, sh_next_nvalid;
   BaResult AS1* R = v.res;
   const int nc = R->n_cams, np = R->n_pts, nm = R->n_meas;
@@ -1254,23 +1328,19 @@ DEVFN void ba_compute(const BaView& v_, const BaConfig& cfg) {
   __syncthreads();
   const int nfree = R->n_free, nS = nfree * 6;
   if (nfree > 64) { if (threadIdx.x == 0) { R->accepted = -1; R->converged = 0; R->hit_max = 0; R->counter = 0; R->n_outlier_meas = 0; } __syncthreads(); return; }   // pt_maskF holds 64 ordinals
-#ifdef VSLAM_BA_PROF
-  unsigned long long ba_t0 = clock64();
-#endif
-  static_assert(sizeof(lds_buf) >= 2 * 4097 * sizeof(int) && sizeof(lds_buf) >= (65536 / 32) * sizeof(unsigned) &&
-                sizeof(lds_buf) >= (size_t)LDS_SWEEP * sizeof(double), "the LDS buffer serves the layout, the step sweep and the erase");
-  ba_build_layout(v_, nc, np, ired, (int*)lds_buf);
+  Sums sums(v_, v, cfg, o, red, ired);
+  static_assert(sizeof(Sums::lds) >= 2 * 4097 * sizeof(int) && sizeof(Sums::lds) >= BA_LDS_N * (BA_LDS_N + 1) * sizeof(double) &&
+                sizeof(Sums::lds) >= (65536 / 32) * sizeof(unsigned), "Sums::lds serves the layout, the LDS solve and the erase's bit map");
+  ba_build_layout(v_, nc, np, ired, (int*)sums.lds);
   const int M = v.ch_n[3];                                            // slots = measurements of the list
-  BA_STAMP(0);
+  sums.begin(M, nm);
+  sums.stamp(0);
 
   while (!sh_converged && !sh_hitmax && !sh_error) {             // :153 (no abort signal: the map-maker runs synchronously)
     // ================= Do_LM_Step =================
-    // pass 1 (:209-215): the squared errors of the measurements still in the list, for the median
-    const bool cached = sh_cache_valid != 0;                       // the previous step was accepted: FindNewError has left them
-    int nvalid;
-    if (cached) nvalid = sh_next_nvalid;
-    else nvalid = ba_block_sum_i(ba_find_new_error(v_, cfg, M, 1.0, 0, lds_buf).nvalid, ired);
-    BA_STAMP(1);
+    const bool cached = sh_cache_valid != 0;                       // the previous step was accepted: FindNewError has left the squared errors
+    const int nvalid = cached ? sh_next_nvalid : sums.count_valid(M, nc);
+    sums.stamp(1);
     if (nvalid == 0) { if (threadIdx.x == 0) sh_error = 1; __syncthreads(); break; }
     {                                                              // :220-227 Tukey sigma, clamped
       const double med = M > 4096 ? block_radix_select<16>(v.scratch, M, nvalid / 2, hist, sel)   // (big problems: 16 values per lane in flight, 64 per lane and sweep)
@@ -1281,72 +1351,28 @@ DEVFN void ba_compute(const BaView& v_, const BaConfig& cfg) {
       __syncthreads();
     }
     const double sigma2 = sh_sigma2;
-    BA_STAMP(2);
-    // passes 1 + 2 (:209-321) in one sweep: weights, objective, V / epsilon_b, U / epsilon_a; A, B, W are re-derived by their consumers
-    double* stg = lds_buf; double* ured = nullptr; double* camsL = lds_buf + BA_WAVES * 64 * BA_SWEEP_STAGE;
-    for (int t = threadIdx.x; t < nc * 12; t += BA_THREADS) camsL[t] = ((const double AS1*)v.cam_pose)[t];   // Pose = R[9], t[3]
-    __syncthreads();
-    double cur = ba_step_sweep(v_, cfg, 0, sigma2, nfree, stg, ured, camsL);
-    __syncthreads();
-    if (nfree <= BA_FAST_FREE) {
-      for (int t = threadIdx.x; t < nfree * 27; t += BA_THREADS) {     // wave partials in wave order
-        const int f = t / 27, q = t - 27 * f, j = v.free_cams[f];
-        double x = 0.0;
-        for (int w = 0; w < BA_WAVES; w++) x += lds_buf[w * 64 * BA_SWEEP_STAGE + f * 27 + q];
-        if (q < 21) { int r = 0, qq = q; while (qq > r) { qq -= r + 1; r++; } v.cam_U[36 * j + r * 6 + qq] = x; }
-        else v.cam_ea[6 * j + (q - 21)] = x;
-      }
-      __syncthreads();                                                 // the sums sit in the staging areas the next sweep writes
-    }
-    BA_STAMP(3);
-    cur += ba_step_sweep(v_, cfg, 1, sigma2, nfree, stg, ured, camsL);
-    cur = ba_block_sum(cur, red);
-    if (threadIdx.x == 0) sh_cur_err = cur;
-    __syncthreads();
-    BA_STAMP(4);
-    if (nfree > BA_FAST_FREE) { ba_accum_U_generic(v_, nfree, np); __syncthreads(); }
-    BA_STAMP(5);
+    sums.stamp(2);
+    const double cur = sums.step(M, nc, np, nfree, sigma2);
     // ---- inner loop over lambda (:326-501) ----
-    if (threadIdx.x == 0) sh_new_err = sh_cur_err + 9999;
+    if (threadIdx.x == 0) { sh_cur_err = cur; sh_new_err = cur + 9999; }
     __syncthreads();
     while (sh_new_err > sh_cur_err && !sh_converged && !sh_hitmax && !sh_error) {
       const double lambda = sh_lambda;
-      BA_STAMP(6);
-      // S: diagonal blocks + E (:362-396) and off-diagonal blocks (:400-426); V*^-1 (:329-347) is formed where it is used
-      if (nfree == 0) { }                                              // only fixed cameras: no camera unknowns, the points move alone
-      else if (nfree <= BA_MFMA_FREE) ba_schur_mfma<true>(v_, np, nS, lambda, lds_buf, 0, nfree, 0, nfree);
-      else if (nfree <= 2 * BA_MFMA_FREE) {                           // two groups of cameras: two diagonal blocks and the block between them
-        const int g0 = (nfree + 1) / 2, g1 = nfree - g0;
-        ba_schur_mfma<true>(v_, np, nS, lambda, lds_buf, 0, g0, 0, g0);
-        ba_schur_mfma<true>(v_, np, nS, lambda, lds_buf, g0, g1, g0, g1);
-        ba_schur_mfma<false>(v_, np, nS, lambda, lds_buf, g0, g1, 0, g0);
-      }
-      else {
-        for (int t = threadIdx.x; t < nS * nS; t += BA_THREADS) v.S[t] = 0.0;
-        __syncthreads();
-        const int ntask = nfree + nfree * (nfree - 1) / 2;
-        for (int task = wave; task < ntask; task += BA_WAVES) {
-          if (task < nfree) ba_task_diag(v_, task, np, nS, lambda);
-          else ba_task_pair(v_, task - nfree, np, nS, lambda);
-        }
-      }
-      __syncthreads();
-      BA_STAMP(7);
+      sums.stamp(6);
+      sums.reduced_system(np, nfree, lambda);
+      sums.stamp(7);
       bool solved = true;
-      if (nS > 0 && nS <= BA_WSOLVE_N && VSLAM_BA_WSOLVE) {           // one wavefront, registers (the BundleAdjustRecent size)
+      if (nS > 0 && nS <= BA_WSOLVE_N) {                               // one wavefront, registers (the BundleAdjustRecent size)
         if (wave == 0) { const bool okw = ba_solve_wave(v_, nS); if (lane == 0) ired[0] = okw ? 1 : 0; }
         __syncthreads();
         solved = ired[0] != 0;
         __syncthreads();
-      } else if (nS > 0) solved = nS <= BA_LDS_N ? ba_block_solve_lds((const double*)v.S, (double*)v.E, nS, lds_A, ired) : ba_block_solve((double*)v.S, (double*)v.E, nS, ired);
+      } else if (nS > 0) solved = nS <= BA_LDS_N ? ba_block_solve_lds<Sums::ordered>((const double*)v.S, (double*)v.E, nS, sums.lds, ired) : ba_block_solve((double*)v.S, (double*)v.E, nS, ired);
       if (!solved) { if (threadIdx.x == 0) sh_error = 1; __syncthreads(); break; }
       for (int t = threadIdx.x; t < nS; t += BA_THREADS) v.cam_up[t] = v.E[t];
       __syncthreads();
-      BA_STAMP(8);
-      // map updates (:440-462)
-      double ssq = ba_map_update(v_, nfree, np, lambda, lds_buf);
-      for (int t = threadIdx.x; t < nS; t += BA_THREADS) ssq += v.cam_up[t] * v.cam_up[t];
-      ssq = ba_block_sum(ssq, red);                                    // :467-470
+      sums.stamp(8);
+      double ssq = sums.map_update(np, nfree, nS, lambda);
       for (int j = threadIdx.x; j < nc; j += BA_THREADS) {             // :476-482
         const Pose Tj = ba_load_pose(v.cam_pose + j);
         if (v.cam_fixed[j]) ba_store_pose(v.cam_new + j, Tj);
@@ -1357,17 +1383,13 @@ DEVFN void ba_compute(const BaView& v_, const BaConfig& cfg) {
         }
       }
       __syncthreads();
-      BA_STAMP(9);
-      // FindNewError (:537-561)
-      const BaNewError fne = ba_find_new_error(v_, cfg, M, sigma2, 1, lds_buf);
-      const double ne = ba_block_sum(fne.ne, red);
-      const int nv_next = ba_block_sum_i(fne.nvalid, ired);
-      BA_STAMP(10);
+      sums.stamp(9);
+      const int nv_next = sums.new_error(M, nc, np, nS, sh_sigma2, ssq, &sh_new_err);
+      sums.stamp(10);
       if (threadIdx.x == 0) {
         sh_next_nvalid = nv_next;
         if (ssq < cfg.convergence_limit) sh_converged = 1;
-        sh_new_err = ne;
-        if (ne > sh_cur_err) { sh_lambda = sh_lambda * sh_factor; sh_factor = sh_factor * 2; }   // ModifyLambda_BadStep :614-617
+        if (sh_new_err > sh_cur_err) { sh_lambda = sh_lambda * sh_factor; sh_factor = sh_factor * 2; }   // ModifyLambda_BadStep :614-617
         sh_counter++; R->trials++;
         if (sh_counter >= cfg.max_iterations) sh_hitmax = 1;           // :498-500
       }
@@ -1380,14 +1402,14 @@ DEVFN void ba_compute(const BaView& v_, const BaConfig& cfg) {
       if (threadIdx.x == 0) { sh_factor = 2.0; sh_lambda *= 0.3; sh_accepted++; sh_cache_valid = 1; }   // ModifyLambda_GoodStep :609-612
     } else if (threadIdx.x == 0) sh_cache_valid = 0;
     __syncthreads();
-    BA_STAMP(11);
+    sums.stamp(11);
     {                                                                  // erase the outliers in list order (:517-528)
-      const int no = ba_erase_outliers(v_, M, nm, sh_nout, (unsigned*)lds_buf, ired);
+      const int no = ba_erase_outliers(v_, M, nm, sh_nout, (unsigned*)sums.lds, ired);
       __syncthreads();
       if (threadIdx.x == 0) sh_nout = no;
       __syncthreads();
     }
-    BA_STAMP(12);
+    sums.stamp(12);
   }
   if (threadIdx.x == 0) {
     R->accepted = sh_error ? -1 : sh_accepted;                         // :170-177

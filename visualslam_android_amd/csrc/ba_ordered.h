@@ -252,110 +252,44 @@ DEVFN void ord_map_update(const BaViewG& v, const BaOrdView& o, int np, double l
   }
 }
 
-// ba_block_solve_lds with the back-substitution of the reference-order mode: the elimination updates every element independently
-// (the same multiply / subtract per element as lu_solve, whatever thread does it), but the fast path's back-substitution sums a row's
-// products across lanes; here one lane subtracts them in ascending column order.
-DEVFN bool ord_solve_lds(const double* S, double* E, int n, double* A, int* ired) {
-  const int ld = n + 1, lane = threadIdx.x & 63;
-  for (int t = threadIdx.x; t < n * ld; t += blockDim.x) { const int r = t / ld, c = t - r * ld; A[t] = c < n ? S[(size_t)r * n + c] : E[r]; }
-  __syncthreads();
-  for (int k = 0; k < n; k++) {
-    if (threadIdx.x < 64) {                                        // partial pivoting: first row of maximal |A[r][k]|, r >= k
-      double best = -1.0; int piv = k;
-      for (int r = k + lane; r < n; r += 64) { const double a = fabs(A[r * ld + k]); if (a > best) { best = a; piv = r; } }
-      for (int d = 32; d > 0; d >>= 1) {
-        const double ob = __shfl_xor(best, d); const int op = __shfl_xor(piv, d);
-        if (ob > best || (ob == best && op < piv)) { best = ob; piv = op; }
-      }
-      if (lane == 0) ired[0] = best == 0.0 ? -1 : piv;
-    }
-    __syncthreads();
-    const int piv = ired[0];
-    if (piv < 0) return false;
-    if (piv != k) for (int c = threadIdx.x; c < ld; c += blockDim.x) { const double t = A[k * ld + c]; A[k * ld + c] = A[piv * ld + c]; A[piv * ld + c] = t; }
-    __syncthreads();
-    const double inv = 1.0 / A[k * ld + k];
-    const int rem = n - k - 1, wid = ld - k - 1;
-    for (int t = threadIdx.x; t < rem * wid; t += blockDim.x) {
-      const int r = k + 1 + t / wid, c = k + 1 + t % wid;
-      const double f = A[r * ld + k] * inv;
-      A[r * ld + c] -= f * A[k * ld + c];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0)
-    for (int k = n - 1; k >= 0; k--) {
-      double s = A[k * ld + n];
-      for (int c = k + 1; c < n; c++) s -= A[k * ld + c] * A[c * ld + n];
-      A[k * ld + n] = s / A[k * ld + k];
-    }
-  __syncthreads();
-  for (int t = threadIdx.x; t < n; t += blockDim.x) E[t] = A[t * ld + n];
-  __syncthreads();
-  return true;
-}
-
-DEVFN void ba_compute_ordered(const BaView& v_, const BaConfig& cfg, const BaOrdView& o) {
-  const BaViewG v = ba_g(v_);
-  __shared__ int ired[BA_WAVES];
-  __shared__ int hist[768];
-  __shared__ unsigned long long sel[1];
-  __shared__ double sh_lambda, sh_factor, sh_sigma2, sh_cur_err, sh_new_err, sh_ssq;
-  constexpr int LDS_SOLVE = BA_LDS_N * (BA_LDS_N + 1), LDS_LAYOUT = (2 * 4097 * (int)sizeof(int) + 7) / 8;
-  __shared__ double lds_buf[LDS_SOLVE > LDS_LAYOUT ? LDS_SOLVE : LDS_LAYOUT];
-  __shared__ double camL[12 * 128];                                 // every camera of a problem (at most 128 keyframes per map)
-  __shared__ int sh_converged, sh_hitmax, sh_counter, sh_accepted, sh_error, sh_nout, sh_cache_valid, sh_next_nvalid;
-  static_assert(sizeof(lds_buf) >= (65536 / 32) * sizeof(unsigned), "the LDS buffer also serves the erase's bit map");
-  BaResult AS1* R = v.res;
-  const int nc = R->n_cams, np = R->n_pts, nm = R->n_meas;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) {
-    int nf = 0, row = 0;
-    for (int j = 0; j < nc; j++) {            // AddCamera start rows, jni/Bundle.cc:79-85
-      if (!v.cam_fixed[j]) { v.cam_row[j] = row; row += 6; v.free_cams[nf++] = j; } else v.cam_row[j] = -999999999;
-    }
-    R->n_free = nf;
-    sh_lambda = 0.0001; sh_factor = 2.0;      // :144-145
-    sh_converged = 0; sh_hitmax = 0; sh_counter = 0; sh_accepted = 0; sh_error = 0; sh_nout = 0; sh_sigma2 = 0; sh_cache_valid = 0;
-    R->trials = 0;
-  }
-  __syncthreads();
-  const int nfree = R->n_free, nS = nfree * 6;
-  if (nfree > 64) { if (threadIdx.x == 0) { R->accepted = -1; R->converged = 0; R->hit_max = 0; R->counter = 0; R->n_outlier_meas = 0; } __syncthreads(); return; }
-  ba_build_layout(v_, nc, np, ired, (int*)lds_buf);
-  const int M = v.ch_n[3], MF = v.ch_n[2];
-  for (int i = threadIdx.x; i < nm; i += BA_THREADS) o.of_logical[i] = -1;
-  __syncthreads();
-  for (int s = threadIdx.x; s < M; s += BA_THREADS) o.of_logical[v.sl_logical[s]] = s;
-  __syncthreads();
-  auto load_cams = [&](const Pose AS1* src) {
+// The Sums of ba_lm<> (ba_device.h) in the reference-order mode.  Its phases read the cameras from camL, reloaded from the committed
+// or the trial poses by the phase that projects with them.
+struct BaOrdSums {
+  static constexpr bool ordered = true;
+  static constexpr int LDS_SOLVE = BA_LDS_N * (BA_LDS_N + 1), LDS_LAYOUT = (2 * 4097 * (int)sizeof(int) + 7) / 8;
+  static constexpr int LDS_DOUBLES = LDS_SOLVE > LDS_LAYOUT ? LDS_SOLVE : LDS_LAYOUT;
+  const BaView& v_; const BaViewG& v; const BaConfig& cfg; const BaOrdView& o;
+  int* ired;                                                           // the driver's reduction scratch
+  static __shared__ double lds[LDS_DOUBLES];                           // the driver's layout, solve and erase
+  static __shared__ double camL[12 * 128];                             // every camera of a problem (at most 128 keyframes per map)
+  static __shared__ double ssq_;                                       // dSumSquaredUpdate, from the lane that walks it to the driver
+  int nm, MF;
+  DEVFN BaOrdSums(const BaView& v_, const BaViewG& v, const BaConfig& cfg, const BaOrdView& o, double*, int* ired) : v_(v_), v(v), cfg(cfg), o(o), ired(ired) {}
+  DEVFN void stamp(int) {}
+  DEVFN void load_cams(const Pose AS1* src, int nc) {
     __syncthreads();
     for (int t = threadIdx.x; t < nc * 12; t += BA_THREADS) camL[t] = ((const double AS1*)src)[t];
     __syncthreads();
-  };
-
-  while (!sh_converged && !sh_hitmax && !sh_error) {             // :153
-    // ================= Do_LM_Step =================
-    load_cams(v.cam_pose);
-    const bool cached = sh_cache_valid != 0;                       // the previous step was accepted: FindNewError has left the squared errors
-    int nvalid;
-    if (cached) nvalid = sh_next_nvalid;
-    else nvalid = ba_block_sum_i(ord_errors(v, cfg, o, M, 1.0, 0, camL), ired);
-    if (nvalid == 0) { if (threadIdx.x == 0) sh_error = 1; __syncthreads(); break; }
-    {                                                              // :220-227
-      const double med = M > 4096 ? block_radix_select<16>(v.scratch, M, nvalid / 2, hist, sel)   // (big problems: 16 values per lane in flight, 64 per lane and sweep)
-                                  : block_radix_select<8>(v.scratch, M, nvalid / 2, hist, sel);
-      double s2 = tukey_sigma_squared(med, (unsigned long)nvalid);
-      if (s2 < cfg.min_sigma2) s2 = cfg.min_sigma2;
-      if (threadIdx.x == 0) sh_sigma2 = s2;
-      __syncthreads();
-    }
-    const double sigma2 = sh_sigma2;
+  }
+  DEVFN void begin(int M, int nm_) {                                   // behind the layout: list index -> slot
+    nm = nm_; MF = v.ch_n[2];
+    for (int i = threadIdx.x; i < nm; i += BA_THREADS) o.of_logical[i] = -1;
+    __syncthreads();
+    for (int s = threadIdx.x; s < M; s += BA_THREADS) o.of_logical[v.sl_logical[s]] = s;
+    __syncthreads();
+  }
+  DEVFN int count_valid(int M, int nc) {                                       // pass 1 (:209-215)
+    load_cams(v.cam_pose, nc);
+    return ba_block_sum_i(ord_errors(v, cfg, o, M, 1.0, 0, camL), ired);
+  }
+  DEVFN double step(int M, int nc, int np, int nfree, double sigma2) {
+    load_cams(v.cam_pose, nc);
     ord_sweep(v, cfg, o, M, MF, sigma2, camL);
     __syncthreads();
+    double cur = 0.0;
     for (int task = threadIdx.x; task < 1 + 27 * nfree; task += BA_THREADS) {      // dCurrentError; U, epsilon_a
       const double x = ord_list_chain(v, o, nm, MF, task);
-      if (task == 0) sh_cur_err = x;
+      if (task == 0) cur = x;
       else {
         const int f = (task - 1) / 27, q = (task - 1) - 27 * f, j = v.free_cams[f];
         if (q < 21) { int r = 0, qq = q; while (qq > r) { qq -= r + 1; r++; } v.cam_U[36 * j + r * 6 + qq] = x; }
@@ -364,78 +298,35 @@ DEVFN void ba_compute_ordered(const BaView& v_, const BaConfig& cfg, const BaOrd
     }
     ord_point_sums(v, o, np, MF);                                   // V, epsilon_b
     __syncthreads();
-    // ---- inner loop over lambda (:326-501) ----
-    if (threadIdx.x == 0) sh_new_err = sh_cur_err + 9999;
-    __syncthreads();
-    while (sh_new_err > sh_cur_err && !sh_converged && !sh_hitmax && !sh_error) {
-      const double lambda = sh_lambda;
-      ord_trial_operands(v, o, np, MF, lambda);
-      __syncthreads();
-      const int ntask = 27 * nfree + 36 * (nfree * (nfree - 1) / 2);
-      for (int task = threadIdx.x; task < ntask; task += BA_THREADS) ord_schur_chain(v, o, np, nfree, nS, lambda, task);
-      __syncthreads();
-      bool solved = true;
-      if (nS > 0 && nS <= BA_WSOLVE_N) {
-        if (wave == 0) { const bool okw = ba_solve_wave(v_, nS); if (lane == 0) ired[0] = okw ? 1 : 0; }
-        __syncthreads();
-        solved = ired[0] != 0;
-        __syncthreads();
-      } else if (nS > 0) solved = nS <= BA_LDS_N ? ord_solve_lds((const double*)v.S, (double*)v.E, nS, lds_buf, ired) : ba_block_solve((double*)v.S, (double*)v.E, nS, ired);
-      if (!solved) { if (threadIdx.x == 0) sh_error = 1; __syncthreads(); break; }
-      for (int t = threadIdx.x; t < nS; t += BA_THREADS) v.cam_up[t] = v.E[t];
-      __syncthreads();
-      ord_map_update(v, o, np, lambda);
-      for (int j = threadIdx.x; j < nc; j += BA_THREADS) {             // :476-482
-        const Pose Tj = ba_load_pose(v.cam_pose + j);
-        if (v.cam_fixed[j]) ba_store_pose(v.cam_new + j, Tj);
-        else {
-          double mu[6];
-          _Pragma("unroll") for (int k = 0; k < 6; k++) mu[k] = v.cam_up[v.cam_row[j] + k];
-          ba_store_pose(v.cam_new + j, pose_mul(se3_exp(mu), Tj));
-        }
-      }
-      __syncthreads();
-      load_cams(v.cam_new);
-      const int nv_next = ba_block_sum_i(ord_errors(v, cfg, o, M, sh_sigma2, 1, camL), ired);   // FindNewError's terms (:537-561)
-      if (threadIdx.x == 0) {                                          // dSumSquaredUpdate (:467-470): the camera updates, then the points'
-        double acc = 0.0;
-        for (int t = 0; t < nS; t++) { const double x = v.cam_up[t]; acc += x * x; }
-        for (int t0 = 0; t0 < 3 * np; t0 += ORD_PF) {
-          double x[ORD_PF];
-          _Pragma("unroll") for (int u = 0; u < ORD_PF; u++) x[u] = t0 + u < 3 * np ? o.up[t0 + u] : 0.0;
-          _Pragma("unroll") for (int u = 0; u < ORD_PF; u++) acc += x[u] * x[u];
-        }
-        sh_ssq = acc;
-      }
-      if (threadIdx.x == 64) sh_new_err = ord_list_chain(v, o, nm, MF, 0);   // dNewError in list order (another wavefront, beside the chain above)
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        sh_next_nvalid = nv_next;
-        if (sh_ssq < cfg.convergence_limit) sh_converged = 1;
-        if (sh_new_err > sh_cur_err) { sh_lambda = sh_lambda * sh_factor; sh_factor = sh_factor * 2; }   // ModifyLambda_BadStep :614-617
-        sh_counter++; R->trials++;
-        if (sh_counter >= cfg.max_iterations) sh_hitmax = 1;           // :498-500
-      }
-      __syncthreads();
-    }
-    if (sh_error) break;
-    if (sh_new_err < sh_cur_err) {                                     // :503-514
-      for (int j = threadIdx.x; j < nc; j += BA_THREADS) ba_store_pose(v.cam_pose + j, ba_load_pose(v.cam_new + j));
-      for (int t = threadIdx.x; t < 3 * np; t += BA_THREADS) v.pt_pos[t] = v.pt_new[t];
-      if (threadIdx.x == 0) { sh_factor = 2.0; sh_lambda *= 0.3; sh_accepted++; sh_cache_valid = 1; }   // ModifyLambda_GoodStep :609-612
-    } else if (threadIdx.x == 0) sh_cache_valid = 0;
-    __syncthreads();
-    {                                                                  // erase the outliers in list order (:517-528)
-      const int no = ba_erase_outliers(v_, M, nm, sh_nout, (unsigned*)lds_buf, ired);
-      __syncthreads();
-      if (threadIdx.x == 0) sh_nout = no;
-      __syncthreads();
-    }
+    return cur;
   }
-  if (threadIdx.x == 0) {
-    R->accepted = sh_error ? -1 : sh_accepted;                         // :170-177
-    R->converged = sh_converged; R->hit_max = sh_hitmax; R->counter = sh_counter;
-    R->sigma2 = sh_sigma2; R->lambda = sh_lambda; R->lambda_factor = sh_factor; R->n_outlier_meas = sh_nout;
+  DEVFN void reduced_system(int np, int nfree, double lambda) {
+    const int nS = nfree * 6;
+    ord_trial_operands(v, o, np, MF, lambda);
+    __syncthreads();
+    const int ntask = 27 * nfree + 36 * (nfree * (nfree - 1) / 2);
+    for (int task = threadIdx.x; task < ntask; task += BA_THREADS) ord_schur_chain(v, o, np, nfree, nS, lambda, task);
+    __syncthreads();
   }
-  __syncthreads();
-}
+  DEVFN double map_update(int np, int, int, double lambda) { ord_map_update(v, o, np, lambda); return 0.0; }   // (the sum: new_error)
+  // FindNewError's terms (:537-561); then two lanes of different wavefronts walk their chains side by side: dSumSquaredUpdate
+  // (:467-470: the camera updates, then the points') and dNewError in list order
+  DEVFN int new_error(int M, int nc, int np, int nS, double sigma2, double& ssq, double* new_err) {
+    load_cams(v.cam_new, nc);
+    const int nv = ba_block_sum_i(ord_errors(v, cfg, o, M, sigma2, 1, camL), ired);
+    if (threadIdx.x == 0) {
+      double acc = 0.0;
+      for (int t = 0; t < nS; t++) { const double x = v.cam_up[t]; acc += x * x; }
+      for (int t0 = 0; t0 < 3 * np; t0 += ORD_PF) {
+        double x[ORD_PF];
+        _Pragma("unroll") for (int u = 0; u < ORD_PF; u++) x[u] = t0 + u < 3 * np ? o.up[t0 + u] : 0.0;
+        _Pragma("unroll") for (int u = 0; u < ORD_PF; u++) acc += x[u] * x[u];
+      }
+      ssq_ = acc;
+    }
+    if (threadIdx.x == 64) *new_err = ord_list_chain(v, o, nm, MF, 0);
+    __syncthreads();
+    ssq = ssq_;
+    return nv;
+  }
+};
