@@ -77,8 +77,8 @@ struct KeyFrame {
     vslam_detail::check(vslam_make_keyframe_lite(sys, im.data, im.step, 0, 0));
     vslam_detail::check(vslam_synchronize(sys));
   }
-  // jni/KeyFrame.cc:53-95: fast_nonmax + Shi-Tomasi candidates (gvdCandidateMinSTScore = 70); the SmallBlurryImage
-  // of the relocaliser is not built.
+  // jni/KeyFrame.cc:53-95: fast_nonmax + Shi-Tomasi candidates (gvdCandidateMinSTScore = 70); the SmallBlurryImage of the
+  // relocaliser (:97-100) is made on the device when a frame becomes a keyframe of a system with vslam_params.relocalise.
   void MakeKeyFrame_Rest() { vslam_detail::check(vslam_make_keyframe_rest(sys, 70.0)); }
   struct Candidate { int x, y; double dSTScore; };                  // jni/KeyFrame.h:36-43 (irLevelPos, dSTScore)
   std::vector<Candidate> Candidates(int level) const {              // Level::vCandidates
@@ -143,6 +143,30 @@ class MapMaker {
  protected:
   Map& mMap;
   ATANCamera mCamera;
+};
+
+// jni/Relocaliser.h:18-37.  The work is the device's (vslam_attempt_recovery; a system created with vslam_params.relocalise runs it
+// inside every TrackFrame for a lost stream, jni/Tracker.cc:133-139); this handle makes the call and reports the result.
+class Relocaliser {
+ public:
+  Relocaliser(Map& map, const ATANCamera&) : mMap(map) {}
+  bool AttemptRecovery(KeyFrame& /*kCurrent*/) {                    // jni/Relocaliser.cc:17-42, on the device's current frame
+    int before[4], after[4]; double d[24];
+    vslam_detail::check(vslam_get_reloc_info(mMap.sys, 0, before, d));
+    vslam_detail::check(vslam_attempt_recovery(mMap.sys));
+    vslam_detail::check(vslam_get_reloc_info(mMap.sys, 0, after, d));
+    return after[1] > before[1];
+  }
+  mySE3 BestPose() {                                                 // :13-15 mse3Best
+    int i[4]; double d[24];
+    vslam_detail::check(vslam_get_reloc_info(mMap.sys, 0, i, d));
+    mySE3 T; memcpy(T.R, d + 8, sizeof(T.R)); memcpy(T.t, d + 17, sizeof(T.t));
+    return T;
+  }
+  int BestKeyFrame() { int i[4]; double d[24]; vslam_detail::check(vslam_get_reloc_info(mMap.sys, 0, i, d)); return i[2]; }     // mnBest
+  double BestScore() { int i[4]; double d[24]; vslam_detail::check(vslam_get_reloc_info(mMap.sys, 0, i, d)); return d[0]; }     // mdBestScore
+ protected:
+  Map& mMap;
 };
 
 // jni/Tracker.h:43-150 (public surface).

@@ -99,6 +99,12 @@ typedef struct vslam_params {
                                       matrix-core products (results within ~1e-10 of the reference's loops).  1: every sum in the order of the
                                       reference's loops (jni/Bundle.cc:241-321, 362-470, 537-561) -- same results as the reference's sequential
                                       code bit for bit, several times slower: the parity mode */
+  int relocalise;                  /* 1: the relocaliser (jni/Relocaliser.cc, jni/Tracker.cc:133-139, 163-175): every keyframe keeps a SmallBlurryImage
+                                      (jni/KeyFrame.cc:97-100; 12 * (width/16) * (height/16) bytes each, max_keyframes per stream) and a stream that has
+                                      been lost for three frames attempts a recovery in every frame (vslam_attempt_recovery).  0 (default): a lost stream
+                                      stays lost, no kernel is launched and nothing is allocated for it */
+  double reloc_blur;               /* jni/SmallBlurryImage.h:19-20 dBlur of the relocaliser's images: 2.5.  <= 2: 9 x 9 Gaussian, > 2: 17 x 17
+                                      (jni/SmallBlurryImage.cc:51-54) */
 } vslam_params;
 
 const char* vslam_last_error(void);
@@ -140,7 +146,8 @@ int vslam_read_max_corners(vslam_system* sys, int stream, int level, uint32_t* c
 /* KeyFrame::MakeKeyFrame_Rest (jni/KeyFrame.cc:53-95) for the current frame of every stream: fast_nonmax on the four levels,
  * then the candidate list -- maximal corners inside the 10-px border whose Shi-Tomasi score (half-window 3,
  * jni/vision/ImageHandler.cpp:124-155) exceeds min_shi_tomasi_score (reference: 70, :57).  The SmallBlurryImage part of the
- * function belongs to the relocaliser and is not built. */
+ * function (:97-100) belongs to the relocaliser: with vslam_params.relocalise it is made when a frame becomes a keyframe
+ * (vslam_read_keyframe_sbi), not here. */
 int vslam_make_keyframe_rest(vslam_system* sys, double min_shi_tomasi_score);
 /* MapMaker::ThinCandidates (jni/MapMaker.cc:393-422) on all four levels of the current candidate lists, against the
  * measurements of `keyframe` of each stream (keyframe < 0: the tracker's measurements of the current frame, i.e. what
@@ -154,6 +161,18 @@ int vslam_get_keyframe_corners(vslam_system* sys, int stream, int keyframe, int 
 /* use_sbi = 1: the SmallBlurryImage of the current frame (jni/SmallBlurryImage.cc:20-55: (w/16) x (h/16) u8 image and its
  * zero-mean blurred fp32 template) and rot8 = { mv6SBIRot[6] (jni/Tracker.cc:885-893), final ESM score, 0 }. */
 int vslam_read_sbi(vslam_system* sys, int stream, uint8_t* small_img, float* tmpl, double rot8[8]);
+/* relocalise = 1: KeyFrame::pSBI of a keyframe of the map (jni/KeyFrame.cc:97-100, jni/SmallBlurryImage.cc:20-79): mimTemplate
+ * ((w/16) x (h/16) floats) and mimImageJacs (two floats per pixel).  Either pointer may be NULL.  VSLAM_E_STATE with relocalise = 0. */
+int vslam_read_keyframe_sbi(vslam_system* sys, int stream, int keyframe, float* tmpl, float* jacs);
+/* relocalise = 1: the relocaliser's members (jni/Relocaliser.h) for a stream.  out_i = AttemptRecovery calls so far, those that returned
+ * true, mnBest and the frame number of the last call; out_d = mdBestScore (jni/Relocaliser.cc:46-58), the final score of
+ * IteratePosRelToTarget (:29-31), ln of SE3fromSE2's result (6; the quantity vslam_read_sbi reports as rot8), mse3Best (:34) as R row-major
+ * (9) + t (3), four zeros.  VSLAM_E_STATE with relocalise = 0. */
+int vslam_get_reloc_info(vslam_system* sys, int stream, int out_i[4], double out_d[24]);
+/* relocalise = 1: the images of the stream's last AttemptRecovery: kCurrent.pSBI->mimTemplate (jni/Relocaliser.cc:20-23) and the ZMSSD of
+ * every keyframe ScoreKFs computed (:51-57; the first `cap`).  Returns the number of keyframes scored.  Either pointer may be NULL.
+ * VSLAM_E_STATE with relocalise = 0 or before the first attempt. */
+int vslam_read_reloc_attempt(vslam_system* sys, int stream, float* cur_tmpl, double* zmssd, int cap);
 
 /* ---- MiniPatch (jni/MiniPatch.cc), the primitives of the reference's trail tracking ------------- */
 /* MiniPatch::SampleFromImage (:71-83): 9x9 patches around n integer positions of the current frame's level 0
@@ -230,10 +249,18 @@ int vslam_track_frame(vslam_system* sys, const uint8_t* gray, size_t row_stride,
  *                               UpdateMotionModel (:802-820), AssessTrackingQuality (:832-878), the keyframe decision (:128-132);
  *   vslam_finish_frame(sys)     MapMaker::AddKeyFrame + BundleAdjustRecent for the streams whose tracker asked for a keyframe.
  * vslam_track_frame is exactly this sequence.  All asynchronous; the tracker state between two stages is read with
- * vslam_get_state / vslam_get_point_tracks / vslam_get_template (pose = the tracker's current estimate) . */
+ * vslam_get_state / vslam_get_point_tracks / vslam_get_template (pose = the tracker's current estimate) .
+ * With vslam_params.relocalise, vslam_attempt_recovery comes between vslam_make_keyframe_lite and vslam_patch_search(sys, 0). */
 int vslam_patch_search(vslam_system* sys, int stage);
 int vslam_pose_update(vslam_system* sys, int stage);
 int vslam_finish_frame(vslam_system* sys);
+/* Tracker::AttemptRecovery (jni/Tracker.cc:163-175) with Relocaliser::AttemptRecovery (jni/Relocaliser.cc:17-58) for the streams that have a
+ * map and have been lost for three frames (jni/Tracker.cc:133-139), on the current frame, before vslam_patch_search(sys, 0): the frame's
+ * SmallBlurryImage at reloc_blur, ScoreKFs (ZMSSD against every keyframe's, jni/SmallBlurryImage.cc:82-94), IteratePosRelToTarget(best, 6),
+ * SE3fromSE2.  A final score below 9e6 sets the pose to mse3Best, the velocity to zero and mbJustRecoveredSoUseCoarse; that frame then runs
+ * TrackMap and AssessTrackingQuality only (no motion model, no keyframe).  The other streams are not touched.  Does nothing with
+ * vslam_params.relocalise = 0.  vslam_track_frame calls it.  Asynchronous. */
+int vslam_attempt_recovery(vslam_system* sys);
 /* the JNI-equivalent per-frame entry: native_update (jni/jni_part.cpp:132-145): host gray image of stream 0..n-1,
  * synchronous; native_touchScreen (:120-124) = the spacebar of every stream: with vslam_params.bootstrap it starts the trails / runs
  * InitFromStereo on the next frame of the streams that have no map, otherwise (and once a map exists) it has no effect. */

@@ -33,6 +33,7 @@ class Params(C.Structure):
         ("ba_min_tukey_sigma", C.c_double), ("ba_window", C.c_int), ("ba_min_keyframes", C.c_int),
         ("cam", C.c_double * 5), ("quirks", C.c_int), ("device", C.c_int), ("ba_delay_frames", C.c_int),
         ("grow_map", C.c_int), ("ba_batch_frames", C.c_int), ("idle_iterations", C.c_int), ("bootstrap", C.c_int), ("ba_sum_order", C.c_int),
+        ("relocalise", C.c_int), ("reloc_blur", C.c_double),
     ]
 
 
@@ -67,6 +68,10 @@ SYMBOLS = {
     "vslam_read_max_corners": (_i, [_sys, _i, _i, _vp, _vp, _i, _ip]),
     "vslam_get_keyframe_corners": (_i, [_sys, _i, _i, _i, _vp, _i, _ip]),
     "vslam_read_sbi": (_i, [_sys, _i, _vp, _vp, _vp]),
+    "vslam_read_keyframe_sbi": (_i, [_sys, _i, _i, _vp, _vp]),
+    "vslam_get_reloc_info": (_i, [_sys, _i, _vp, _vp]),
+    "vslam_read_reloc_attempt": (_i, [_sys, _i, _vp, _vp, _i]),
+    "vslam_attempt_recovery": (_i, [_sys]),
     "vslam_make_keyframe_rest": (_i, [_sys, C.c_double]),
     "vslam_thin_candidates": (_i, [_sys, _i]),
     "vslam_read_candidates": (_i, [_sys, _i, _i, _vp, _vp, _i, _ip]),
@@ -440,6 +445,33 @@ class System:
         small = np.zeros((hs, ws), np.uint8); tmpl = np.zeros((hs, ws), np.float32); rot = np.zeros(8)
         _check(self.lib.vslam_read_sbi(self.h, stream, small.ctypes.data, tmpl.ctypes.data, rot.ctypes.data))
         return small, tmpl, rot[:6].copy(), float(rot[6])
+
+    # ---- relocaliser (vslam_params.relocalise) ------------------------------------------------
+    def attempt_recovery(self):
+        """Tracker::AttemptRecovery for the lost streams, between make_keyframe_lite and patch_search(0) (vslam_attempt_recovery)"""
+        _check(self.lib.vslam_attempt_recovery(self.h))
+
+    def keyframe_sbi(self, stream, keyframe):
+        """-> (mimTemplate [h/16, w/16] float32, mimImageJacs [h/16, w/16, 2] float32) of a keyframe's SmallBlurryImage"""
+        hs, ws = self.params.height // 16, self.params.width // 16
+        tmpl = np.zeros((hs, ws), np.float32); jacs = np.zeros((hs, ws, 2), np.float32)
+        _check(self.lib.vslam_read_keyframe_sbi(self.h, stream, int(keyframe), tmpl.ctypes.data, jacs.ctypes.data))
+        return tmpl, jacs
+
+    def reloc_info(self, stream):
+        """-> the relocaliser's members of a stream (vslam_get_reloc_info) as a dict"""
+        oi = np.zeros(4, np.int32); od = np.zeros(24)
+        _check(self.lib.vslam_get_reloc_info(self.h, stream, oi.ctypes.data, od.ctypes.data))
+        return {"attempts": int(oi[0]), "successes": int(oi[1]), "best": int(oi[2]), "frame": int(oi[3]), "best_zmssd": float(od[0]),
+                "score": float(od[1]), "ln_adj": od[2:8].copy(), "best_pose": od[8:20].copy()}
+
+    def reloc_attempt(self, stream):
+        """-> (the current frame's template, the ZMSSD of every keyframe) of the stream's last recovery attempt"""
+        hs, ws = self.params.height // 16, self.params.width // 16
+        K = self.params.max_keyframes
+        tmpl = np.zeros((hs, ws), np.float32); sc = np.zeros(K)
+        n = _check(self.lib.vslam_read_reloc_attempt(self.h, stream, tmpl.ctypes.data, sc.ctypes.data, K))
+        return tmpl, sc[:n].copy()
 
     def make_keyframe_rest(self, min_score=70.0):
         _check(self.lib.vslam_make_keyframe_rest(self.h, float(min_score)))

@@ -852,6 +852,7 @@ int ba_run(vslam_system* sys, int mode, bool host_driven_keyframe) {
     KfCopyArgs a; fill_kfcopy(sys, a);
     prof_mark(sys, 10);
     hipLaunchKernelGGL(k_add_keyframe, dim3(32, sys->S), dim3(256), 0, sys->stream, sys->map, sys->tp, a);
+    { int rs = reloc_keyframe_sbi_pending(sys); if (rs) return rs; }   // MakeKeyFrame_Rest's SmallBlurryImage (jni/KeyFrame.cc:97-100; vslam_params.relocalise)
     int rg = grow_on_keyframe(sys);                      // AddSomeMapPoints (vslam_params.grow_map), before the bundle adjustment sees the keyframe
     if (rg) return rg;
   }
@@ -908,7 +909,7 @@ int ba_launch_add_keyframe(vslam_system* sys) {
   KfCopyArgs a; fill_kfcopy(sys, a);
   hipLaunchKernelGGL(k_add_keyframe, dim3(32, sys->S), dim3(256), 0, sys->stream, sys->map, sys->tp, a);
   HIPCHK(hipGetLastError());
-  return VSLAM_OK;
+  return reloc_keyframe_sbi_pending(sys);
 }
 
 int ba_add_keyframe_and_adjust(vslam_system* sys) { return ba_run(sys, 0, false); }

@@ -51,6 +51,7 @@ extern "C" int vslam_map_add_keyframe(vslam_system* sys, int s, const double pos
   HIPCHK(hipMemcpyAsync(sys->map.kf_depth + ((size_t)s * K + k) * 2, dd, sizeof(dd), hipMemcpyHostToDevice, sys->stream));
   HIPCHK(hipMemsetAsync(sys->map.kf_meas + ((size_t)s * K + k) * sys->p.max_points, 0, sizeof(MeasDev) * sys->p.max_points, sys->stream));
   if (sys->p.grow_map || sys->p.idle_iterations != 0) { r = fe_keyframe_corners(sys, s, k); if (r) return r; }   // Level::vCorners, needed as an epipolar-search target
+  r = reloc_keyframe_sbi(sys, s, k, 1); if (r) return r;                // KeyFrame::pSBI (relocalise)
   st.n_kf = k + 1;
   r = put_state(sys, s, &st); if (r) return r;
   return k;
@@ -99,6 +100,7 @@ extern "C" int vslam_map_add_keyframes(vslam_system* sys, int s, int n, const do
   HIPCHK(hipMemcpyAsync(sys->map.kf_fixed + (size_t)s * K + k, fx.data(), sizeof(int) * n, hipMemcpyHostToDevice, sys->stream));
   HIPCHK(hipMemcpyAsync(sys->map.kf_depth + ((size_t)s * K + k) * 2, depth_mean_sigma, sizeof(double) * 2 * n, hipMemcpyHostToDevice, sys->stream));
   HIPCHK(hipMemsetAsync(sys->map.kf_meas + ((size_t)s * K + k) * sys->p.max_points, 0, sizeof(MeasDev) * sys->p.max_points * (size_t)n, sys->stream));
+  r = reloc_keyframe_sbi(sys, s, k, n); if (r) return r;                // KeyFrame::pSBI (relocalise)
   st.n_kf = k + n;
   r = put_state(sys, s, &st); if (r) return r;         // (synchronises: the host arrays above are done with)
   return k;
@@ -277,7 +279,7 @@ int map_init_states(vslam_system* sys) {
 // per-stage HIP-event times are those of each kernel running alone on the device.
 static bool profile_serial() { static const bool serial = getenv("VSLAM_PROFILE_SERIAL") != nullptr; return serial; }
 
-// TrackFrame in its pieces; vslam_track_frame is exactly vslam_make_keyframe_lite, vslam_patch_search(0), vslam_pose_update(0),
+// TrackFrame in its pieces; vslam_track_frame is exactly vslam_make_keyframe_lite, vslam_attempt_recovery, vslam_patch_search(0), vslam_pose_update(0),
 // vslam_patch_search(1), vslam_pose_update(1), vslam_finish_frame.
 extern "C" int vslam_patch_search(vslam_system* sys, int stage) {
   if (!sys || stage < 0 || stage > 1) { vslam_set_error("patch_search: bad argument"); return VSLAM_E_INVALID; }
@@ -317,6 +319,8 @@ extern "C" int vslam_track_frame(vslam_system* sys, const uint8_t* gray, size_t 
   int r = fe_make_keyframe_lite(sys, gray, row_stride, stream_stride, on_device);   // jni/Tracker.cc:85
   if (r) return r;
   if (profile_serial()) HIPCHK(hipStreamSynchronize(sys->fe_stream));
+  r = vslam_attempt_recovery(sys);                                                   // :133-139, for the lost streams (vslam_params.relocalise)
+  if (r) return r;
   r = vslam_patch_search(sys, 0);                                                    // :103-124 TrackMap
   if (!r) r = vslam_pose_update(sys, 0);
   if (!r) r = vslam_patch_search(sys, 1);

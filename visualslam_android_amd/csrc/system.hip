@@ -51,6 +51,8 @@ extern "C" int vslam_default_params(vslam_params* p, int width, int height, int 
   p->idle_iterations = 0;
   p->bootstrap = 0;
   p->ba_sum_order = 0;
+  p->relocalise = 0;
+  p->reloc_blur = 2.5;                                  // jni/SmallBlurryImage.h:19-20
   return VSLAM_OK;
 }
 
@@ -80,6 +82,7 @@ extern "C" int vslam_create(const vslam_params* p, vslam_system** out) {
     vslam_set_error("create: bootstrap needs grow_map != 0 (keyframe corner lists for InitFromStereo's AddSomeMapPoints) and ba_delay_frames = 0, got grow_map %d, ba_delay_frames %d", p->grow_map, p->ba_delay_frames);
     return VSLAM_E_INVALID;
   }
+  if (p->relocalise && !(p->reloc_blur > 0.0)) { vslam_set_error("create: relocalise needs reloc_blur > 0, got %g", p->reloc_blur); return VSLAM_E_INVALID; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
     vslam_set_error("create: no HIP device visible (the MI355X path has no CPU fallback)");
@@ -169,6 +172,7 @@ extern "C" int vslam_create(const vslam_params* p, vslam_system** out) {
     if (!r) r = ba_alloc(sys);
     if (!r) r = grow_alloc(sys);
     if (!r) r = boot_alloc(sys);
+    if (!r) r = reloc_alloc(sys);
     if (!r && hipStreamSynchronize(sys->stream) != hipSuccess) r = VSLAM_E_HIP;
     if (!r) r = map_init_states(sys);
     if (r) { vslam_destroy(sys); return r; }

@@ -86,15 +86,17 @@ __global__ __launch_bounds__(64) void k_motion(MapDev m, int S, const double* sb
   const int s = blockIdx.x * 64 + threadIdx.x;
   if (s >= S) return;
   TrackerState* st = &m.st[s];
-  const bool tracking = st->map_good && st->lost_frames < 3;       // jni/Tracker.cc:103-104
+  const bool tracking = trk_runs_track_map(st);                     // jni/Tracker.cc:103-104, 135-136
   st->frame++;                                                     // :100
   st->kf_pending = 0; st->kf_added = 0;
   if (!tracking) return;
-  double v[6];
-  for (int i = 0; i < 6; i++) v[i] = st->velocity[i];
-  if (sbi_rot) { v[0] = 0.0; v[1] = 0.0; for (int i = 3; i < 6; i++) v[i] = sbi_rot[(size_t)s * 8 + i]; }   // mbUseSBIInit :788-794
-  const Pose pred = pose_mul(se3_exp(v), st->pose_final);
-  st->start_pose = st->pose_final; st->pose_cur = pred;
+  if (!st->recovered_now) {                                        // a recovered frame starts from the relocaliser's pose (:133-139, 169-172)
+    double v[6];
+    for (int i = 0; i < 6; i++) v[i] = st->velocity[i];
+    if (sbi_rot) { v[0] = 0.0; v[1] = 0.0; for (int i = 3; i < 6; i++) v[i] = sbi_rot[(size_t)s * 8 + i]; }   // mbUseSBIInit :788-794
+    const Pose pred = pose_mul(se3_exp(v), st->pose_final);
+    st->start_pose = st->pose_final; st->pose_cur = pred;
+  }
   for (int l = 0; l < NLEV; l++) { st->attempted[l] = 0; st->found[l] = 0; }   // :360-361
   st->n_search = 0; st->n_coarse = 0; st->n_iter = 0; st->n_l3 = 0; st->coarse_found = 0;
 }
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(64) void k_motion(MapDev m, int S, const double* sb
 __global__ __launch_bounds__(TRK_THREADS) VSLAM_PVS_ATTR void k_pvs(MapDev m, TrackParams tp) {
   const int s = blockIdx.y;
   TrackerState* st = &m.st[s];
-  const bool tracking = st->map_good && st->lost_frames < 3;       // jni/Tracker.cc:103-104
+  const bool tracking = trk_runs_track_map(st);                     // jni/Tracker.cc:103-104, 135-136
   const int n_points = st->n_points, i0 = blockIdx.x * TRK_THREADS;
   if (!tracking || i0 >= n_points) return;
   __shared__ __align__(16) double pbuf[TRK_THREADS * PVS_OUT];
@@ -168,7 +170,7 @@ __global__ __launch_bounds__(TRK_THREADS) VSLAM_PVS_ATTR void k_pvs(MapDev m, Tr
 __global__ __launch_bounds__(TRK_THREADS) void k_plan(MapDev m, TrackParams tp, int stage) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
-  if (!(st->map_good && st->lost_frames < 3)) return;
+  if (!trk_runs_track_map(st)) return;
   const int P = tp.max_points;
   TrackData* td = m.td + (size_t)s * P;
   const MapPointDev* pts = m.pts + (size_t)s * P;
@@ -334,7 +336,7 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
   xcd_stream_block(a.nblk, a.S, s, bx);
   if (s < 0) return;
   TrackerState* st = &m.st[s];
-  if (!(st->map_good && st->lost_frames < 3)) return;
+  if (!trk_runs_track_map(st)) return;
   const int nsearch = st->n_search;
   if (bx * PPW >= nsearch) return;
   const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
@@ -643,7 +645,7 @@ __global__ __launch_bounds__(64) void k_subpixN(MapDev m, TrackParams tp, Search
   xcd_stream_block(a.nblk, a.S, s, bx);
   if (s < 0) return;
   TrackerState* st = &m.st[s];
-  if (!(st->map_good && st->lost_frames < 3)) return;
+  if (!trk_runs_track_map(st)) return;
   const int nsub = stage == 0 ? st->n_search : st->n_l3;             // entries that carry a sub-pixel budget
   for (int blk = bx; blk * (64 / G) < nsub; blk += a.nblk) subpix_block<PS, G>(m, tp, a, st, s, nsub, blk);
 }
@@ -919,7 +921,7 @@ DEVFN double kf_linear_dist(const Pose& a, const Pose& b) {
 __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VSLAM_POSE_WAVES, VSLAM_POSE_WAVES))) void k_pose(MapDev m, TrackParams tp, int stage) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
-  if (!(st->map_good && st->lost_frames < 3)) return;
+  if (!trk_runs_track_map(st)) return;
   const int P = tp.max_points;
   TrackData* td = m.td + (size_t)s * P;
   MapPointDev* pts = m.pts + (size_t)s * P;
@@ -1098,7 +1100,9 @@ __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VS
     st->depth_sigma = sqrt((dSumSq / nNum) - (st->depth_mean) * (st->depth_mean));
   }
   st->pose_cur = pose; st->pose_final = pose;
-  {                                                                  // UpdateMotionModel, :802-820
+  const bool recovered = st->recovered_now != 0;                     // :135-138: TrackMap and AssessTrackingQuality only
+  st->recovered_now = 0;
+  if (!recovered) {                                                  // UpdateMotionModel, :802-820
     const Pose nfo = pose_mul(pose, pose_inverse(st->start_pose));
     double motion[6];
     se3_ln(nfo, motion);
@@ -1128,7 +1132,7 @@ __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VS
     if (quality == 0) st->lost_frames++; else st->lost_frames = 0;
     st->quality = quality;
   }
-  {                                                                  // jni/Tracker.cc:128-132 + NeedNewKeyFrame, jni/MapMaker.cc:761-773
+  if (!recovered) {                                                  // jni/Tracker.cc:128-132 + NeedNewKeyFrame, jni/MapMaker.cc:761-773
     double dDist = closest;
     dDist *= (1.0 / st->depth_mean);
     const bool need = dDist > tp.max_kf_dist_wiggle_mult * st->wiggle_depth_norm;
@@ -1254,7 +1258,7 @@ int trk_search_stage(vslam_system* sys, int stage) {
     prof_mark(sys, 4);
     hipLaunchKernelGGL(k_plan, dim3(S), dim3(TRK_THREADS), 0, sys->stream, m, tp, 0);
     prof_mark(sys, 5);
-    if (!tp.coarse_disabled) {
+    if (!tp.coarse_disabled || sys->p.relocalise) {                  // a recovered frame has a coarse stage whatever the switch says (:432-433)
       const int nc = 2 * tp.coarse_max;
       if (tp.P == 8) {
         a.nblk = (nc + 7) / 8; hipLaunchKernelGGL((k_searchN<8, 8>), dim3(xcd_grid(a.nblk, S)), dim3(64), 0, sys->stream, m, tp, a, 0);
@@ -1286,7 +1290,7 @@ int trk_search_stage(vslam_system* sys, int stage) {
 // The ten Gauss-Newton iterations of a stage (:466-488 / :543-577); stage 1 also ends TrackMap and TrackFrame on device
 // (measurement export, scene depth, UpdateMotionModel, AssessTrackingQuality, the keyframe decision).
 int trk_pose_stage(vslam_system* sys, int stage) {
-  if (stage == 0 && sys->tp.coarse_disabled) return VSLAM_OK;
+  if (stage == 0 && sys->tp.coarse_disabled && !sys->p.relocalise) return VSLAM_OK;
   hipLaunchKernelGGL(k_pose, dim3(sys->S), dim3(POSE_THREADS), 0, sys->stream, sys->map, sys->tp, stage);
   HIPCHK(hipGetLastError());
   return VSLAM_OK;

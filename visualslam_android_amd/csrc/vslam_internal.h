@@ -115,7 +115,10 @@ struct TrackerState {       // Tracker members, jni/Tracker.h:77-150 (+ MapMaker
   int boot_ok, n_hom_inliers, n_init_points;
   unsigned boot_seed;       // stands in for the reference's rand() state
   int boot_host_matches;    // vslam_init_from_stereo: the trails are the caller's matches; this frame's TrailTracking_Advance does not search
+  int recovered_now;        // vslam_params.relocalise: AttemptRecovery succeeded in this frame (jni/Tracker.cc:133-139), cleared at the frame's end
 };
+// jni/Tracker.cc:103-104 and :135-136: TrackMap runs for a stream that is not lost, or that the relocaliser has just recovered
+DEVFN bool trk_runs_track_map(const TrackerState* st) { return st->map_good && (st->lost_frames < 3 || st->recovered_now); }
 
 struct TrackParams {        // device copy of the tunables the kernels read
   CamModel cam;
@@ -167,6 +170,21 @@ struct MapDev {             // device pointers of the map + tracker of all strea
   int* pose_wsi;            // [S][2][max_points]  flags, map point index
 };
 
+// ---- relocaliser (vslam_params.relocalise; reloc.hip): Relocaliser members, jni/Relocaliser.h ----------------------------------
+struct RelocInfo {
+  int attempts, successes, best, frame;   // AttemptRecovery calls / those that returned true, mnBest and mnFrame of the last one
+  double best_zmssd, score;               // mdBestScore, IteratePosRelToTarget's final score
+  double ln_adj[6];                       // ln(SE3fromSE2(mse2))
+  Pose best_pose;                         // mse3Best
+};
+struct RelocDev {             // all null with relocalise = 0
+  float* kf_tmpl;           // [S][max_keyframes][hs*ws]      KeyFrame::pSBI->mimTemplate
+  float* kf_jacs;           // [S][max_keyframes][hs*ws][2]   KeyFrame::pSBI->mimImageJacs
+  float* cur_tmpl;          // [S][hs*ws]                     kCurrent.pSBI->mimTemplate of the last attempt
+  double* scores;           // [S][max_keyframes]             ZMSSD against every keyframe in the last attempt
+  RelocInfo* info;          // [S]
+};
+
 struct vslam_system {
   vslam_params p;
   int S;
@@ -207,6 +225,7 @@ struct vslam_system {
   TrackParams tp;
   MapDev map;
   void* ba_ws;                 // bundle-adjustment workspace (ba.hip)
+  RelocDev reloc = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // per-stage HIP-event timing of vslam_track_frame (vslam_profile_begin/end)
   std::vector<hipEvent_t> prof_ev;
   int prof_cap = 0, prof_frame = 0;
@@ -257,6 +276,11 @@ int ba_add_keyframe_and_adjust(vslam_system* sys);
 int ba_run(vslam_system* sys, int mode, bool host_driven_keyframe = false);
 int ba_frame_start(vslam_system* sys);
 int ba_sync_streams(vslam_system* sys);   // launches an open batch first, then   // host wait for every map-maker stream   // asynchronous map-maker: apply the results that are due at this frame
+// reloc.hip
+int reloc_alloc(vslam_system* sys);
+int reloc_keyframe_sbi_pending(vslam_system* sys);                        // SmallBlurryImage of the keyframe k_add_keyframe has just stored (streams with kf_pending)
+int reloc_keyframe_sbi(vslam_system* sys, int s, int first, int n);       // ... of the uploaded keyframes [first, first + n) of stream s
+int reloc_attempt_recovery(vslam_system* sys);
 // map.hip
 int map_init_states(vslam_system* sys);
 
