@@ -145,12 +145,9 @@ __device__ unsigned long long g_ba_prof[32];
 
 struct BaConfig { CamModel cam; int max_iterations; double convergence_limit, min_sigma2; int sum_order; /* vslam_params.ba_sum_order */ };
 
-DEVFN double ba_wave_sum(double v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
-DEVFN int ba_wave_sum_i(int v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
-
 // block-wide sum of one double per thread; result returned to every thread. red: LDS [BA_WAVES]
 DEVFN double ba_block_sum(double v, double* red) {
-  v = ba_wave_sum(v);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -159,7 +156,7 @@ DEVFN double ba_block_sum(double v, double* red) {
   return t;
 }
 DEVFN int ba_block_sum_i(int v, int* red) {
-  v = ba_wave_sum_i(v);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -311,7 +308,7 @@ DEVFN bool ba_block_solve_lds(const double* S, double* E, int n, double* A, int*
     for (int k = n - 1; k >= 0; k--) {
       double s = 0.0;
       for (int c = k + 1 + lane; c < n; c += 64) s += A[k * ld + c] * A[c * ld + n];
-      for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+      s = wave_sum(s);
       if (lane == 0) A[k * ld + n] = (A[k * ld + n] - s) / A[k * ld + k];
       __builtin_amdgcn_s_waitcnt(0);
       __builtin_amdgcn_wave_barrier();
@@ -795,7 +792,7 @@ BA_PHASE_FN void ba_accum_U_generic(const BaView& v_, int nfree, int np) {
       _Pragma("unroll") for (int r = 0; r < 6; r++) for (int c = 0; c <= r; c++) acc[q++] += A[r] * A[c] + A[6 + r] * A[6 + c];
       _Pragma("unroll") for (int r = 0; r < 6; r++) acc[21 + r] += A[r] * e0 + A[6 + r] * e1;
     }
-    _Pragma("unroll") for (int k = 0; k < 27; k++) acc[k] = ba_wave_sum(acc[k]);
+    _Pragma("unroll") for (int k = 0; k < 27; k++) acc[k] = wave_sum(acc[k]);
     if (lane == 0) {
       double AS1* U = v.cam_U + 36 * j;
       int q = 0;
@@ -827,7 +824,7 @@ BA_PHASE_FN void ba_task_diag(const BaView& v_, int task, int np, int nS, double
     _Pragma("unroll") for (int r = 0; r < 3; r++) ve[r] = Vi[r * 3] * eb[0] + Vi[r * 3 + 1] * eb[1] + Vi[r * 3 + 2] * eb[2];
     _Pragma("unroll") for (int r = 0; r < 6; r++) acc[21 + r] += W[r * 3] * ve[0] + W[r * 3 + 1] * ve[1] + W[r * 3 + 2] * ve[2];
   }
-  _Pragma("unroll") for (int k = 0; k < 27; k++) acc[k] = ba_wave_sum(acc[k]);
+  _Pragma("unroll") for (int k = 0; k < 27; k++) acc[k] = wave_sum(acc[k]);
   if (lane == 0) {
     const double AS1* U = v.cam_U + 36 * j;
     int q = 0;
@@ -869,7 +866,7 @@ BA_PHASE_FN void ba_task_pair(const BaView& v_, int task, int np, int nS, double
     ba_jac_W(mk, v.cam_pose[k].R, Wk);
     _Pragma("unroll") for (int r = 0; r < 6; r++) for (int c = 0; c < 6; c++) acc[r * 6 + c] += Y[r * 3] * Wk[c * 3] + Y[r * 3 + 1] * Wk[c * 3 + 1] + Y[r * 3 + 2] * Wk[c * 3 + 2];
   }
-  _Pragma("unroll") for (int q = 0; q < 36; q++) acc[q] = ba_wave_sum(acc[q]);
+  _Pragma("unroll") for (int q = 0; q < 36; q++) acc[q] = wave_sum(acc[q]);
   if (lane == 0)
     _Pragma("unroll") for (int r = 0; r < 6; r++) for (int c = 0; c < 6; c++) {
       v.S[(size_t)(jrow + r) * nS + krow + c] = -acc[r * 6 + c];

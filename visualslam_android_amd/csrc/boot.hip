@@ -134,7 +134,7 @@ DEVFN bool mp_find(const BootFrame& f, int s, int w, int h, const uint8_t* tmpl 
           const uint8_t* ib = img + (size_t)(cy - MPH) * f.pitch + (cx - MPH);
           for (int q = sub; q < MPP; q += 8) { const int r = q / MPS, cc = q - r * MPS; const int d = (int)ib[r * f.pitch + cc] - (int)tmpl[q]; sum += d * d; }
         }
-        for (int d = 1; d < 8; d <<= 1) sum += __shfl_xor(sum, d);
+        sum = grp_sum<8>(sum);
         ssd = inside ? sum : BOOT_MAX_SSD + 1;
       }
       for (int d = 8; d < 64; d <<= 1) {
@@ -339,7 +339,6 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_boot_homography(MapDev m, Trac
 // alignment in the second, triangulation; appended in match order.
 template <int PS>
 __global__ __launch_bounds__(BOOT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_boot_points(MapDev m, TrackParams tp, BootArgs a) {
-  constexpr int NPIX = PS * PS, HALF = PS / 2;
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
   if (!st->boot_run) return;
@@ -364,10 +363,9 @@ __global__ __launch_bounds__(BOOT_THREADS) __attribute__((amdgpu_waves_per_eu(2,
     double sub0 = 0, sub1 = 0;
     if (alive) {
       cx = pos[4 * i]; cy = pos[4 * i + 1]; sub0 = (double)pos[4 * i + 2]; sub1 = (double)pos[4 * i + 3];
-      const int bord = HALF + 1;                                     // MakeTemplateCoarseNoWarp, jni/PatchFinder.cc:130-142
-      if (!(cx >= bord && cy >= bord && cx < a.w - bord && cy < a.h - bord)) alive = false;
+      int tsum, tsumsq;                                              // (the sub-pixel iterations need no template sums)
+      alive = template_no_warp<PS>(img0, a.kf_pitch, a.w, a.h, cx, cy, tmpl, lane, tsum, tsumsq);
     }
-    if (alive) for (int q = lane; q < NPIX; q += 64) { const int y = q / PS, x = q - y * PS; tmpl[q] = img0[(size_t)(cy - HALF + y) * a.kf_pitch + (cx - HALF + x)]; }
     __builtin_amdgcn_s_waitcnt(0xC07F);
     __builtin_amdgcn_wave_barrier();
     if (alive && !wave_subpix<PS>(tmpl, img1, a.kf_pitch, a.w, a.h, 0, 10, lane, sub0, sub1, sh_slab[wave])) alive = false;   // :298-304
@@ -380,9 +378,9 @@ __global__ __launch_bounds__(BOOT_THREADS) __attribute__((amdgpu_waves_per_eu(2,
         // pixel DOWN and the "down" neighbour one pixel RIGHT -- the reference's
         double cen[3], rgt[3], dwn[3];
         unit_ray(tp.cam, (double)cx, (double)cy, cen); unit_ray(tp.cam, (double)cx + 0, (double)cy + 1, rgt); unit_ray(tp.cam, (double)cx + 1, (double)cy + 0, dwn);
-        const double hgt = fabs(-wp[2]), rc = fabs(-cen[2]), rr = fabs(-rgt[2]), rd = fabs(-dwn[2]);
         Res& r = res[wave];
-        for (int k = 0; k < 3; k++) { const double cop = cen[k] * hgt / rc; r.right[k] = rgt[k] * hgt / rr - cop; r.down[k] = dwn[k] * hgt / rd - cop; r.pos[k] = wp[k]; }
+        refresh_pixel_vectors(cen, rgt, dwn, wp[2], r.right, r.down);
+        for (int k = 0; k < 3; k++) r.pos[k] = wp[k];
         r.sub[0] = sub0; r.sub[1] = sub1; r.cx = cx; r.cy = cy; r.ok = 1;
       }
     }
@@ -396,22 +394,13 @@ __global__ __launch_bounds__(BOOT_THREADS) __attribute__((amdgpu_waves_per_eu(2,
         MapPointDev mp;
         for (int k = 0; k < 3; k++) { mp.pos[k] = r.pos[k]; mp.right[k] = r.right[k]; mp.down[k] = r.down[k]; }
         mp.src_kf = 0; mp.src_level = 0; mp.irx = r.cx; mp.iry = r.cy; mp.bad = 0; mp.n_in = 0; mp.n_out = 0; mp.n_meas_kfs = 2;
-        m.pts[(size_t)s * P + pid] = mp;
-        TrackData td;
-        for (int k = 0; k < 3; k++) td.cam[k] = 0;
-        for (int k = 0; k < 2; k++) { td.image[k] = 0; td.vfound[k] = 0; }
-        for (int k = 0; k < 4; k++) { td.derivs[k] = 0; td.warp_inv[k] = 0; td.last_warp[k] = 0; }
-        td.sqrt_inv_noise = 0; td.tsum = 0; td.tsumsq = 0;
-        td.last_warp[0] = 9999.9; td.last_warp[3] = 9999.9;
-        m.td[(size_t)s * P + pid] = td;
-        m.pt_level[(size_t)s * P + pid] = -1; m.pt_flags[(size_t)s * P + pid] = 0;
+        append_point(m, tp, s, pid, mp);
         MeasDev mm;
         mm.valid = 1; mm.level = 0; mm.subpix = 1; mm.pad = 0;
         mm.source = 2 /* SRC_ROOT */; mm.root[0] = (double)r.cx; mm.root[1] = (double)r.cy;
         m.kf_meas[((size_t)s * K + 0) * P + pid] = mm;
         mm.source = 3 /* SRC_TRAIL */; mm.root[0] = r.sub[0]; mm.root[1] = r.sub[1];
         m.kf_meas[((size_t)s * K + 1) * P + pid] = mm;
-        m.cur_meas[(size_t)s * P + pid].valid = 0;
         st->n_points = pid + 1;
       }
     }

@@ -277,6 +277,12 @@ HDFN void inv2(const double m[4], double o[4]) {
 }
 
 #ifdef __HIPCC__
+// Xor-butterfly sums (int, unsigned or double; the result is in every lane).  wave_sum: the 64 lanes of a wavefront, partner
+// distance 32 down to 1.  grp_sum<G>: aligned groups of G lanes, distance 1 up to G/2.  Every double sum's rounding rests on these
+// pairings and directions.
+template <class T> DEVFN T wave_sum(T v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
+template <int G, class T> DEVFN T grp_sum(T v) { for (int d = 1; d < G; d <<= 1) v += __shfl_xor(v, d); return v; }
+
 // Sum N (a power of two, <= 64) per-lane values over the 64 lanes of a wavefront by recursive halving: at distance d
 // the lanes with bit d clear keep the lower half of the values and hand the upper half to their partner (and vice versa),
 // so N/2 + N/4 + ... shuffles move the data instead of 6 N.  The pairing tree -- hence every rounding -- is that of

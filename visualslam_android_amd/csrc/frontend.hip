@@ -395,8 +395,7 @@ __global__ __launch_bounds__(SL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
     // ---- the round's survivors: compact per wavefront, full test on dense lanes ----
     const int relg = i0 - 2 * HALO;                                  // band row of the round's slot 0
     int cnt = __popc(pw[0]) + __popc(pw[1]) + __popc(pw[2]) + __popc(pw[3]);
-    int tot = cnt;
-    for (int d = 32; d > 0; d >>= 1) tot += __shfl_xor(tot, d);
+    const int tot = wave_sum(cnt);
 #ifdef VSLAM_SL_SKIP_FLUSH
     if (tot != 123456) continue;
 #endif
@@ -476,7 +475,7 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_compact(FeArgs a, int cband
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int above = 0;
   for (int y = threadIdx.x; y < y0; y += COMPACT_THREADS) above += rc[y];
-  for (int d = 32; d > 0; d >>= 1) above += __shfl_xor(above, d);
+  above = wave_sum(above);
   if (lane == 0) wsum[wave] = above;
   __syncthreads();
   if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < COMPACT_THREADS / 64; w++) t += wsum[w]; sh_above = t; }

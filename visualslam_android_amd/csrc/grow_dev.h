@@ -1,44 +1,7 @@
-// Wavefront-level pieces of the map-maker's patch work shared by mapgrow.hip (AddPointEpipolar, ReFind_Common) and boot.hip
-// (InitFromStereo): zero-mean SSD, the sub-pixel iterations, triangulation, unit rays.  See mapgrow.hip for the reference lines.
+// Wavefront-level pieces of the map maker's point making shared by mapgrow.hip (AddPointEpipolar, ReFind_Common) and boot.hip
+// (InitFromStereo): the sub-pixel iterations, triangulation, unit rays.  The patch finder proper is in patch_dev.h.
 #pragma once
-#include "vslam_internal.h"
-
-DEVFN int wsum_i(int v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
-DEVFN double wsum_d(double v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
-
-// PatchFinder::ZMSSDAtPoint (jni/PatchFinder.cc:352-380) by one wavefront; the template lies in LDS
-template <int PS>
-DEVFN int wave_zmssd(const uint8_t* tmpl, const uint8_t* img, int ip, int wl, int hl, int cx, int cy, int tsum, int tsumsq, int max_ssd, int lane) {
-  constexpr int NPIX = PS * PS, HALF = PS / 2;
-  if (!(cx >= HALF && cy >= HALF && cx < wl - HALF && cy < hl - HALF)) return max_ssd + 1;
-  int sA = 0, sQ = 0, sX = 0;
-  for (int q = lane; q < NPIX; q += 64) {
-    const int y = q / PS, x = q - y * PS;
-    const int n = img[(size_t)(cy - HALF + y) * ip + (cx - HALF + x)], t = tmpl[q];
-    sA += n; sQ += n * n; sX += n * t;
-  }
-  sA = wsum_i(sA); sQ = wsum_i(sQ); sX = wsum_i(sX);
-  const int SA = tsum, SB = sA;
-  return ((2 * SA * SB - SA * SA - SB * SB) / NPIX + sQ + tsumsq - 2 * sX);
-}
-
-// Several ZMSSDAtPoint evaluations (jni/PatchFinder.cc:352-380) per wavefront step, the way k_searchN scores its
-// candidates: G lanes per patch (8 for 8x8 -> 8 patches at once, 16 for 11x11 -> 4), lane r < PS owns row r of template
-// and image patch as packed bytes and the three sums are v_dot4_u32_u8 products reduced over the G lanes.
-template <int PS> struct GRow { unsigned w[(PS + 3) / 4]; };
-template <int PS> DEVFN GRow<PS> grow_load_row(const uint8_t* p) {
-  GRow<PS> r;
-  _Pragma("unroll") for (int k = 0; k < (PS + 3) / 4; k++) r.w[k] = 0u;
-  __builtin_memcpy(&r, p, PS);
-  return r;
-}
-template <int PS> DEVFN GRow<PS> grow_load_row_lds(const uint8_t* p) {      // the template row out of LDS (byte reads: 8-byte rows of an 11-byte pitch are unaligned)
-  GRow<PS> r;
-  _Pragma("unroll") for (int k = 0; k < (PS + 3) / 4; k++) r.w[k] = 0u;
-  _Pragma("unroll") for (int x = 0; x < PS; x++) r.w[x >> 2] |= (unsigned)p[x] << (8 * (x & 3));
-  return r;
-}
-template <int G> DEVFN int grow_grp_sum(int v) { for (int d = 1; d < G; d <<= 1) v += __shfl_xor(v, d); return v; }
+#include "patch_dev.h"
 
 // MakeSubPixTemplate (jni/PatchFinder.cc:242-271) + IterateSubPixToConvergence (:273-350) by one wavefront, starting from
 // the level-zero position in sub0/sub1; these are left wherever the iteration stopped (ReFind_Common reads them regardless)
@@ -58,7 +21,7 @@ DEVFN bool wave_subpix(const uint8_t* tmpl, const uint8_t* img, int ip, int wl, 
       h00 += gx[q] * gx[q]; h01 += gx[q] * gy[q]; h02 += gx[q]; h11 += gy[q] * gy[q]; h12 += gy[q]; h22 += 1.0;
     }
   }
-  h00 = wsum_d(h00); h01 = wsum_d(h01); h02 = wsum_d(h02); h11 = wsum_d(h11); h12 = wsum_d(h12); h22 = wsum_d(h22);
+  h00 = wave_sum(h00); h01 = wave_sum(h01); h02 = wave_sum(h02); h11 = wave_sum(h11); h12 = wave_sum(h12); h22 = wave_sum(h22);
   const double H[9] = {h00, h01, h02, h01, h11, h12, h02, h12, h22};
   double Hinv[9];
   inv3(H, Hinv);

@@ -1,5 +1,6 @@
 // Map upload, per-frame entry points (Tracker::TrackFrame / JNI-equivalent update) and read-back of the C ABI.
 #include "vslam_internal.h"
+#include "patch_dev.h"
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -118,8 +119,7 @@ extern "C" int vslam_map_add_point(vslam_system* sys, int s, const double pos[3]
   MapPointDev mp; memset(&mp, 0, sizeof(mp));
   for (int q = 0; q < 3; q++) { mp.pos[q] = pos[q]; mp.right[q] = right[q]; mp.down[q] = down[q]; }
   mp.src_kf = src_keyframe; mp.src_level = src_level; mp.irx = ir_x; mp.iry = ir_y;
-  TrackData td; memset(&td, 0, sizeof(td));
-  td.last_warp[0] = 9999.9; td.last_warp[3] = 9999.9;   // jni/PatchFinder.cc:23
+  const TrackData td = fresh_track_data();
   const int lvl0[2] = {-1, 0};
   HIPCHK(hipMemcpyAsync(sys->map.pt_level + (size_t)s * P + i, &lvl0[0], sizeof(int), hipMemcpyHostToDevice, sys->stream));
   HIPCHK(hipMemcpyAsync(sys->map.pt_flags + (size_t)s * P + i, &lvl0[1], sizeof(int), hipMemcpyHostToDevice, sys->stream));
@@ -185,14 +185,12 @@ extern "C" int vslam_map_add_points(vslam_system* sys, int s, int n, const doubl
   if (n < 0 || st.n_points + n > P) { vslam_set_error("map point capacity %d reached", P); return VSLAM_E_CAPACITY; }
   if (n == 0) return st.n_points;
   std::vector<MapPointDev> mp(n);
-  std::vector<TrackData> td(n);
+  std::vector<TrackData> td(n, fresh_track_data());
   memset(mp.data(), 0, sizeof(MapPointDev) * n);
-  memset(td.data(), 0, sizeof(TrackData) * n);
   for (int i = 0; i < n; i++) {
     if (src_keyframe[i] < 0 || src_keyframe[i] >= st.n_kf || src_level[i] < 0 || src_level[i] >= NLEV) { vslam_set_error("map_add_points: bad entry %d", i); return VSLAM_E_INVALID; }
     for (int q = 0; q < 3; q++) { mp[i].pos[q] = pos[3 * i + q]; mp[i].right[q] = right[3 * i + q]; mp[i].down[q] = down[3 * i + q]; }
     mp[i].src_kf = src_keyframe[i]; mp[i].src_level = src_level[i]; mp[i].irx = ir_xy[2 * i]; mp[i].iry = ir_xy[2 * i + 1];
-    td[i].last_warp[0] = 9999.9; td[i].last_warp[3] = 9999.9;   // jni/PatchFinder.cc:23
   }
   HIPCHK(hipMemcpy(sys->map.pts + (size_t)s * P + st.n_points, mp.data(), sizeof(MapPointDev) * n, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(sys->map.td + (size_t)s * P + st.n_points, td.data(), sizeof(TrackData) * n, hipMemcpyHostToDevice));

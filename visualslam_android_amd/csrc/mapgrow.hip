@@ -169,26 +169,14 @@ __global__ __launch_bounds__(GROW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
           if (dMaxLen > 2.0) dMaxLen = 2.0;
         }
       }
-      // ---- MakeTemplateCoarseNoWarp (jni/PatchFinder.cc:130-142) + MakeTemplateSums ----
       ca = (int)irx; cb = (int)iry;
-      const int bord = HALF + 1;
-      if (!(ca >= bord && cb >= bord && ca < wl - bord && cb < hl - bord)) { if (alive) why = 4; alive = false; }
     }
     GROW_STAMP(0);   // geometry
     int tsum = 0, tsumsq = 0;
-    if (alive) {
-      int sa = 0, sq = 0;
-      for (int q = lane; q < NPIX; q += 64) {
-        const int y = q / PS, x = q - y * PS;
-        const int v = img_src[(size_t)(cb - HALF + y) * ip + (ca - HALF + x)];
-        tmpl[q] = (uint8_t)v; sa += v; sq += v * v;
-      }
-      tsum = wsum_i(sa); tsumsq = wsum_i(sq);
-    }
+    if (alive && !template_no_warp<PS>(img_src, ip, wl, hl, ca, cb, tmpl, lane, tsum, tsumsq)) { alive = false; why = 4; }
     __builtin_amdgcn_wave_barrier();
-    GRow<PS> trow;
-    _Pragma("unroll") for (int q = 0; q < (PS + 3) / 4; q++) trow.w[q] = 0u;
-    if (alive && sub < PS) trow = grow_load_row_lds<PS>(tmpl + sub * PS);
+    PRow<PS> trow = zero_row<PS>();
+    if (alive && sub < PS) trow = load_row_lds<PS>(tmpl + sub * PS);
     GROW_STAMP(1);   // template
     // ---- the target keyframe's corners near the epipolar line, :622-641: filter 64 at a time, score the survivors in order ----
     int nBest = -1, nBestZMSSD = tp.max_ssd + 1;
@@ -215,22 +203,12 @@ __global__ __launch_bounds__(GROW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
           __builtin_amdgcn_wave_barrier();
           const int2 pick = sel[grp < nsel ? grp : 0];
           const int cx = pick.x & 0xFFFF, cy = (unsigned)pick.x >> 16;
-          int ssd = tp.max_ssd + 1;
           const bool inb = cx >= HALF && cy >= HALF && cx < wl - HALF && cy < hl - HALF;
-          {
-            int sA = 0, sQ = 0, sX = 0;
-            if (inb && grp < nsel && sub < PS) {
-              const GRow<PS> ir = grow_load_row<PS>(img_tgt + (size_t)(cy - HALF + sub) * ip + (cx - HALF));
-              _Pragma("unroll") for (int q = 0; q < (PS + 3) / 4; q++) {
-                sA = (int)__builtin_amdgcn_udot4(ir.w[q], 0x01010101u, (unsigned)sA, false);
-                sQ = (int)__builtin_amdgcn_udot4(ir.w[q], ir.w[q], (unsigned)sQ, false);
-                sX = (int)__builtin_amdgcn_udot4(ir.w[q], trow.w[q], (unsigned)sX, false);
-              }
-            }
-            sA = grow_grp_sum<G>(sA); sQ = grow_grp_sum<G>(sQ); sX = grow_grp_sum<G>(sX);
-            const int SA = tsum, SB = sA;
-            if (inb) ssd = ((2 * SA * SB - SA * SA - SB * SB) / NPIX + sQ + tsumsq - 2 * sX);   // ZMSSDAtPoint :352-380
-          }
+          PRow<PS> ir = zero_row<PS>();
+          if (inb && grp < nsel && sub < PS) ir = load_row<PS>(img_tgt + (size_t)(cy - HALF + sub) * ip + (cx - HALF));
+          int sA, sQ, sX;
+          grp_zmssd_sums<PS, G>(ir, trow, sA, sQ, sX);
+          const int ssd = inb ? zmssd_score<NPIX>(tsum, tsumsq, sA, sQ, sX) : tp.max_ssd + 1;   // ZMSSDAtPoint :352-380
           _Pragma("unroll") for (int g = 0; g < NPW; g++) {          // first strict minimum in list order (:630-637)
             const int sg = __shfl(ssd, g * G), ig = __shfl(pick.y, g * G);
             if (g < nsel && sg < nBestZMSSD) { nBest = ig; nBestZMSSD = sg; }
@@ -261,10 +239,9 @@ __global__ __launch_bounds__(GROW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
       double cen[3], rgt[3], dwn[3];
       unit_ray(tp.cam, root0, root1, cen); unit_ray(tp.cam, root0 + nLevelScale, root1, rgt); unit_ray(tp.cam, root0, root1 + nLevelScale, dwn);
       double pc[3];
-      pose_xform(Tsrc, pw, pc);                                        // RefreshPixelVectors, normal (0, 0, -1)
-      const double hgt = fabs(-pc[2]), rc = fabs(-cen[2]), rr = fabs(-rgt[2]), rd = fabs(-dwn[2]);
+      pose_xform(Tsrc, pw, pc);
       double dr[3], dd[3];
-      for (int i = 0; i < 3; i++) { const double cop = cen[i] * hgt / rc; dr[i] = rgt[i] * hgt / rr - cop; dd[i] = dwn[i] * hgt / rd - cop; }
+      refresh_pixel_vectors(cen, rgt, dwn, pc[2], dr, dd);
       EpiResult& r = res[wave];
       rot_inv(Tsrc, dr, r.right); rot_inv(Tsrc, dd, r.down);
       for (int i = 0; i < 3; i++) r.pos[i] = pw[i];
@@ -285,15 +262,7 @@ __global__ __launch_bounds__(GROW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
         MapPointDev mp;
         for (int i = 0; i < 3; i++) { mp.pos[i] = r.pos[i]; mp.right[i] = r.right[i]; mp.down[i] = r.down[i]; }
         mp.src_kf = ksrc; mp.src_level = nLevel; mp.irx = r.irx; mp.iry = r.iry; mp.bad = 0; mp.n_in = 0; mp.n_out = 0; mp.n_meas_kfs = 2;
-        m.pts[(size_t)s * P + pid] = mp;
-        TrackData td;
-        for (int i = 0; i < 3; i++) td.cam[i] = 0;
-        for (int i = 0; i < 2; i++) { td.image[i] = 0; td.vfound[i] = 0; }
-        for (int i = 0; i < 4; i++) { td.derivs[i] = 0; td.warp_inv[i] = 0; td.last_warp[i] = 0; }
-        td.sqrt_inv_noise = 0; td.tsum = 0; td.tsumsq = 0;
-        td.last_warp[0] = 9999.9; td.last_warp[3] = 9999.9;               // jni/PatchFinder.cc:23
-        m.td[(size_t)s * P + pid] = td;
-        m.pt_level[(size_t)s * P + pid] = -1; m.pt_flags[(size_t)s * P + pid] = 0;
+        append_point(m, tp, s, pid, mp);
         MeasDev mm;
         mm.valid = 1; mm.level = (signed char)nLevel; mm.subpix = 1; mm.pad = 0;
         for (int k = 0; k <= ksrc; k++) {                                 // the new column of the measurement table
@@ -304,7 +273,6 @@ __global__ __launch_bounds__(GROW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
         m.kf_meas[((size_t)s * K + ksrc) * P + pid] = mm;
         mm.source = 4 /* SRC_EPIPOLAR */; mm.root[0] = r.sub[0]; mm.root[1] = r.sub[1];
         m.kf_meas[((size_t)s * K + ktgt) * P + pid] = mm;
-        m.cur_meas[(size_t)s * P + pid].valid = 0;
         st->n_points = pid + 1;
       }
     }
@@ -327,7 +295,6 @@ DEVFN void never_retry_set(const MapDev& m, const TrackParams& tp, int s, int pi
 template <int PS>
 DEVFN bool refind_common(const MapDev& m, const TrackParams& tp, const GrowArgs& a, int s, int k, int pid, const int* rowlut,
                          uint8_t* tmpl, double* slab, RefindCache& cache, int lane) {
-  constexpr int HALF = PS / 2;
   const int K = tp.max_keyframes, P = tp.max_points;
   MapPointDev& p = m.pts[(size_t)s * P + pid];
   MeasDev& cell = m.kf_meas[((size_t)s * K + k) * P + pid];
@@ -344,64 +311,36 @@ DEVFN bool refind_common(const MapDev& m, const TrackParams& tp, const GrowArgs&
   if (pr.im[0] < 0 || pr.im[1] < 0 || pr.im[0] > a.w[0] || pr.im[1] > a.h[0]) { never_retry_set(m, tp, s, pid, k, lane); return false; }   // :996
   double d[4];
   cam_derivs(tp.cam, pr, d);
-  // CalcSearchLevelAndWarpMatrix, jni/PatchFinder.cc:31-68
-  const double ooz = 1.0 / c[2];
-  double mr[3], md[3];
-  pose_rot(Tk, p.right, mr);
-  pose_rot(Tk, p.down, md);
-  const double r0 = mr[0] - c[0] * mr[2] * ooz, r1 = mr[1] - c[1] * mr[2] * ooz;
-  const double d0 = md[0] - c[0] * md[2] * ooz, d1 = md[1] - c[1] * md[2] * ooz;
-  const double wi[4] = {(d[0] * r0 + d[1] * r1) * ooz, (d[0] * d0 + d[1] * d1) * ooz, (d[2] * r0 + d[3] * r1) * ooz, (d[2] * d0 + d[3] * d1) * ooz};
-  double det = wi[0] * wi[3] - wi[1] * wi[2];
-  int level = 0;
-  while (det > 3 && level < NLEV - 1) { level++; det *= 0.25; }
-  const bool bad_scale = det > 3 || det < 0.25;                      // mbTemplateBad = true (:62-65); a regenerated template replaces the verdict
+  double wi[4];
+  int level;
+  const bool bad_scale = search_level_and_warp(Tk, c, d, p.right, p.down, wi, level) < 0;   // a regenerated template replaces the verdict
   const int scale = 1 << level;
   REFIND_STAMP(10);  // projection, derivatives, warp
   // MakeTemplateCoarseCont, :79-125: transform_image with the accumulated stepping of jni/vision/ImageHandler.cpp:21-113
-  double inv[4];
-  inv2(wi, inv);
-  const double m2[4] = {inv[0] * scale, inv[1] * scale, inv[2] * scale, inv[3] * scale};
-  bool refresh = !cache.have_last;
-  for (int i = 0; !refresh && i < 2; i++) {
-    const double dx = m2[i] - cache.last_warp[i], dy = m2[2 + i] - cache.last_warp[2 + i];
-    if (dx * dx + dy * dy > 0.07 * 0.07) refresh = true;
-  }
+  double m2[4];
+  template_warp_matrix(wi, scale, m2);
   bool bad;
-  if (refresh) {
+  if (!cache.have_last || warp_moved(m2, cache.last_warp)) {
     int nOutside = 0, sum = 0, sumsq = 0;
     const int sl = p.src_level;
     const uint8_t* src = m.kf_img[sl] + ((size_t)s * K + p.src_kf) * a.kf_stride[sl];
     const int sp = a.kf_pitch[sl], iw = a.w[sl], ih = a.h[sl];
-    const double across[2] = {m2[0], m2[2]}, down[2] = {m2[1], m2[3]};
-    const double px0 = (double)p.irx - (m2[0] * HALF + m2[1] * HALF), py0 = (double)p.iry - (m2[2] * HALF + m2[3] * HALF);
-    const double cr[2] = {down[0] - PS * across[0], down[1] - PS * across[1]};
+    const TemplateWarp tw = template_warp<PS>(m2, p.irx, p.iry, iw, ih);
     // one template pixel per lane (two for 11x11): the lane walks the accumulated sample position to its pixel with exactly
     // the additions transform_image makes (whole rows with their carriage return, then steps along the row)
-    const float x_bound = (float)(iw - 1), y_bound = (float)(ih - 1);
     for (int q = lane; q < PS * PS; q += 64) {
       const int r = q / PS, j = q - r * PS;
-      double x = px0, y = py0;
+      double x = tw.x0, y = tw.y0;
 #pragma unroll 1
-      for (int i = 0; i < r; i++) {
-#pragma unroll
-        for (int jj = 0; jj < PS; jj++) { x += across[0]; y += across[1]; }
-        x += cr[0]; y += cr[1];
-      }
+      for (int i = 0; i < r; i++) warp_row_step<PS>(tw, x, y);
 #pragma unroll 1
-      for (int jj = 0; jj < j; jj++) { x += across[0]; y += across[1]; }
-      int v = 0;
-      if (0 <= x && 0 <= y && x < x_bound && y < y_bound) {
-        const int lx = (int)x, ly = (int)y;
-        x -= lx; y -= ly;
-        const uint8_t* q0 = src + (size_t)ly * sp + lx;
-        v = (uint8_t)((1 - y) * ((1 - x) * q0[0] + x * q0[1]) + y * ((1 - x) * q0[sp] + x * q0[sp + 1]));
-      } else nOutside++;
+      for (int jj = 0; jj < j; jj++) warp_pixel_step(tw, x, y);
+      const int v = warp_sample(tw, src, sp, x, y, nOutside);
       tmpl[q] = (uint8_t)v;
       sum += v; sumsq += v * v;
     }
-    nOutside = wsum_i(nOutside);
-    cache.tsum = wsum_i(sum); cache.tsumsq = wsum_i(sumsq);
+    nOutside = wave_sum(nOutside);
+    cache.tsum = wave_sum(sum); cache.tsumsq = wave_sum(sumsq);
     __builtin_amdgcn_wave_barrier();
     bad = nOutside != 0;
     cache.have_last = true;
@@ -417,24 +356,20 @@ DEVFN bool refind_common(const MapDev& m, const TrackParams& tp, const GrowArgs&
   const uint32_t* corners = m.kf_corners[level] + ((size_t)s * K + k) * tp.kcap[level];
   const int nc = m.kf_ncorners[((size_t)s * K + k) * NLEV + level];
   const double irx = pr.im[0] / scale, iry = pr.im[1] / scale;
-  const unsigned nRange = (4u + scale - 1) / scale;
-  int nTop = (int)(iry - nRange);
-  const int nBottomPlusOne = (int)(iry + nRange + 1);
-  const int nLeft = (int)(irx - nRange), nRight = (int)(irx + nRange);
-  if (nTop < 0) nTop = 0;
-  if (nTop >= hl || nBottomPlusOne <= 0) { never_retry_set(m, tp, s, pid, k, lane); return false; }
+  const CoarseWindow cw = coarse_window(irx, iry, 4, scale, hl);
+  if (cw.empty) { never_retry_set(m, tp, s, pid, k, lane); return false; }
   int i0, i1;
   if (rowlut) {
     // the new keyframe's corner list is the current frame's (k_copy_kf_corners), so the frame's row look-up table serves
     // (two loads instead of two binary searches of dependent global loads; indices clamped to the stored list)
     const int* lut = a.rowlut[level] + (size_t)s * (hl + 1);
-    i0 = lut[nTop]; i1 = nBottomPlusOne >= hl ? nc : lut[nBottomPlusOne];
+    i0 = lut[cw.top]; i1 = cw.bottom_plus_one >= hl ? nc : lut[cw.bottom_plus_one];
     if (i0 > nc) i0 = nc;
     if (i1 > nc) i1 = nc;
   } else {
     // Level::vCornerRowLUT of a stored keyframe = first corner of a row: lower bound of (row << 16) in the raster-ordered list
     auto lower = [&](int row) { int lo = 0, hi = nc; const uint32_t key = (uint32_t)row << 16; while (lo < hi) { const int mid = (lo + hi) >> 1; if (corners[mid] < key) lo = mid + 1; else hi = mid; } return lo; };
-    i0 = lower(nTop); i1 = nBottomPlusOne >= hl ? nc : lower(nBottomPlusOne);
+    i0 = lower(cw.top); i1 = cw.bottom_plus_one >= hl ? nc : lower(cw.bottom_plus_one);
   }
   int bestx = -1, besty = -1, nBest = tp.max_ssd + 1;
   for (int base = i0; base < i1; base += 64) {
@@ -444,7 +379,7 @@ DEVFN bool refind_common(const MapDev& m, const TrackParams& tp, const GrowArgs&
       cv = corners[base + lane];
       const int cx = cv & 0xFFFF, cy = cv >> 16;
       const double dx = irx - cx, dy = iry - cy;
-      ok = !(cx < nLeft || cx > nRight) && !(dx * dx + dy * dy > (double)(nRange * nRange));
+      ok = !(cx < cw.left || cx > cw.right) && !(dx * dx + dy * dy > (double)(cw.range * cw.range));
     }
     unsigned long long bm = __ballot(ok);
     while (bm) {

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(64) void k_minipatch_find(const uint8_t* img, int p
           const uint8_t* ib = img + (size_t)(cy - MP_HALF) * pitch + (cx - MP_HALF);
           for (int q = sub; q < MP_PIX; q += 8) { const int r = q / MP_SIDE, cc = q - r * MP_SIDE; const int d = (int)ib[r * pitch + cc] - (int)tmpl[q]; s += d * d; }
         }
-        for (int d = 1; d < 8; d <<= 1) s += __shfl_xor(s, d);
+        s = grp_sum<8>(s);
         ssd = inside ? s : max_ssd + 1;
       }
       for (int d = 8; d < 64; d <<= 1) {

@@ -74,7 +74,7 @@ DEVFN void sbi_make_from_l3(const uint8_t* l3, int l3_pitch, int W, int H, const
     t0[i] = (float)v;
     part += v;
   }
-  for (int d = 32; d > 0; d >>= 1) part += __shfl_xor(part, d);
+  part = wave_sum(part);
   if (lane == 0) sh.isum[wave] = part;
   __syncthreads();
   unsigned int nSum = 0;

@@ -56,15 +56,6 @@ extern "C" int vslam_default_params(vslam_params* p, int width, int height, int 
   return VSLAM_OK;
 }
 
-template <class T>
-static int dev_alloc(vslam_system* sys, T** out, size_t count) {
-  void* ptr = nullptr;
-  HIPCHK(hipMalloc(&ptr, count * sizeof(T) + 64));
-  HIPCHK(hipMemsetAsync(ptr, 0, count * sizeof(T) + 64, sys->stream));
-  sys->allocs.push_back(ptr);
-  *out = (T*)ptr;
-  return VSLAM_OK;
-}
 #define ALLOC(ptr, count) do { int _r = dev_alloc(sys, &(ptr), (count)); if (_r) { vslam_destroy(sys); return _r; } } while (0)
 
 extern "C" int vslam_create(const vslam_params* p, vslam_system** out) {

@@ -18,6 +18,7 @@
 //              AssessTrackingQuality and the new-keyframe decision (:594-625, :802-878, :128-132)
 // Transcendentals come from vslam_libm.h (one source for this file and the oracle); nothing here may be contracted into FMAs.
 #include "vslam_internal.h"
+#include "patch_dev.h"
 
 #define TRK_THREADS 256
 #define SORT_CAP 4096
@@ -131,21 +132,10 @@ __global__ __launch_bounds__(TRK_THREADS) VSLAM_PVS_ATTR void k_pvs(MapDev m, Tr
       if (flags & TDF_IN_IMAGE) {
         nwr = PVS_OUT;
         cam_derivs(tp.cam, pr, td.derivs);                         // :384 GetDerivsUnsafe
-        // CalcSearchLevelAndWarpMatrix, jni/PatchFinder.cc:31-68
-        const double ooz = 1.0 / td.cam[2];
-        double mr[3], md[3];
-        pose_rot(pred, p.right, mr);
-        pose_rot(pred, p.down, md);
-        const double r0 = mr[0] - td.cam[0] * mr[2] * ooz, r1 = mr[1] - td.cam[1] * mr[2] * ooz;
-        const double d0 = md[0] - td.cam[0] * md[2] * ooz, d1 = md[1] - td.cam[1] * md[2] * ooz;
-        const double* d = td.derivs;
-        td.warp_inv[0] = (d[0] * r0 + d[1] * r1) * ooz; td.warp_inv[2] = (d[2] * r0 + d[3] * r1) * ooz;
-        td.warp_inv[1] = (d[0] * d0 + d[1] * d1) * ooz; td.warp_inv[3] = (d[2] * d0 + d[3] * d1) * ooz;
-        double det = td.warp_inv[0] * td.warp_inv[3] - td.warp_inv[1] * td.warp_inv[2];
-        int lv = 0;
-        while (det > 3 && lv < NLEV - 1) { lv++; det *= 0.25; }
-        if (det > 3 || det < 0.25) flags |= TDF_TMPL_BAD;          // mbTemplateBad = true; return -1
-        else { flags &= ~(TDF_SEARCHED | TDF_FOUND); level = lv; } // :389-390
+        int lv;
+        level = search_level_and_warp(pred, td.cam, td.derivs, p.right, p.down, td.warp_inv, lv);
+        if (level < 0) flags |= TDF_TMPL_BAD;                      // mbTemplateBad = true; return -1
+        else flags &= ~(TDF_SEARCHED | TDF_FOUND);                 // :389-390
       }
       m.pt_flags[gi] = flags;
     }
@@ -286,9 +276,6 @@ __global__ __launch_bounds__(TRK_THREADS) void k_plan(MapDev m, TrackParams tp, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-DEVFN int wave_sum_i(int v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
-DEVFN double wave_sum_d(double v) { for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d); return v; }
-
 struct SearchArgs {
   const uint8_t* img[NLEV]; size_t img_sstride[NLEV]; int img_pitch[NLEV];   // current frame pyramid
   const uint32_t* corners[NLEV]; const int* rowlut[NLEV]; const int* ncorners;
@@ -303,18 +290,6 @@ struct SearchArgs {
 // reference's 11x11 default -> 4 per wave), lane r < PS owns template row r as packed dwords (unused bytes zero).  Same
 // arithmetic per pixel / per candidate as the reference; no LDS, and the dependent global loads of the patches of a wave
 // overlap (a one-patch-per-wavefront version of this kernel was 2.4x slower at 8x8 and 2.7x slower at 11x11).  ZMSSD sums use v_dot4_u32_u8.
-template <int PS> struct PRow { unsigned w[(PS + 3) / 4]; };
-template <int PS> DEVFN PRow<PS> load_row(const uint8_t* p) {
-  PRow<PS> r;
-#pragma unroll
-  for (int k = 0; k < (PS + 3) / 4; k++) r.w[k] = 0u;
-  __builtin_memcpy(&r, p, PS);
-  return r;
-}
-template <int PS> DEVFN int row_byte(const PRow<PS>& r, int x) { return (int)((r.w[x >> 2] >> (8 * (x & 3))) & 255u); }
-template <int G> DEVFN int grp_sum_i(int v) { for (int d = 1; d < G; d <<= 1) v += __shfl_xor(v, d); return v; }
-template <int G> DEVFN double grp_sum_d(double v) { for (int d = 1; d < G; d <<= 1) v += __shfl_xor(v, d); return v; }
-DEVFN unsigned udot4(unsigned a, unsigned b, unsigned c) { return __builtin_amdgcn_udot4(a, b, c, false); }
 
 // Workgroups go to the eight XCDs of the device round-robin by their linear index, and every XCD has its own L2.  The search kernels
 // gather from one stream's frame pyramid and keyframes: with (patch block, stream) as (x, y) of the grid the ~140 workgroups of a stream
@@ -331,7 +306,7 @@ static int xcd_grid(int nblk, int S) { return nblk * ((S + TRK_XCDS - 1) / TRK_X
 
 template <int PS, int G>
 __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, SearchArgs a, int stage) {
-  constexpr int NPIX = PS * PS, HALF = PS / 2, PPW = 64 / G, NW = (PS + 3) / 4;
+  constexpr int NPIX = PS * PS, HALF = PS / 2, PPW = 64 / G;
   int s, bx;
   xcd_stream_block(a.nblk, a.S, s, bx);
   if (s < 0) return;
@@ -356,18 +331,10 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
   int flags = tdflags;
 
   // ---- MakeTemplateCoarseCont, jni/PatchFinder.cc:79-125 ----
-  double inv[4];
-  inv2(td.warp_inv, inv);
-  const double m2[4] = {inv[0] * scale, inv[1] * scale, inv[2] * scale, inv[3] * scale};
-  bool refresh = !(flags & TDF_HAVE_LAST);
-  for (int i = 0; !refresh && i < 2; i++) {
-    const double dx = m2[i] - td.last_warp[i], dy = m2[2 + i] - td.last_warp[2 + i];
-    if (dx * dx + dy * dy > 0.07 * 0.07) refresh = true;
-  }
-  refresh = refresh && act;
-  PRow<PS> trow;                                                     // template row `sub`
-#pragma unroll
-  for (int k = 0; k < NW; k++) trow.w[k] = 0u;
+  double m2[4];
+  template_warp_matrix(td.warp_inv, scale, m2);
+  const bool refresh = (!(flags & TDF_HAVE_LAST) || warp_moved(m2, td.last_warp)) && act;
+  PRow<PS> trow = zero_row<PS>();                                    // template row `sub`
   if (rowact) trow = load_row<PS>(gtmpl + sub * PS);                 // the cached row, fetched along with the tracker data; a refresh overwrites it
   const int tsum_cached = td.tsum, tsumsq_cached = td.tsumsq;
   int tsum, tsumsq;
@@ -376,43 +343,29 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
     const int sl = p.src_level;
     const uint8_t* src = m.kf_img[sl] + ((size_t)s * tp.max_keyframes + p.src_kf) * a.kf_stride[sl];
     const int sp = a.kf_pitch[sl], iw = a.w[sl], ih = a.h[sl];
-    const double across[2] = {m2[0], m2[2]}, down[2] = {m2[1], m2[3]};
-    double px = (double)p.irx - (m2[0] * HALF + m2[1] * HALF), py = (double)p.iry - (m2[2] * HALF + m2[3] * HALF);
-    const double cr[2] = {down[0] - PS * across[0], down[1] - PS * across[1]};
+    const TemplateWarp tw = template_warp<PS>(m2, p.irx, p.iry, iw, ih);
+    double px = tw.x0, py = tw.y0;
     // every lane walks the accumulated sample position through the rows above its own (PS steps + the carriage return
     // each, exactly the additions transform_image makes), then samples its row while stepping along it
 #pragma unroll 1
     for (int i = 0; i < PS - 1; i++) {
-      if (i < sub) {
-#pragma unroll
-        for (int j = 0; j < PS; j++) { px += across[0]; py += across[1]; }
-        px += cr[0]; py += cr[1];
-      }
+      if (i < sub) warp_row_step<PS>(tw, px, py);
     }
     if (refresh) {
       int nOutside = 0, sum = 0, sumsq = 0;
-      const float x_bound = (float)(iw - 1), y_bound = (float)(ih - 1);
       if (rowact) {
+        trow = zero_row<PS>();
 #pragma unroll
-      for (int k = 0; k < NW; k++) trow.w[k] = 0u;
-#pragma unroll
-      for (int j = 0; j < PS; j++) {
-        double x = px, y = py;
-        px += across[0]; py += across[1];
-        int v = 0;
-        if (0 <= x && 0 <= y && x < x_bound && y < y_bound) {
-          const int lx = (int)x, ly = (int)y;                        // sample(), ImageHandler.cpp:12-19
-          x -= lx; y -= ly;
-          const uint8_t* q0 = src + (size_t)ly * sp + lx;
-          v = (uint8_t)((1 - y) * ((1 - x) * q0[0] + x * q0[1]) + y * ((1 - x) * q0[sp] + x * q0[sp + 1]));
-        } else nOutside++;
-        trow.w[j >> 2] |= (unsigned)v << (8 * (j & 3));
-        sum += v; sumsq += v * v;
+        for (int j = 0; j < PS; j++) {
+          const int v = warp_sample(tw, src, sp, px, py, nOutside);
+          warp_pixel_step(tw, px, py);
+          trow.w[j >> 2] |= (unsigned)v << (8 * (j & 3));
+          sum += v; sumsq += v * v;
+        }
+        __builtin_memcpy(gtmpl + sub * PS, &trow, PS);
       }
-      __builtin_memcpy(gtmpl + sub * PS, &trow, PS);
-      }
-      nOutside = grp_sum_i<G>(nOutside);
-      tsum = grp_sum_i<G>(sum); tsumsq = grp_sum_i<G>(sumsq);        // MakeTemplateSums :152-164
+      nOutside = grp_sum<G>(nOutside);
+      tsum = grp_sum<G>(sum); tsumsq = grp_sum<G>(sumsq);        // MakeTemplateSums :152-164
       flags = nOutside ? (flags | TDF_TMPL_BAD) : (flags & ~TDF_TMPL_BAD);
       flags |= TDF_HAVE_LAST;
       if (lead) { td.tsum = tsum; td.tsumsq = tsumsq; for (int i = 0; i < 4; i++) td.last_warp[i] = m2[i]; }
@@ -430,12 +383,8 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
 
   // ---- FindPatchCoarse, jni/PatchFinder.cc:170-235 ----
   const double irx = td.image[0] / scale, iry = td.image[1] / scale;
-  const unsigned nRange = ((unsigned)nRangeL0 + scale - 1) / scale;
-  int nTop = (int)(iry - nRange);
-  const int nBottomPlusOne = (int)(iry + nRange + 1);
-  const int nLeft = (int)(irx - nRange), nRight = (int)(irx + nRange);
   const int rows = a.h[level], cols = a.w[level];
-  if (nTop < 0) nTop = 0;
+  const CoarseWindow cw = coarse_window(irx, iry, nRangeL0, scale, rows);
   int nBestSSD = tp.max_ssd + 1;
   uint32_t bestCorner = 0;                                           // packed position of the best candidate so far
   unsigned nEval = 0;
@@ -443,12 +392,12 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
   const uint8_t* img = a.img[level] + (size_t)s * a.img_sstride[level];
   const int ip = a.img_pitch[level];
   int i0 = 0, i1 = 0;
-  if (act && !(nTop >= rows) && !(nBottomPlusOne <= 0)) {
+  if (act && !cw.empty) {
     const int* lut = a.rowlut[level] + (size_t)s * (rows + 1);
-    i0 = lut[nTop];
-    i1 = nBottomPlusOne >= rows ? a.ncorners[s * NLEV + level] : lut[nBottomPlusOne];
+    i0 = lut[cw.top];
+    i1 = cw.bottom_plus_one >= rows ? a.ncorners[s * NLEV + level] : lut[cw.bottom_plus_one];
   }
-  const double r2max = (double)(nRange * nRange);
+  const double r2max = (double)(cw.range * cw.range);
   // Filter 4 G corners of the row-LUT window per step (:216-219: x window, then the circular range test): lane `sub` takes
   // corners base + j G + sub, j < 4, so the group's survivors form one bit mask in raster order.  Survivors are scored two
   // at a time (both image rows are in flight before either is used) and compared in raster order (:223).
@@ -467,7 +416,7 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
       bool ok = false;
       if (ci < i1) {
         const int cx = cval[j] & 0xFFFF, cy = cval[j] >> 16;
-        if (!(cx < nLeft || cx > nRight)) {
+        if (!(cx < cw.left || cx > cw.right)) {
           const double dx = irx - cx, dy = iry - cy;
           ok = !(dx * dx + dy * dy > r2max);
         }
@@ -487,27 +436,16 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
         c[u] = __shfl(csel, grp * G + (kk[u] % G));
         const int cx = c[u] & 0xFFFF, cy = c[u] >> 16;
         inside[u] = has[u] && cx >= HALF && cy >= HALF && cx < cols - HALF && cy < rows - HALF;   // in_image_with_border
-#pragma unroll
-        for (int k = 0; k < NW; k++) n[u].w[k] = 0u;
+        n[u] = zero_row<PS>();
         if (inside[u] && rowact) n[u] = load_row<PS>(img + (size_t)(cy - HALF + sub) * ip + (cx - HALF));
       }
 #pragma unroll
       for (int u = 0; u < 2; u++) {
         // ZMSSDAtPoint (:352-380): one image row per lane; the pad bytes of both rows are zero
-        unsigned sA = 0, sQ = 0, sX = 0;
-#pragma unroll
-        for (int k = 0; k < NW; k++) {
-          sA = udot4(n[u].w[k], 0x01010101u, sA);
-          sQ = udot4(n[u].w[k], n[u].w[k], sQ);
-          sX = udot4(n[u].w[k], trow.w[k], sX);
-        }
-        sA = grp_sum_i<G>(sA); sQ = grp_sum_i<G>(sQ); sX = grp_sum_i<G>(sX);
+        int sA, sQ, sX;
+        grp_zmssd_sums<PS, G>(n[u], trow, sA, sQ, sX);
         if (has[u]) {
-          int ssd = tp.max_ssd + 1;
-          if (inside[u]) {
-            const int SA = tsum, SB = (int)sA;
-            ssd = ((2 * SA * SB - SA * SA - SB * SB) / NPIX + (int)sQ + tsumsq - 2 * (int)sX);
-          }
+          const int ssd = inside[u] ? zmssd_score<NPIX>(tsum, tsumsq, sA, sQ, sX) : tp.max_ssd + 1;
           if (ssd < nBestSSD) { nBestSSD = ssd; bestCorner = c[u]; }   // first strict minimum in raster order (:223)
         }
       }
@@ -515,7 +453,7 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
   }
   flags |= TDF_SEARCHED;                                             // :645
   {
-    const int tot = wave_sum_i(act && lead ? (int)nEval : 0);
+    const int tot = wave_sum(act && lead ? (int)nEval : 0);
     if (lane == 0 && tot) atomicAdd(&st->n_zmssd, (unsigned long long)tot);
   }
   bool found = act && nBestSSD < tp.max_ssd;
@@ -556,9 +494,7 @@ DEVFN void subpix_block(const MapDev& m, const TrackParams& tp, const SearchArgs
   const int rows = a.h[level], cols = a.w[level];
   const uint8_t* img = a.img[level] + (size_t)s * a.img_sstride[level];
   const int ip = a.img_pitch[level];
-  PRow<PS> trow, rup, rdn;
-#pragma unroll
-  for (int k = 0; k < NW; k++) trow.w[k] = 0u;
+  PRow<PS> trow = zero_row<PS>(), rup, rdn;
   if (sub < PS) trow = load_row<PS>(m.tmpl + ((size_t)s * tp.max_points + idx) * TMPL_PITCH + sub * PS);
   const bool rowok = sub >= 1 && sub <= Q;
 #pragma unroll
@@ -575,8 +511,8 @@ DEVFN void subpix_block(const MapDev& m, const TrackParams& tp, const SearchArgs
       h11 += gy[x - 1] * gy[x - 1]; h12 += gy[x - 1]; h22 += 1.0;
     }
   }
-  h00 = grp_sum_d<G>(h00); h01 = grp_sum_d<G>(h01); h02 = grp_sum_d<G>(h02);     // quarter-integers: exact in any order
-  h11 = grp_sum_d<G>(h11); h12 = grp_sum_d<G>(h12); h22 = grp_sum_d<G>(h22);
+  h00 = grp_sum<G>(h00); h01 = grp_sum<G>(h01); h02 = grp_sum<G>(h02);     // quarter-integers: exact in any order
+  h11 = grp_sum<G>(h11); h12 = grp_sum<G>(h12); h22 = grp_sum<G>(h22);
   const double H[9] = {h00, h01, h02, h01, h11, h12, h02, h12, h22};
   double Hinv[9];
   inv3(H, Hinv);
@@ -1154,16 +1090,7 @@ extern "C" int vslam_debug_pose_prof(unsigned long long* out16, int reset) {
 #endif
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-template <class T>
-static int dalloc(vslam_system* sys, T** out, size_t count) {
-  void* ptr = nullptr;
-  HIPCHK(hipMalloc(&ptr, count * sizeof(T) + 64));
-  HIPCHK(hipMemsetAsync(ptr, 0, count * sizeof(T) + 64, sys->stream));
-  sys->allocs.push_back(ptr);
-  *out = (T*)ptr;
-  return VSLAM_OK;
-}
-#define TALLOC(ptr, count) do { int _r = dalloc(sys, &(ptr), (count)); if (_r) return _r; } while (0)
+#define TALLOC(ptr, count) do { int _r = dev_alloc(sys, &(ptr), (count)); if (_r) return _r; } while (0)
 
 int trk_alloc(vslam_system* sys) {
   const vslam_params& p = sys->p;

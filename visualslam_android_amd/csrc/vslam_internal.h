@@ -232,6 +232,17 @@ struct vslam_system {
   bool prof_on = false;
 };
 
+// count zeroed elements of T (and 64 bytes of slack) in HBM, owned by the handle
+template <class T>
+static inline int dev_alloc(vslam_system* sys, T** out, size_t count) {
+  void* ptr = nullptr;
+  HIPCHK(hipMalloc(&ptr, count * sizeof(T) + 64));
+  HIPCHK(hipMemsetAsync(ptr, 0, count * sizeof(T) + 64, sys->stream));
+  sys->allocs.push_back(ptr);
+  *out = (T*)ptr;
+  return VSLAM_OK;
+}
+
 #define PROF_MARKS (VSLAM_N_STAGES + 3)   // marks 0..2 + PROF_FE_END on the front-end stream, 3..VSLAM_N_STAGES on the main stream
 #define PROF_FE_END (VSLAM_N_STAGES + 1)
 #define PROF_BA_END (VSLAM_N_STAGES + 2)  // asynchronous map-maker: marks 12 and PROF_BA_END live on the BA stream
