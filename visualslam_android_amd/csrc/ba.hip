@@ -226,12 +226,29 @@ extern "C" int vslam_bundle_destroy(vslam_bundle* b) {
 
 #define BCHECK(cond, msg) do { if (!(cond)) { vslam_set_error("bundle: %s", msg); return VSLAM_E_INVALID; } } while (0)
 
+// Bundle::AddCamera / AddPoint / AddMeas on the host problem (jni/Bundle.cc:75-120): every rule about what may be appended is stated
+// here, for the per-item calls and for vslam_bundle_set_problem alike
+static void hp_add_camera(HostProblem& h, const double pose12[12], int fixed) { h.cams.push_back(pose_from12(pose12)); h.fixed.push_back(fixed ? 1 : 0); }
+static void hp_add_point(HostProblem& h, const double pos[3]) {
+  double q[3] = {pos[0], pos[1], pos[2]};
+  if (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] != q[0] * q[0] + q[1] * q[1] + q[2] * q[2]) q[0] = q[1] = q[2] = 0;   // NaN guard, jni/Bundle.cc:93-96
+  h.pts.insert(h.pts.end(), q, q + 3);
+}
+static int hp_add_meas(HostProblem& h, int cam, int point, const double pos[2], double sigma_squared, int max_meas) {
+  BCHECK(cam >= 0 && cam < (int)h.cams.size() && point >= 0 && point < (int)h.pts.size() / 3, "measurement refers to an unknown camera/point");   // asserts :107-108
+  BCHECK(!h.pairs.count(meas_key(cam, point)), "a second measurement of the same (camera, point) pair");
+  if ((int)h.mp.size() >= max_meas) { vslam_set_error("bundle: measurement capacity"); return VSLAM_E_CAPACITY; }
+  h.pairs.insert(meas_key(cam, point));
+  h.mp.push_back(point); h.mc.push_back(cam); h.mfound.push_back(pos[0]); h.mfound.push_back(pos[1]);
+  h.msin.push_back(sqrt(1.0 / sigma_squared));   // :115
+  return VSLAM_OK;
+}
+
 extern "C" int vslam_bundle_add_camera(vslam_bundle* b, int n, const double pose12[12], int fixed) {
   BCHECK(b && n >= 0 && n < b->pool.N && pose12, "bad camera argument");
   HostProblem& h = b->host[n];
   if ((int)h.cams.size() >= b->pool.max_cams) { vslam_set_error("bundle: camera capacity"); return VSLAM_E_CAPACITY; }
-  Pose p; for (int i = 0; i < 9; i++) p.R[i] = pose12[i]; for (int i = 0; i < 3; i++) p.t[i] = pose12[9 + i];
-  h.cams.push_back(p); h.fixed.push_back(fixed ? 1 : 0);
+  hp_add_camera(h, pose12, fixed);
   b->dirty = true;
   return (int)h.cams.size() - 1;
 }
@@ -240,22 +257,14 @@ extern "C" int vslam_bundle_add_point(vslam_bundle* b, int n, const double pos[3
   BCHECK(b && n >= 0 && n < b->pool.N && pos, "bad point argument");
   HostProblem& h = b->host[n];
   if ((int)h.pts.size() / 3 >= b->pool.max_pts) { vslam_set_error("bundle: point capacity"); return VSLAM_E_CAPACITY; }
-  double q[3] = {pos[0], pos[1], pos[2]};
-  if (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] != q[0] * q[0] + q[1] * q[1] + q[2] * q[2]) q[0] = q[1] = q[2] = 0;   // NaN guard, jni/Bundle.cc:93-96
-  h.pts.insert(h.pts.end(), q, q + 3);
+  hp_add_point(h, pos);
   b->dirty = true;
   return (int)h.pts.size() / 3 - 1;
 }
 
 extern "C" int vslam_bundle_add_meas(vslam_bundle* b, int n, int cam, int point, const double pos[2], double sigma_squared) {
   BCHECK(b && n >= 0 && n < b->pool.N && pos, "bad measurement argument");
-  HostProblem& h = b->host[n];
-  BCHECK(cam >= 0 && cam < (int)h.cams.size() && point >= 0 && point < (int)h.pts.size() / 3, "measurement refers to an unknown camera/point");   // asserts :107-108
-  BCHECK(!h.pairs.count(meas_key(cam, point)), "a second measurement of the same (camera, point) pair");
-  if ((int)h.mp.size() >= b->pool.max_meas) { vslam_set_error("bundle: measurement capacity"); return VSLAM_E_CAPACITY; }
-  h.pairs.insert(meas_key(cam, point));
-  h.mp.push_back(point); h.mc.push_back(cam); h.mfound.push_back(pos[0]); h.mfound.push_back(pos[1]);
-  h.msin.push_back(sqrt(1.0 / sigma_squared));   // :115
+  int r = hp_add_meas(b->host[n], cam, point, pos, sigma_squared, b->pool.max_meas); if (r) return r;
   b->dirty = true;
   return VSLAM_OK;
 }
@@ -268,18 +277,9 @@ extern "C" int vslam_bundle_set_problem(vslam_bundle* b, int n, int n_cams, cons
   BCHECK((n_cams == 0 || (pose12 && fixed)) && (n_pts == 0 || pos3) && (n_meas == 0 || (cam && point && xy && sigma_squared)), "set_problem: null array");
   if (n_cams > b->pool.max_cams || n_pts > b->pool.max_pts || n_meas > b->pool.max_meas) { vslam_set_error("bundle: set_problem exceeds the capacity"); return VSLAM_E_CAPACITY; }
   HostProblem h;                                     // built aside: a refused call leaves the problem as it was
-  for (int c = 0; c < n_cams; c++) { Pose p; for (int i = 0; i < 9; i++) p.R[i] = pose12[12 * c + i]; for (int i = 0; i < 3; i++) p.t[i] = pose12[12 * c + 9 + i]; h.cams.push_back(p); h.fixed.push_back(fixed[c] ? 1 : 0); }
-  for (int i = 0; i < n_pts; i++) {
-    double q[3] = {pos3[3 * i], pos3[3 * i + 1], pos3[3 * i + 2]};
-    if (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] != q[0] * q[0] + q[1] * q[1] + q[2] * q[2]) q[0] = q[1] = q[2] = 0;   // NaN guard, jni/Bundle.cc:93-96
-    h.pts.insert(h.pts.end(), q, q + 3);
-  }
-  for (int i = 0; i < n_meas; i++) {
-    BCHECK(cam[i] >= 0 && cam[i] < n_cams && point[i] >= 0 && point[i] < n_pts, "measurement refers to an unknown camera/point");
-    BCHECK(h.pairs.insert(meas_key(cam[i], point[i])).second, "a second measurement of the same (camera, point) pair");
-    h.mp.push_back(point[i]); h.mc.push_back(cam[i]); h.mfound.push_back(xy[2 * i]); h.mfound.push_back(xy[2 * i + 1]);
-    h.msin.push_back(sqrt(1.0 / sigma_squared[i]));
-  }
+  for (int c = 0; c < n_cams; c++) hp_add_camera(h, pose12 + 12 * c, fixed[c]);
+  for (int i = 0; i < n_pts; i++) hp_add_point(h, pos3 + 3 * i);
+  for (int i = 0; i < n_meas; i++) { int r = hp_add_meas(h, cam[i], point[i], xy + 2 * i, sigma_squared[i], n_meas); if (r) return r; }
   b->host[n] = std::move(h);
   b->dirty = true;
   return VSLAM_OK;
@@ -370,7 +370,7 @@ extern "C" int vslam_bundle_get_camera(vslam_bundle* b, int n, int i, double pos
   BCHECK(i >= 0 && i < r.n_cams, "camera index");
   Pose p;
   HIPCHK(hipMemcpy(&p, ba_view(b->pool, n).cam_pose + i, sizeof(Pose), hipMemcpyDeviceToHost));
-  for (int k = 0; k < 9; k++) pose12[k] = p.R[k]; for (int k = 0; k < 3; k++) pose12[9 + k] = p.t[k];
+  pose_to12(p, pose12);
   return VSLAM_OK;
 }
 extern "C" int vslam_bundle_get_point(vslam_bundle* b, int n, int i, double pos[3]) {

@@ -1,4 +1,7 @@
 // Map upload, per-frame entry points (Tracker::TrackFrame / JNI-equivalent update) and read-back of the C ABI.
+// Every upload has one body, for n items; its per-item entry point is that body with n = 1.
+// Host-stream ordering: sys->stream is non-blocking, so a hipMemcpy on the null stream does not wait for it.  get_states, put_state and
+// download wait for the main stream themselves; every other copy in this file follows one of the three.
 #include "vslam_internal.h"
 #include "patch_dev.h"
 #include <stdlib.h>
@@ -7,58 +10,28 @@
 
 #define CHK_STREAM(sys, s) do { if (!(sys) || (s) < 0 || (s) >= (sys)->S) { vslam_set_error("bad system/stream"); return VSLAM_E_INVALID; } } while (0)
 
-static int get_state(vslam_system* sys, int s, TrackerState* st) {
-  HIPCHK(hipMemcpyAsync(st, sys->map.st + s, sizeof(TrackerState), hipMemcpyDeviceToHost, sys->stream));
+static int get_states(vslam_system* sys, int first, int n, TrackerState* st) {
+  HIPCHK(hipMemcpyAsync(st, sys->map.st + first, sizeof(TrackerState) * n, hipMemcpyDeviceToHost, sys->stream));
   HIPCHK(hipStreamSynchronize(sys->stream));
   return VSLAM_OK;
 }
+static int get_state(vslam_system* sys, int s, TrackerState* st) { return get_states(sys, s, 1, st); }
 static int put_state(vslam_system* sys, int s, const TrackerState* st) {
   HIPCHK(hipMemcpyAsync(sys->map.st + s, st, sizeof(TrackerState), hipMemcpyHostToDevice, sys->stream));
   HIPCHK(hipStreamSynchronize(sys->stream));
   return VSLAM_OK;
 }
-
-// one pyramid level of a stored keyframe: (a+b+c+d+2)>>2 (jni/KeyFrame.cc:19-23, see frontend.hip)
-__global__ void k_halve_plain(const uint8_t* src, int sp, uint8_t* dst, int dp, int dw, int dh) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= dw || y >= dh) return;
-  const uint8_t* r0 = src + (size_t)(2 * y) * sp + 2 * x;
-  const uint8_t* r1 = r0 + sp;
-  dst[(size_t)y * dp + x] = (uint8_t)((r0[0] + r0[1] + r1[0] + r1[1] + 2) >> 2);
+// read-back of n elements of a device array (n = 0 allowed), after everything the main stream holds
+template <class T>
+static int download(vslam_system* sys, const T* src, int n, std::vector<T>& out) {
+  HIPCHK(hipStreamSynchronize(sys->stream));
+  out.resize(n > 0 ? n : 0);
+  if (n > 0) HIPCHK(hipMemcpy(out.data(), src, sizeof(T) * n, hipMemcpyDeviceToHost));
+  return VSLAM_OK;
 }
 
-extern "C" int vslam_map_add_keyframe(vslam_system* sys, int s, const double pose12[12], int fixed, const uint8_t* gray,
-                                      size_t row_stride, double depth_mean, double depth_sigma) {
-  CHK_STREAM(sys, s);
-  if (!pose12 || !gray || (int)row_stride < sys->geom[0].w) { vslam_set_error("map_add_keyframe: bad argument"); return VSLAM_E_INVALID; }
-  TrackerState st;
-  int r = get_state(sys, s, &st); if (r) return r;
-  const int K = sys->p.max_keyframes;
-  if (st.n_kf >= K) { vslam_set_error("keyframe capacity %d reached", K); return VSLAM_E_CAPACITY; }
-  const int k = st.n_kf;
-  const LevelGeom* g = sys->geom;
-  uint8_t* lvl[NLEV];
-  for (int l = 0; l < NLEV; l++) lvl[l] = sys->map.kf_img[l] + ((size_t)s * K + k) * ((size_t)g[l].pitch * g[l].h);
-  HIPCHK(hipMemcpy2DAsync(lvl[0], g[0].pitch, gray, row_stride, g[0].w, g[0].h, hipMemcpyHostToDevice, sys->stream));
-  for (int l = 1; l < NLEV; l++)
-    hipLaunchKernelGGL(k_halve_plain, dim3((g[l].w + 255) / 256, g[l].h), dim3(256), 0, sys->stream, lvl[l - 1], g[l - 1].pitch, lvl[l], g[l].pitch, g[l].w, g[l].h);
-  Pose p;
-  for (int i = 0; i < 9; i++) p.R[i] = pose12[i];
-  for (int i = 0; i < 3; i++) p.t[i] = pose12[9 + i];
-  const double dd[2] = {depth_mean, depth_sigma};
-  const int fx = fixed ? 1 : 0;
-  HIPCHK(hipMemcpyAsync(sys->map.kf_pose + (size_t)s * K + k, &p, sizeof(Pose), hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemcpyAsync(sys->map.kf_fixed + (size_t)s * K + k, &fx, sizeof(int), hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemcpyAsync(sys->map.kf_depth + ((size_t)s * K + k) * 2, dd, sizeof(dd), hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemsetAsync(sys->map.kf_meas + ((size_t)s * K + k) * sys->p.max_points, 0, sizeof(MeasDev) * sys->p.max_points, sys->stream));
-  if (sys->p.grow_map || sys->p.idle_iterations != 0) { r = fe_keyframe_corners(sys, s, k); if (r) return r; }   // Level::vCorners, needed as an epipolar-search target
-  r = reloc_keyframe_sbi(sys, s, k, 1); if (r) return r;                // KeyFrame::pSBI (relocalise)
-  st.n_kf = k + 1;
-  r = put_state(sys, s, &st); if (r) return r;
-  return k;
-}
-
-// the same level for n images at once (blockIdx.z = image; images sstride / dstride bytes apart)
+// one pyramid level of n stored keyframes: (a+b+c+d+2)>>2 (jni/KeyFrame.cc:19-23, see frontend.hip); blockIdx.z = image, images
+// sstride / dstride bytes apart
 __global__ void k_halve_batch(const uint8_t* src, int sp, size_t sstride, uint8_t* dst, int dp, size_t dstride, int dw, int dh) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= dw || y >= dh) return;
@@ -67,22 +40,11 @@ __global__ void k_halve_batch(const uint8_t* src, int sp, size_t sstride, uint8_
   dst[(size_t)blockIdx.z * dstride + (size_t)y * dp + x] = (uint8_t)((r0[0] + r0[1] + r1[0] + r1[1] + 2) >> 2);
 }
 
-// vslam_map_add_keyframe for n keyframes of one stream at once: one pyramid launch per level and one clear of the measurement rows for
-// all of them (a map upload of eight keyframes is 4 kernel launches instead of 32: set-up of thousands of streams, and profiler passes
-// that serialise every dispatch).  gray: n images image_stride bytes apart.  Returns the index of the first new keyframe.
-extern "C" int vslam_map_add_keyframes(vslam_system* sys, int s, int n, const double* pose12, const int* fixed, const uint8_t* gray, size_t row_stride,
-                                       size_t image_stride, const double* depth_mean_sigma) {
-  CHK_STREAM(sys, s);
-  if (n < 1 || !pose12 || !fixed || !gray || !depth_mean_sigma || (int)row_stride < sys->geom[0].w) { vslam_set_error("map_add_keyframes: bad argument"); return VSLAM_E_INVALID; }
-  if (sys->p.grow_map || sys->p.idle_iterations != 0) {                 // keyframe corner lists are made one keyframe at a time
-    int first = -1;
-    for (int i = 0; i < n; i++) {
-      const int k = vslam_map_add_keyframe(sys, s, pose12 + 12 * i, fixed[i], gray + (size_t)i * image_stride, row_stride, depth_mean_sigma[2 * i], depth_mean_sigma[2 * i + 1]);
-      if (k < 0) return k;
-      if (i == 0) first = k;
-    }
-    return first;
-  }
+// n keyframes of one stream: one pyramid launch per level and one clear of the measurement rows for all of them (a map upload of eight
+// keyframes is 4 kernel launches instead of 32: set-up of thousands of streams, and profiler passes that serialise every dispatch).
+// gray: n images image_stride bytes apart.  Returns the index of the first new keyframe.
+static int add_keyframes(vslam_system* sys, int s, int n, const double* pose12, const int* fixed, const uint8_t* gray, size_t row_stride,
+                         size_t image_stride, const double* depth_mean_sigma) {
   TrackerState st;
   int r = get_state(sys, s, &st); if (r) return r;
   const int K = sys->p.max_keyframes;
@@ -96,86 +58,36 @@ extern "C" int vslam_map_add_keyframes(vslam_system* sys, int s, int n, const do
   for (int l = 1; l < NLEV; l++)
     hipLaunchKernelGGL(k_halve_batch, dim3((g[l].w + 255) / 256, g[l].h, n), dim3(256), 0, sys->stream, lvl[l - 1], g[l - 1].pitch, ls[l - 1], lvl[l], g[l].pitch, ls[l], g[l].w, g[l].h);
   std::vector<Pose> p((size_t)n); std::vector<int> fx((size_t)n);
-  for (int i = 0; i < n; i++) { for (int q = 0; q < 9; q++) p[i].R[q] = pose12[12 * i + q]; for (int q = 0; q < 3; q++) p[i].t[q] = pose12[12 * i + 9 + q]; fx[i] = fixed[i] ? 1 : 0; }
+  for (int i = 0; i < n; i++) { p[i] = pose_from12(pose12 + 12 * i); fx[i] = fixed[i] ? 1 : 0; }
   HIPCHK(hipMemcpyAsync(sys->map.kf_pose + (size_t)s * K + k, p.data(), sizeof(Pose) * n, hipMemcpyHostToDevice, sys->stream));
   HIPCHK(hipMemcpyAsync(sys->map.kf_fixed + (size_t)s * K + k, fx.data(), sizeof(int) * n, hipMemcpyHostToDevice, sys->stream));
   HIPCHK(hipMemcpyAsync(sys->map.kf_depth + ((size_t)s * K + k) * 2, depth_mean_sigma, sizeof(double) * 2 * n, hipMemcpyHostToDevice, sys->stream));
   HIPCHK(hipMemsetAsync(sys->map.kf_meas + ((size_t)s * K + k) * sys->p.max_points, 0, sizeof(MeasDev) * sys->p.max_points * (size_t)n, sys->stream));
+  if (sys->p.grow_map || sys->p.idle_iterations != 0)                   // Level::vCorners, needed as an epipolar-search target: from the stored
+    for (int i = 0; i < n; i++) { r = fe_keyframe_corners(sys, s, k + i); if (r) return r; }   // images alone, one keyframe at a time
   r = reloc_keyframe_sbi(sys, s, k, n); if (r) return r;                // KeyFrame::pSBI (relocalise)
   st.n_kf = k + n;
   r = put_state(sys, s, &st); if (r) return r;         // (synchronises: the host arrays above are done with)
   return k;
 }
 
-extern "C" int vslam_map_add_point(vslam_system* sys, int s, const double pos[3], int src_keyframe, int src_level, int ir_x,
-                                   int ir_y, const double right[3], const double down[3]) {
+extern "C" int vslam_map_add_keyframe(vslam_system* sys, int s, const double pose12[12], int fixed, const uint8_t* gray,
+                                      size_t row_stride, double depth_mean, double depth_sigma) {
   CHK_STREAM(sys, s);
-  TrackerState st;
-  int r = get_state(sys, s, &st); if (r) return r;
-  if (!pos || !right || !down || src_keyframe < 0 || src_keyframe >= st.n_kf || src_level < 0 || src_level >= NLEV) { vslam_set_error("map_add_point: bad argument"); return VSLAM_E_INVALID; }
-  const int P = sys->p.max_points;
-  if (st.n_points >= P) { vslam_set_error("map point capacity %d reached", P); return VSLAM_E_CAPACITY; }
-  const int i = st.n_points;
-  MapPointDev mp; memset(&mp, 0, sizeof(mp));
-  for (int q = 0; q < 3; q++) { mp.pos[q] = pos[q]; mp.right[q] = right[q]; mp.down[q] = down[q]; }
-  mp.src_kf = src_keyframe; mp.src_level = src_level; mp.irx = ir_x; mp.iry = ir_y;
-  const TrackData td = fresh_track_data();
-  const int lvl0[2] = {-1, 0};
-  HIPCHK(hipMemcpyAsync(sys->map.pt_level + (size_t)s * P + i, &lvl0[0], sizeof(int), hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemcpyAsync(sys->map.pt_flags + (size_t)s * P + i, &lvl0[1], sizeof(int), hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemcpyAsync(sys->map.pts + (size_t)s * P + i, &mp, sizeof(mp), hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemcpyAsync(sys->map.td + (size_t)s * P + i, &td, sizeof(td), hipMemcpyHostToDevice, sys->stream));
-  st.n_points = i + 1;
-  st.newq_head = st.n_points;                 // uploaded points are not "newly made" (mqNewQueue holds AddPointEpipolar's)
-  r = put_state(sys, s, &st); if (r) return r;
-  return i;
+  if (!pose12 || !gray || (int)row_stride < sys->geom[0].w) { vslam_set_error("map_add_keyframe: bad argument"); return VSLAM_E_INVALID; }
+  const double dd[2] = {depth_mean, depth_sigma};
+  return add_keyframes(sys, s, 1, pose12, &fixed, gray, row_stride, 0, dd);
 }
 
-extern "C" int vslam_map_add_measurement(vslam_system* sys, int s, int keyframe, int point, int level, const double root_pos[2],
-                                         int subpix, int source) {
+extern "C" int vslam_map_add_keyframes(vslam_system* sys, int s, int n, const double* pose12, const int* fixed, const uint8_t* gray, size_t row_stride,
+                                       size_t image_stride, const double* depth_mean_sigma) {
   CHK_STREAM(sys, s);
-  TrackerState st;
-  int r = get_state(sys, s, &st); if (r) return r;
-  if (!root_pos || keyframe < 0 || keyframe >= st.n_kf || point < 0 || point >= st.n_points || level < 0 || level >= NLEV) { vslam_set_error("map_add_measurement: bad argument"); return VSLAM_E_INVALID; }
-  const int P = sys->p.max_points, K = sys->p.max_keyframes;
-  MeasDev* slot = sys->map.kf_meas + ((size_t)s * K + keyframe) * P + point;
-  MeasDev old;
-  HIPCHK(hipMemcpy(&old, slot, sizeof(old), hipMemcpyDeviceToHost));
-  MeasDev m; memset(&m, 0, sizeof(m));
-  m.root[0] = root_pos[0]; m.root[1] = root_pos[1]; m.valid = 1; m.level = (signed char)level; m.subpix = subpix ? 1 : 0; m.source = (signed char)source;
-  HIPCHK(hipMemcpy(slot, &m, sizeof(m), hipMemcpyHostToDevice));
-  if (!old.valid) {   // MapMakerData::sMeasurementKFs.insert
-    MapPointDev mp;
-    HIPCHK(hipMemcpy(&mp, sys->map.pts + (size_t)s * P + point, sizeof(mp), hipMemcpyDeviceToHost));
-    mp.n_meas_kfs++;
-    HIPCHK(hipMemcpy(sys->map.pts + (size_t)s * P + point, &mp, sizeof(mp), hipMemcpyHostToDevice));
-  }
-  return VSLAM_OK;
+  if (n < 1 || !pose12 || !fixed || !gray || !depth_mean_sigma || (int)row_stride < sys->geom[0].w) { vslam_set_error("map_add_keyframes: bad argument"); return VSLAM_E_INVALID; }
+  return add_keyframes(sys, s, n, pose12, fixed, gray, row_stride, image_stride, depth_mean_sigma);
 }
 
-// bulk upload used by the Python mirror for speed: arrays of n measurements
-extern "C" int vslam_map_add_measurements(vslam_system* sys, int s, int n, const int* keyframe, const int* point, const int* level,
-                                          const double* root_pos, const int* subpix, const int* source) {
-  CHK_STREAM(sys, s);
-  TrackerState st;
-  int r = get_state(sys, s, &st); if (r) return r;
-  const int P = sys->p.max_points, K = sys->p.max_keyframes;
-  std::vector<MeasDev> km((size_t)K * P);
-  std::vector<MapPointDev> pts(P);
-  HIPCHK(hipMemcpy(km.data(), sys->map.kf_meas + (size_t)s * K * P, sizeof(MeasDev) * km.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(pts.data(), sys->map.pts + (size_t)s * P, sizeof(MapPointDev) * P, hipMemcpyDeviceToHost));
-  for (int i = 0; i < n; i++) {
-    if (keyframe[i] < 0 || keyframe[i] >= st.n_kf || point[i] < 0 || point[i] >= st.n_points || level[i] < 0 || level[i] >= NLEV) { vslam_set_error("map_add_measurements: bad entry %d", i); return VSLAM_E_INVALID; }
-    MeasDev& m = km[(size_t)keyframe[i] * P + point[i]];
-    if (!m.valid) pts[point[i]].n_meas_kfs++;
-    m.root[0] = root_pos[2 * i]; m.root[1] = root_pos[2 * i + 1]; m.valid = 1; m.level = (signed char)level[i]; m.subpix = subpix[i] ? 1 : 0; m.source = (signed char)source[i]; m.pad = 0;
-  }
-  HIPCHK(hipMemcpy(sys->map.kf_meas + (size_t)s * K * P, km.data(), sizeof(MeasDev) * km.size(), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(sys->map.pts + (size_t)s * P, pts.data(), sizeof(MapPointDev) * P, hipMemcpyHostToDevice));
-  return VSLAM_OK;
-}
-
-// bulk form of vslam_map_add_point: n points at once (arrays of n; pos/right/down 3n doubles, ir 2n ints)
+// n points (arrays of n; pos/right/down 3n doubles, ir 2n ints).  Returns the new number of points.  The capacity is checked before the
+// entries, so a call that is wrong in both ways reports VSLAM_E_CAPACITY; a refused call has written nothing.
 extern "C" int vslam_map_add_points(vslam_system* sys, int s, int n, const double* pos, const int* src_keyframe, const int* src_level,
                                     const int* ir_xy, const double* right, const double* down) {
   CHK_STREAM(sys, s);
@@ -200,9 +112,60 @@ extern "C" int vslam_map_add_points(vslam_system* sys, int s, int n, const doubl
     HIPCHK(hipMemcpy(sys->map.pt_flags + (size_t)s * P + st.n_points, fl.data(), sizeof(int) * n, hipMemcpyHostToDevice));
   }
   st.n_points += n;
-  st.newq_head = st.n_points;
+  st.newq_head = st.n_points;                 // uploaded points are not "newly made" (mqNewQueue holds AddPointEpipolar's)
   r = put_state(sys, s, &st); if (r) return r;
   return st.n_points;
+}
+
+// ... and one: returns the new point's index
+extern "C" int vslam_map_add_point(vslam_system* sys, int s, const double pos[3], int src_keyframe, int src_level, int ir_x,
+                                   int ir_y, const double right[3], const double down[3]) {
+  CHK_STREAM(sys, s);
+  const int ir[2] = {ir_x, ir_y};
+  const int r = pos && right && down ? vslam_map_add_points(sys, s, 1, pos, &src_keyframe, &src_level, ir, right, down) : VSLAM_E_INVALID;
+  if (r == VSLAM_E_INVALID) vslam_set_error("map_add_point: bad argument");
+  return r < 0 ? r : r - 1;
+}
+
+// n measurements (arrays of n).  Every entry is checked before anything changes: a refused call leaves the map as it was.  Only the
+// part of the stream's [K][P] measurement table that the entries touch travels, keyframes [k0, k1] x points [p0, p1], and the same
+// range of points (for one measurement: one slot and one point).
+extern "C" int vslam_map_add_measurements(vslam_system* sys, int s, int n, const int* keyframe, const int* point, const int* level,
+                                          const double* root_pos, const int* subpix, const int* source) {
+  CHK_STREAM(sys, s);
+  TrackerState st;
+  int r = get_state(sys, s, &st); if (r) return r;
+  if (n <= 0) return VSLAM_OK;
+  int k0 = keyframe[0], k1 = k0, p0 = point[0], p1 = p0;
+  for (int i = 0; i < n; i++) {
+    if (keyframe[i] < 0 || keyframe[i] >= st.n_kf || point[i] < 0 || point[i] >= st.n_points || level[i] < 0 || level[i] >= NLEV) { vslam_set_error("map_add_measurements: bad entry %d", i); return VSLAM_E_INVALID; }
+    if (keyframe[i] < k0) k0 = keyframe[i]; if (keyframe[i] > k1) k1 = keyframe[i];
+    if (point[i] < p0) p0 = point[i]; if (point[i] > p1) p1 = point[i];
+  }
+  const size_t P = sys->p.max_points, K = sys->p.max_keyframes, nk = k1 - k0 + 1, np = p1 - p0 + 1;
+  MeasDev* d_km = sys->map.kf_meas + ((size_t)s * K + k0) * P + p0;
+  MapPointDev* d_pts = sys->map.pts + (size_t)s * P + p0;
+  std::vector<MeasDev> km(nk * np);
+  std::vector<MapPointDev> pts(np);
+  HIPCHK(hipMemcpy2D(km.data(), np * sizeof(MeasDev), d_km, P * sizeof(MeasDev), np * sizeof(MeasDev), nk, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(pts.data(), d_pts, sizeof(MapPointDev) * np, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; i++) {
+    MeasDev& m = km[(size_t)(keyframe[i] - k0) * np + (point[i] - p0)];
+    if (!m.valid) pts[point[i] - p0].n_meas_kfs++;   // MapMakerData::sMeasurementKFs.insert
+    memset(&m, 0, sizeof(m));
+    m.root[0] = root_pos[2 * i]; m.root[1] = root_pos[2 * i + 1]; m.valid = 1; m.level = (signed char)level[i]; m.subpix = subpix[i] ? 1 : 0; m.source = (signed char)source[i];
+  }
+  HIPCHK(hipMemcpy2D(d_km, P * sizeof(MeasDev), km.data(), np * sizeof(MeasDev), np * sizeof(MeasDev), nk, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(d_pts, pts.data(), sizeof(MapPointDev) * np, hipMemcpyHostToDevice));
+  return VSLAM_OK;
+}
+
+extern "C" int vslam_map_add_measurement(vslam_system* sys, int s, int keyframe, int point, int level, const double root_pos[2],
+                                         int subpix, int source) {
+  CHK_STREAM(sys, s);
+  const int r = root_pos ? vslam_map_add_measurements(sys, s, 1, &keyframe, &point, &level, root_pos, &subpix, &source) : VSLAM_E_INVALID;
+  if (r == VSLAM_E_INVALID) vslam_set_error("map_add_measurement: bad argument");
+  return r;
 }
 
 extern "C" int vslam_map_set_good(vslam_system* sys, int s) {
@@ -232,8 +195,7 @@ extern "C" int vslam_set_pose(vslam_system* sys, int s, const double pose12[12])
   TrackerState st;
   int r = get_state(sys, s, &st); if (r) return r;
   reset_tracker_fields(st);
-  for (int i = 0; i < 9; i++) st.pose_final.R[i] = pose12[i];
-  for (int i = 0; i < 3; i++) st.pose_final.t[i] = pose12[9 + i];
+  st.pose_final = pose_from12(pose12);
   st.pose_cur = st.pose_final; st.start_pose = st.pose_final;
   return put_state(sys, s, &st);
 }
@@ -348,9 +310,7 @@ extern "C" int vslam_map_set_keyframe_pose(vslam_system* sys, int s, int keyfram
   TrackerState st;
   int r = get_state(sys, s, &st); if (r) return r;
   if (!pose12 || keyframe < 0 || keyframe >= st.n_kf) { vslam_set_error("map_set_keyframe_pose: bad argument"); return VSLAM_E_INVALID; }
-  Pose p;
-  for (int i = 0; i < 9; i++) p.R[i] = pose12[i];
-  for (int i = 0; i < 3; i++) p.t[i] = pose12[9 + i];
+  const Pose p = pose_from12(pose12);
   HIPCHK(hipMemcpy(sys->map.kf_pose + (size_t)s * sys->p.max_keyframes + keyframe, &p, sizeof(Pose), hipMemcpyHostToDevice));
   return VSLAM_OK;
 }
@@ -418,31 +378,26 @@ extern "C" int vslam_bundle_adjust_all(vslam_system* sys) { if (!sys) return VSL
 // ---- read-back ------------------------------------------------------------------------------------------------------
 static void export_state(const vslam_system* sys, const TrackerState& st, vslam_track_state* o);
 
-extern "C" int vslam_get_state(vslam_system* sys, int s, vslam_track_state* o) {
-  CHK_STREAM(sys, s);
-  if (!o) return VSLAM_E_INVALID;
-  TrackerState st;
-  int r = get_state(sys, s, &st); if (r) return r;
-  export_state(sys, st, o);
-  return VSLAM_OK;
-}
-
 // vslam_get_state for the streams [first, first + n) with one copy (a caller that polls thousands of streams one by one idles the GPU
 // for tens of milliseconds, long enough for its clocks to drop)
 extern "C" int vslam_get_states(vslam_system* sys, int first, int n, vslam_track_state* out) {
   if (!sys || !out || first < 0 || n < 0 || first + n > sys->S) { vslam_set_error("get_states: bad argument"); return VSLAM_E_INVALID; }
   if (n == 0) return VSLAM_OK;
   std::vector<TrackerState> v((size_t)n);
-  HIPCHK(hipMemcpyAsync(v.data(), sys->map.st + first, sizeof(TrackerState) * n, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
+  int r = get_states(sys, first, n, v.data()); if (r) return r;
   for (int i = 0; i < n; i++) export_state(sys, v[(size_t)i], out + i);
   return VSLAM_OK;
 }
 
+extern "C" int vslam_get_state(vslam_system* sys, int s, vslam_track_state* o) {
+  CHK_STREAM(sys, s);
+  if (!o) return VSLAM_E_INVALID;
+  return vslam_get_states(sys, s, 1, o);
+}
+
 static void export_state(const vslam_system* sys, const TrackerState& st, vslam_track_state* o) {
   const Pose& T = sys->frame_open ? st.pose_cur : st.pose_final;   // between the stages of a frame: the tracker's current estimate
-  for (int i = 0; i < 9; i++) o->pose[i] = T.R[i];
-  for (int i = 0; i < 3; i++) o->pose[9 + i] = T.t[i];
+  pose_to12(T, o->pose);
   for (int i = 0; i < 6; i++) o->velocity[i] = st.velocity[i];
   o->msd_velocity = st.msd_vel; o->depth_mean = st.depth_mean; o->depth_sigma = st.depth_sigma;
   for (int i = 0; i < NLEV; i++) { o->attempted[i] = st.attempted[i]; o->found[i] = st.found[i]; }
@@ -523,8 +478,8 @@ extern "C" int vslam_load_map(vslam_system* sys, int s, const char* dir) {
   std::vector<int> lev((size_t)(n > 0 ? n : 1));
   int np = 0, nkf = 0;
   r = vslam_read_map_dump(dir, pos.data(), lev.data(), n, &np, poses.data(), nk, &nkf); if (r) return r;
-  std::vector<MapPointDev> p((size_t)(n > 0 ? n : 1));
-  if (n > 0) HIPCHK(hipMemcpy(p.data(), sys->map.pts + (size_t)s * sys->p.max_points, sizeof(MapPointDev) * n, hipMemcpyDeviceToHost));
+  std::vector<MapPointDev> p;
+  r = download(sys, sys->map.pts + (size_t)s * sys->p.max_points, n, p); if (r) return r;
   int good = 0;
   for (int i = 0; i < n; i++) if (!p[i].bad) good++;
   if (np != good || nkf != nk) { vslam_set_error("load_map: the dump holds %d points and %d keyframes, the map %d good points and %d keyframes", np, nkf, good, nk); return VSLAM_E_STATE; }
@@ -561,13 +516,11 @@ extern "C" int vslam_get_point_tracks(vslam_system* sys, int s, int* found, int*
   TrackerState st;
   int r = get_state(sys, s, &st); if (r) return r;
   const int n = st.n_points < cap ? st.n_points : cap;
-  std::vector<TrackData> td(n > 0 ? n : 1);
-  std::vector<int> lv(n > 0 ? n : 1), fl(n > 0 ? n : 1);
-  if (n > 0) {
-    HIPCHK(hipMemcpy(td.data(), sys->map.td + (size_t)s * sys->p.max_points, sizeof(TrackData) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(lv.data(), sys->map.pt_level + (size_t)s * sys->p.max_points, sizeof(int) * n, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(fl.data(), sys->map.pt_flags + (size_t)s * sys->p.max_points, sizeof(int) * n, hipMemcpyDeviceToHost));
-  }
+  std::vector<TrackData> td;
+  std::vector<int> lv, fl;
+  r = download(sys, sys->map.td + (size_t)s * sys->p.max_points, n, td); if (r) return r;
+  r = download(sys, sys->map.pt_level + (size_t)s * sys->p.max_points, n, lv); if (r) return r;
+  r = download(sys, sys->map.pt_flags + (size_t)s * sys->p.max_points, n, fl); if (r) return r;
   for (int i = 0; i < n; i++) {
     if (found) found[i] = (fl[i] & TDF_FOUND) ? 1 : 0;
     if (searched) searched[i] = (fl[i] & TDF_SEARCHED) ? 1 : 0;
@@ -584,8 +537,8 @@ extern "C" int vslam_get_points(vslam_system* sys, int s, double* pos3, int* bad
   TrackerState st;
   int r = get_state(sys, s, &st); if (r) return r;
   const int n = st.n_points < cap ? st.n_points : cap;
-  std::vector<MapPointDev> p(n > 0 ? n : 1);
-  if (n > 0) HIPCHK(hipMemcpy(p.data(), sys->map.pts + (size_t)s * sys->p.max_points, sizeof(MapPointDev) * n, hipMemcpyDeviceToHost));
+  std::vector<MapPointDev> p;
+  r = download(sys, sys->map.pts + (size_t)s * sys->p.max_points, n, p); if (r) return r;
   for (int i = 0; i < n; i++) {
     if (pos3) for (int q = 0; q < 3; q++) pos3[3 * i + q] = p[i].pos[q];
     if (bad) bad[i] = p[i].bad;
@@ -598,11 +551,9 @@ extern "C" int vslam_get_points(vslam_system* sys, int s, double* pos3, int* bad
 extern "C" int vslam_get_keyframe_pose(vslam_system* sys, int s, int k, double pose12[12]) {
   CHK_STREAM(sys, s);
   if (k < 0 || k >= sys->p.max_keyframes || !pose12) return VSLAM_E_INVALID;
-  Pose p;
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  HIPCHK(hipMemcpy(&p, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes + k, sizeof(p), hipMemcpyDeviceToHost));
-  for (int i = 0; i < 9; i++) pose12[i] = p.R[i];
-  for (int i = 0; i < 3; i++) pose12[9 + i] = p.t[i];
+  std::vector<Pose> p;
+  int r = download(sys, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes + k, 1, p); if (r) return r;
+  pose_to12(p[0], pose12);
   return VSLAM_OK;
 }
 
@@ -611,8 +562,8 @@ extern "C" int vslam_get_keyframe_pose(vslam_system* sys, int s, int k, double p
 static int nearest_keyframe_dist(vslam_system* sys, int s, TrackerState* st, double* dist) {
   int r = get_state(sys, s, st); if (r) return r;
   if (st->n_kf < 1) { vslam_set_error("no keyframes"); return VSLAM_E_STATE; }
-  std::vector<Pose> kp(st->n_kf);
-  HIPCHK(hipMemcpy(kp.data(), sys->map.kf_pose + (size_t)s * sys->p.max_keyframes, sizeof(Pose) * st->n_kf, hipMemcpyDeviceToHost));
+  std::vector<Pose> kp;
+  r = download(sys, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes, st->n_kf, kp); if (r) return r;
   const Pose ic = pose_inverse(st->pose_final);
   double best = 9999999999.9;                                      // ClosestKeyFrame :737-758 with KeyFrameLinearDist :705-712
   for (int k = 0; k < st->n_kf; k++) {
@@ -652,10 +603,10 @@ extern "C" int vslam_save_map(vslam_system* sys, int s, const char* dir) {
   TrackerState st;
   int r = get_state(sys, s, &st); if (r) return r;
   const int n = st.n_points, nk = st.n_kf;
-  std::vector<MapPointDev> p(n > 0 ? n : 1);
-  if (n > 0) HIPCHK(hipMemcpy(p.data(), sys->map.pts + (size_t)s * sys->p.max_points, sizeof(MapPointDev) * n, hipMemcpyDeviceToHost));
-  std::vector<Pose> kp(nk > 0 ? nk : 1);
-  if (nk > 0) HIPCHK(hipMemcpy(kp.data(), sys->map.kf_pose + (size_t)s * sys->p.max_keyframes, sizeof(Pose) * nk, hipMemcpyDeviceToHost));
+  std::vector<MapPointDev> p;
+  r = download(sys, sys->map.pts + (size_t)s * sys->p.max_points, n, p); if (r) return r;
+  std::vector<Pose> kp;
+  r = download(sys, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes, nk, kp); if (r) return r;
   char path[4096];
   snprintf(path, sizeof(path), "%s/map.dump", dir);
   FILE* f = fopen(path, "w");
@@ -686,8 +637,8 @@ extern "C" int vslam_get_keyframe_measurements(vslam_system* sys, int s, int k, 
   int r = get_state(sys, s, &st); if (r) return r;
   if (k < 0 || k >= st.n_kf) return VSLAM_E_INVALID;
   const int P = sys->p.max_points;
-  std::vector<MeasDev> km(P);
-  HIPCHK(hipMemcpy(km.data(), sys->map.kf_meas + ((size_t)s * sys->p.max_keyframes + k) * P, sizeof(MeasDev) * P, hipMemcpyDeviceToHost));
+  std::vector<MeasDev> km;
+  r = download(sys, sys->map.kf_meas + ((size_t)s * sys->p.max_keyframes + k) * P, st.n_points, km); if (r) return r;
   int n = 0;
   for (int i = 0; i < st.n_points; i++) {
     if (!km[i].valid) continue;
@@ -702,35 +653,17 @@ extern "C" int vslam_get_keyframe_measurements(vslam_system* sys, int s, int k, 
   return n;
 }
 
-extern "C" int vslam_get_template(vslam_system* sys, int s, int point, uint8_t* tmpl, int* sum, int* sumsq, int* bad) {
-  CHK_STREAM(sys, s);
-  const int P = sys->p.max_points, PS = sys->p.patch_size;
-  if (point < 0 || point >= P) return VSLAM_E_INVALID;
-  TrackData td;
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  HIPCHK(hipMemcpy(&td, sys->map.td + (size_t)s * P + point, sizeof(td), hipMemcpyDeviceToHost));
-  if (tmpl) HIPCHK(hipMemcpy(tmpl, sys->map.tmpl + ((size_t)s * P + point) * TMPL_PITCH, PS * PS, hipMemcpyDeviceToHost));
-  if (sum) *sum = td.tsum;
-  if (sumsq) *sumsq = td.tsumsq;
-  int fl = 0;
-  HIPCHK(hipMemcpy(&fl, sys->map.pt_flags + (size_t)s * P + point, sizeof(int), hipMemcpyDeviceToHost));
-  if (bad) *bad = (fl & TDF_TMPL_BAD) ? 1 : 0;
-  return (fl & TDF_HAVE_LAST) ? 1 : 0;
-}
-
-// the same for the points [first, first + n) at once: tmpl n * P * P bytes, the other arrays n ints (any may be NULL)
+// cached templates of the points [first, first + n): tmpl n * P * P bytes, the other arrays n ints (any may be NULL)
 extern "C" int vslam_get_templates(vslam_system* sys, int s, int first, int n, uint8_t* tmpl, int* sum, int* sumsq, int* bad, int* have) {
   CHK_STREAM(sys, s);
   const int P = sys->p.max_points, PS = sys->p.patch_size;
   if (first < 0 || n < 0 || first + n > P) return VSLAM_E_INVALID;
-  if (n == 0) return VSLAM_OK;
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  std::vector<TrackData> td(n);
-  std::vector<uint8_t> raw((size_t)n * TMPL_PITCH);
-  std::vector<int> fl(n);
-  HIPCHK(hipMemcpy(td.data(), sys->map.td + (size_t)s * P + first, sizeof(TrackData) * n, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(raw.data(), sys->map.tmpl + ((size_t)s * P + first) * TMPL_PITCH, raw.size(), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(fl.data(), sys->map.pt_flags + (size_t)s * P + first, sizeof(int) * n, hipMemcpyDeviceToHost));
+  std::vector<TrackData> td;
+  std::vector<uint8_t> raw;
+  std::vector<int> fl;
+  int r = download(sys, sys->map.td + (size_t)s * P + first, n, td); if (r) return r;
+  r = download(sys, sys->map.tmpl + ((size_t)s * P + first) * TMPL_PITCH, n * TMPL_PITCH, raw); if (r) return r;
+  r = download(sys, sys->map.pt_flags + (size_t)s * P + first, n, fl); if (r) return r;
   for (int i = 0; i < n; i++) {
     if (tmpl) memcpy(tmpl + (size_t)i * PS * PS, raw.data() + (size_t)i * TMPL_PITCH, (size_t)PS * PS);
     if (sum) sum[i] = td[i].tsum;
@@ -739,4 +672,11 @@ extern "C" int vslam_get_templates(vslam_system* sys, int s, int first, int n, u
     if (have) have[i] = (fl[i] & TDF_HAVE_LAST) ? 1 : 0;
   }
   return VSLAM_OK;
+}
+
+// ... of one point; returns its `have` flag
+extern "C" int vslam_get_template(vslam_system* sys, int s, int point, uint8_t* tmpl, int* sum, int* sumsq, int* bad) {
+  int have = 0;
+  const int r = vslam_get_templates(sys, s, point, 1, tmpl, sum, sumsq, bad, &have);
+  return r ? r : have;
 }

@@ -204,8 +204,7 @@ extern "C" int vslam_get_reloc_info(vslam_system* sys, int stream, int out_i[4],
   if (out_d) {
     out_d[0] = ri.best_zmssd; out_d[1] = ri.score;
     for (int i = 0; i < 6; i++) out_d[2 + i] = ri.ln_adj[i];
-    for (int i = 0; i < 9; i++) out_d[8 + i] = ri.best_pose.R[i];
-    for (int i = 0; i < 3; i++) out_d[17 + i] = ri.best_pose.t[i];
+    pose_to12(ri.best_pose, out_d + 8);
     for (int i = 20; i < 24; i++) out_d[i] = 0.0;
   }
   return VSLAM_OK;

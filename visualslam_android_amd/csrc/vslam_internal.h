@@ -21,6 +21,10 @@ void vslam_set_error(const char* fmt, ...);
     }                                                                                        \
   } while (0)
 
+// the C ABI's pose12 (R row-major, then t) <-> Pose
+static inline Pose pose_from12(const double* q) { Pose p; for (int i = 0; i < 9; i++) p.R[i] = q[i]; for (int i = 0; i < 3; i++) p.t[i] = q[9 + i]; return p; }
+static inline void pose_to12(const Pose& p, double* q) { for (int i = 0; i < 9; i++) q[i] = p.R[i]; for (int i = 0; i < 3; i++) q[9 + i] = p.t[i]; }
+
 // Geometry of one pyramid level (same for every stream).
 struct LevelGeom {
   int w, h;        // level size: (W >> l, H >> l)            (jni/KeyFrame.cc:21)
