@@ -3,6 +3,7 @@
 // Usage: system_ptam [n_frames]        a ground-truth map is uploaded, then n_frames are tracked
 //        system_ptam [n_frames] boot   no map: the screen is touched at frames 0 and 12 and the tracker makes its own
 //                                      (trail tracking + MapMaker::InitFromStereo on the device), then keeps tracking
+//        system_ptam [n_frames] reset  as boot, then Tracker::Reset() drops the map and a second one is made from the frames that follow
 // (needs an MI355X; prints the tracker's user message per frame)
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +47,31 @@ int main(int argc, char** argv) {
     KeyFrame k0, k1; std::vector<std::pair<MapMaker::ImageRef, MapMaker::ImageRef>> none; mySE3 T;
     const bool ok = boot.mpMapMaker->InitFromStereo(k0, k1, none, T);   // the map exists: reports it
     printf("InitFromStereo: %s, camera at t = (%.3f %.3f %.3f)\n", ok ? "map made" : "no map", T.t[0], T.t[1], T.t[2]);
+    vslam_feeder_destroy(f);
+    return ok ? 0 : 1;
+  }
+  if (argc > 2 && std::string(argv[2]) == "reset") {              // one slot, two sequences: Tracker::Reset() between them (jni/Tracker.cc:45-70)
+    SystemPTAM sys(W, H, true);
+    cv::Mat bw(H, W, CV_8UC1), rgb(H, W, CV_8UC4);
+    bool ok = true;
+    for (int seq = 0; seq < 2; seq++) {
+      for (int t = 0; t < 13 + n; t++) {
+        double p[12];
+        vslam_feeder_pose(f, t, p);
+        vslam_feeder_render_pose(f, p, 100 + 1000 * seq + t, bw.data, bw.step);
+        if (t == 0 || t == 12) sys.onTouchScreen();
+        sys.update(bw, rgb);
+      }
+      printf("sequence %d: %s\n", seq, sys.mpTracker->GetMessageForUser().c_str());
+      ok = ok && sys.mpMap->IsGood();
+      if (seq == 0) {
+        sys.mpTracker->Reset();
+        int info[4];
+        vslam_get_reset_info(sys.mpMap->sys, 0, info);
+        printf("Reset: dropped %d keyframes and %d points at frame %d; map good: %d\n", info[2], info[3], info[1], (int)sys.mpMap->IsGood());
+        ok = ok && !sys.mpMap->IsGood();
+      }
+    }
     vslam_feeder_destroy(f);
     return ok ? 0 : 1;
   }

@@ -105,8 +105,8 @@ class MapMaker {
  public:
   MapMaker(Map& m, const ATANCamera& cam) : mMap(m), mCamera(cam) {}
   void AddKeyFrame(KeyFrame&) { vslam_detail::check(vslam_add_keyframe(mMap.sys, 0)); }              // :470-478
-  void RequestReset() {}
-  bool ResetDone() { return true; }                                                                    // no spin (survey fact #4)
+  void RequestReset() { if (mMap.sys) vslam_detail::check(vslam_reset_streams(mMap.sys, nullptr, 0)); }   // :127-131 -> Reset :60-74, Map::Reset
+  bool ResetDone() { return true; }                                                                    // :133-136: the reset is ordered on the system's stream, nothing to spin for
   int QueueSize() { return 0; }
   bool NeedNewKeyFrame(KeyFrame&) { int v = 0; vslam_detail::check(vslam_need_new_keyframe(mMap.sys, 0, &v)); return v != 0; }              // :761-773 (the tracker's current frame)
   bool IsDistanceToNearestKeyFrameExcessive(KeyFrame&) { int v = 0; vslam_detail::check(vslam_distance_to_nearest_keyframe_excessive(mMap.sys, 0, &v)); return v != 0; }   // :1098-1101
@@ -184,6 +184,7 @@ class Tracker {
   }
   // jni/Tracker.cc:76-146.  imageColor is only drawn on in the reference; it is ignored here.
   void TrackFrame(cv::Mat& imFrame, cv::Mat& /*imageColor*/, bool /*bDraw*/) {
+    if (mbUserPressedReset) Reset();                                                                     // the GUI's "Reset" (jni/Tracker.h:139), taken up by the next frame
     if (mbUserPressedSpacebar) { mbUserPressedSpacebar = false; vslam_touch(mMap.sys); }
     vslam_detail::check(vslam_update(mMap.sys, imFrame.data, imFrame.step, 0));
   }
@@ -193,7 +194,11 @@ class Tracker {
     return T;
   }
   std::string GetMessageForUser() { char b[512]; vslam_detail::check(vslam_get_message(mMap.sys, 0, b, sizeof(b))); return b; }   // :880-883
-  void Reset() {}                                                                                        // no map-maker spin
+  void Reset() {                                                                                         // :45-70; the tracker's members are reset on the device with the map
+    mbUserPressedReset = false; mbUserPressedSpacebar = false;
+    mMapMaker.RequestReset();
+    while (!mMapMaker.ResetDone()) {}
+  }
   bool mbUserPressedSpacebar = false, mbUserPressedReset = false;                                        // jni/Tracker.h:138-139
  protected:
   KeyFrame mCurrentKF;

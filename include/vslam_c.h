@@ -218,6 +218,24 @@ int vslam_set_velocity(vslam_system* sys, int stream, const double v6[6]);
  * the tracker asks for the next one more than min_frames_between_kf frames later (jni/Tracker.cc:128) */
 int vslam_set_last_keyframe_dropped(vslam_system* sys, int stream, int frame);
 
+/* Tracker::Reset (jni/Tracker.cc:45-70) with MapMaker::RequestReset / Reset (jni/MapMaker.cc:60-74, 127-136) and Map::Reset (jni/Map.cc:8-14)
+ * for n streams of a live batch (streams == NULL: every stream): the map is dropped and the tracker returns to its constructed state --
+ * quality GOOD, frame 0, no velocity, scene depth 1 / 1, mnLastKeyFrameDropped -20, mnInitialStage TRAIL_TRACKING_NOT_STARTED, no trails,
+ * no pending spacebar, mbBundleConverged_Full / _Recent true, empty failure and new queues, every per-stream counter zero, the boot seed 1.
+ * Afterwards each of these streams is a stream of a newly created system: every read-back, and every frame tracked after a new map has
+ * been uploaded (vslam_map_add_*) or bootstrapped, gives the bits a new system gives; with use_sbi its next frame makes both
+ * SmallBlurryImages from itself (jni/Tracker.cc:90-92).  An adjustment of the asynchronous map-maker that is pending for the stream is
+ * abandoned (mbBundleAbortRequested, CHECK_RESET jni/MapMaker.cc:76-78): its result never reaches the map.  The other streams are not
+ * touched.  Between frames only: VSLAM_E_STATE while a stage-wise frame is open; VSLAM_E_INVALID for an index outside the batch, and then
+ * no stream is reset.  Ordered on the system's stream, asynchronous (MapMaker::ResetDone, jni/MapMaker.cc:133-136, has nothing to wait for). */
+int vslam_reset_streams(vslam_system* sys, const int* streams, int n);
+/* out[0..3] = Reset calls the stream has seen, mnFrame (jni/Tracker.h:116) at the last one, and the keyframes and map points
+ * (jni/Map.h:29-30) that call dropped. */
+int vslam_get_reset_info(vslam_system* sys, int stream, int out[4]);
+/* HIP-event milliseconds of the last vslam_reset_streams on the system's stream: the flag copy, the wait for the map-maker streams
+ * (asynchronous map-maker) and the reset kernels.  Synchronises.  VSLAM_E_STATE before the first call. */
+int vslam_get_reset_timing(vslam_system* sys, double* ms);
+
 /* ---- tracking ------------------------------------------------------------------------------ */
 
 typedef struct vslam_track_state {

@@ -88,6 +88,9 @@ SYMBOLS = {
     "vslam_set_pose": (_i, [_sys, _i, _vp]),
     "vslam_set_velocity": (_i, [_sys, _i, _vp]),
     "vslam_set_last_keyframe_dropped": (_i, [_sys, _i, _i]),
+    "vslam_reset_streams": (_i, [_sys, _vp, _i]),
+    "vslam_get_reset_info": (_i, [_sys, _i, _vp]),
+    "vslam_get_reset_timing": (_i, [_sys, C.POINTER(_d)]),
     "vslam_track_frame": (_i, [_sys, _vp, _sz, _sz, _i]),
     "vslam_update": (_i, [_sys, _vp, _sz, _sz]),
     "vslam_patch_search": (_i, [_sys, _i]),
@@ -366,6 +369,25 @@ class System:
 
     def set_last_keyframe_dropped(self, stream, frame):
         _check(self.lib.vslam_set_last_keyframe_dropped(self.h, stream, int(frame)))
+
+    def reset(self, streams=None):
+        """Tracker::Reset for the given streams (None: all): each is then a stream of a new system (vslam_reset_streams)"""
+        if streams is None:
+            _check(self.lib.vslam_reset_streams(self.h, None, 0))
+        else:
+            a = np.ascontiguousarray(np.atleast_1d(streams), np.int32)
+            _check(self.lib.vslam_reset_streams(self.h, a.ctypes.data, len(a)))
+
+    def reset_info(self, stream):
+        o = np.zeros(4, np.int32)
+        _check(self.lib.vslam_get_reset_info(self.h, stream, o.ctypes.data))
+        return dict(zip(("resets", "frame", "keyframes", "points"), (int(x) for x in o)))
+
+    def reset_timing(self):
+        """-> HIP-event ms of the last reset on the system's stream (vslam_get_reset_timing)"""
+        ms = C.c_double(0.0)
+        _check(self.lib.vslam_get_reset_timing(self.h, C.byref(ms)))
+        return ms.value
 
     # ---- tracking ----------------------------------------------------------------------------
     def track_frame(self, gray):

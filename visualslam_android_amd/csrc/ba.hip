@@ -828,6 +828,37 @@ int ba_sync_streams(vslam_system* sys) {
   return VSLAM_OK;
 }
 
+// vslam_reset_streams, the map-maker's side: mbBundleAbortRequested + CHECK_RESET (jni/MapMaker.cc:76-78, 127-131).  The pool record of
+// every flagged stream becomes a new system's (all zero: no problem wanted, assembled or solved, the sizes vslam_get_bundle_stats
+// reports), and the stream leaves the work list of the batch that is still open, so the launch of that batch finds nothing of it --
+// a keyframe of the stream's next sequence may enter the same list, and a problem is solved by one workgroup.
+__global__ void k_ba_reset(BaPool pool, const unsigned char* flags, int open_slot) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < pool.N && flags[s]) { const BaResult z = {}; pool.res[s] = z; }
+  if (open_slot < 0 || blockIdx.x != 0 || threadIdx.x != 0) return;
+  int* list = pool.work + (size_t)open_slot * pool.N;
+  const int n = pool.work_n[open_slot];
+  int kept = 0;
+  for (int i = 0; i < n; i++) { const int e = list[i]; if (!flags[e]) list[kept++] = e; }
+  pool.work_n[open_slot] = kept;
+}
+
+// Asynchronous map-maker: everything the map-maker streams hold -- assemblies of the open batch, launches of the earlier ones -- is
+// ordered before the reset by events (the tracker's stream waits on the device, the host does not), so no k_ba_assemble or
+// k_ba_compute reads a pool record or a map while the reset kernels rewrite them.  The caller orders the map-maker streams behind
+// the reset in turn (sys->ev_reset).
+int ba_reset_streams(vslam_system* sys, const unsigned char* d_flags) {
+  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  for (size_t i = 0; i < sys->ba_streams.size(); i++) {
+    HIPCHK(hipEventRecord(sys->ev_reset_ba[i], sys->ba_streams[i]));
+    HIPCHK(hipStreamWaitEvent(sys->stream, sys->ev_reset_ba[i], 0));
+  }
+  const int open_slot = sys->tp.ba_delay > 0 && sys->ba_batch_fill > 0 ? (int)(sys->ba_batch_id % (long)sys->ev_ba.size()) : -1;
+  hipLaunchKernelGGL(k_ba_reset, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, ws->pool, d_flags, open_slot);
+  HIPCHK(hipGetLastError());
+  return VSLAM_OK;
+}
+
 // explicit (host-driven) map-maker calls first collect a bundle adjustment that is still in flight
 static int ba_drain(vslam_system* sys) {
   if (sys->tp.ba_delay <= 0) return VSLAM_OK;

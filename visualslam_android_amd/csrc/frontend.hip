@@ -859,6 +859,7 @@ int fe_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_str
   if (sys->p.use_sbi) {                                           // jni/Tracker.cc:86-97, 104-105
     int r = fe_sbi(sys, sys->have_sbi ? sys->frbuf[b ^ 1] : sys->fr);
     if (r) return r;
+    if (sys->sbi_restart_pending) { r = fe_sbi_restart(sys); if (r) return r; sys->sbi_restart_pending = false; }   // streams reset since the last frame
     sys->have_sbi = true;
   }
   prof_mark(sys, PROF_FE_END);

@@ -182,12 +182,7 @@ extern "C" int vslam_map_set_good(vslam_system* sys, int s) {
 }
 
 static void reset_tracker_fields(TrackerState& st) {   // Tracker::Reset, jni/Tracker.cc:45-62 (first call for a stream)
-  if (st.frame == 0 && st.last_kf_dropped == 0 && st.depth_mean == 0.0) {
-    st.boot_seed = 1u;
-    st.quality = 2; st.last_kf_dropped = -20; st.depth_mean = 1.0; st.depth_sigma = 1.0; st.ba_accepted = -2; st.ba_countdown = -1;
-    for (int i = 0; i < 9; i++) st.pose_final.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    st.pose_cur = st.pose_final; st.start_pose = st.pose_final;
-  }
+  if (st.frame == 0 && st.last_kf_dropped == 0 && st.depth_mean == 0.0) tracker_reset_fields(st);
 }
 
 extern "C" int vslam_set_pose(vslam_system* sys, int s, const double pose12[12]) {
@@ -229,7 +224,7 @@ extern "C" int vslam_set_last_keyframe_dropped(vslam_system* sys, int s, int fra
 int map_init_states(vslam_system* sys) {
   std::vector<TrackerState> v(sys->S);
   memset(v.data(), 0, sizeof(TrackerState) * sys->S);
-  for (auto& st : v) reset_tracker_fields(st);
+  for (auto& st : v) tracker_reset_fields(st);
   HIPCHK(hipMemcpy(sys->map.st, v.data(), sizeof(TrackerState) * sys->S, hipMemcpyHostToDevice));
   return VSLAM_OK;
 }

@@ -19,10 +19,13 @@ struct SbiArgs {
 };
 
 // The stages themselves are the device functions of sbi_dev.h, which the relocaliser (reloc.hip) runs on other images.
-__global__ __launch_bounds__(SBI_THREADS) void k_sbi(SbiArgs a) {
+// RESTART: only the streams flagged in `restart` (vslam_reset_streams), which then lose their flag.
+template <bool RESTART>
+DEVFN void sbi_frame(const SbiArgs& a, unsigned char* restart) {
   extern __shared__ double sbi_dyn[];
   __shared__ SbiShared sh;
   const int s = blockIdx.x, tid = threadIdx.x;
+  if (RESTART && !restart[s]) return;
   const int W = a.w3 / 2, H = a.h3 / 2, N = W * H;
   float* t0 = (float*)sbi_dyn;           // zero-mean small image, later the warped template
   float* t1 = t0 + N;                    // row pass, later this frame's template
@@ -43,21 +46,40 @@ __global__ __launch_bounds__(SBI_THREADS) void k_sbi(SbiArgs a) {
   double* rot = a.rot + (size_t)s * 8;
   for (int i = 0; i < 6; i++) rot[i] = out6[i];
   rot[6] = final_score; rot[7] = 0.0;
+  if (RESTART) restart[s] = 0;
 }
+__global__ __launch_bounds__(SBI_THREADS) void k_sbi(SbiArgs a) { sbi_frame<false>(a, nullptr); }
+// A stream vslam_reset_streams has reset starts a new video: its next frame is a first frame, both SmallBlurryImages made from it
+// (jni/Tracker.cc:90-92).  Launched behind k_sbi in that one frame only, for those streams only.
+__global__ __launch_bounds__(SBI_THREADS) void k_sbi_restart(SbiArgs a, unsigned char* restart) { sbi_frame<true>(a, restart); }
 
-int fe_sbi(vslam_system* sys, const FrameDev& last) {
+static int sbi_args(vslam_system* sys, const FrameDev& last, SbiArgs& a, size_t& lds) {
   const LevelGeom& g3 = sys->geom[3];
   const int W = g3.w / 2, H = g3.h / 2;
   if (W * H > SBI_MAX_PIX || H > SBI_THREADS) { vslam_set_error("use_sbi: small image %d x %d exceeds %d pixels", W, H, SBI_MAX_PIX); return VSLAM_E_INVALID; }
-  SbiArgs a;
   a.l3 = sys->fr.img[3]; a.l3_sstride = sys->fr.img_sstride[3]; a.l3_pitch = sys->fr.img_pitch[3]; a.w3 = g3.w; a.h3 = g3.h;
   a.small = sys->fr.sbi_small; a.tmpl = sys->fr.sbi_tmpl; a.jacs = sys->fr.sbi_jacs; a.rot = sys->fr.sbi_rot;
   a.last_tmpl = last.sbi_tmpl; a.last_jacs = last.sbi_jacs;
   sbi_blur_fill(a.blur, 0.75);                                       // gvdSBIBlur, jni/Tracker.cc:87
   cam_fill(a.cam, sys->p.cam, W, H, sys->p.quirks);
-  const size_t lds = sbi_lds_bytes(W * H);
+  lds = sbi_lds_bytes(W * H);
+  return VSLAM_OK;
+}
+
+int fe_sbi(vslam_system* sys, const FrameDev& last) {
+  SbiArgs a; size_t lds;
+  int r = sbi_args(sys, last, a, lds); if (r) return r;
   if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_sbi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_sbi, dim3(sys->S), dim3(SBI_THREADS), lds, sys->fe_stream, a);
+  HIPCHK(hipGetLastError());
+  return VSLAM_OK;
+}
+
+int fe_sbi_restart(vslam_system* sys) {
+  SbiArgs a; size_t lds;
+  int r = sbi_args(sys, sys->fr, a, lds); if (r) return r;
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_sbi_restart, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_sbi_restart, dim3(sys->S), dim3(SBI_THREADS), lds, sys->fe_stream, a, sys->sbi_restart);
   HIPCHK(hipGetLastError());
   return VSLAM_OK;
 }

@@ -164,6 +164,7 @@ extern "C" int vslam_create(const vslam_params* p, vslam_system** out) {
     if (!r) r = grow_alloc(sys);
     if (!r) r = boot_alloc(sys);
     if (!r) r = reloc_alloc(sys);
+    if (!r) r = reset_alloc(sys);
     if (!r && hipStreamSynchronize(sys->stream) != hipSuccess) r = VSLAM_E_HIP;
     if (!r) r = map_init_states(sys);
     if (r) { vslam_destroy(sys); return r; }
@@ -182,6 +183,7 @@ extern "C" int vslam_destroy(vslam_system* sys) {
   for (hipEvent_t e : sys->ev_ba) (void)hipEventDestroy(e);
   for (hipStream_t st : sys->ba_streams) (void)hipStreamDestroy(st);
   for (void* p : sys->allocs) (void)hipFree(p);
+  reset_free(sys);
   for (hipEvent_t e : sys->prof_ev) (void)hipEventDestroy(e);
   for (int k = 0; k < 4; k++) if (sys->ev_mm[k]) (void)hipEventDestroy(sys->ev_mm[k]);
   for (int b = 0; b < 2; b++) { if (sys->ev_fe_done[b]) (void)hipEventDestroy(sys->ev_fe_done[b]); if (sys->ev_track_done[b]) (void)hipEventDestroy(sys->ev_track_done[b]); }

@@ -121,6 +121,18 @@ struct TrackerState {       // Tracker members, jni/Tracker.h:77-150 (+ MapMaker
   int boot_host_matches;    // vslam_init_from_stereo: the trails are the caller's matches; this frame's TrailTracking_Advance does not search
   int recovered_now;        // vslam_params.relocalise: AttemptRecovery succeeded in this frame (jni/Tracker.cc:133-139), cleared at the frame's end
 };
+// Tracker::Reset (jni/Tracker.cc:45-62) and MapMaker::Reset (jni/MapMaker.cc:60-74) on a zeroed TrackerState: the members that do not
+// start at zero.  The only statement of them: a new system's streams (map_init_states) and a reset stream (k_reset_state) both hold
+// tracker_reset_state().
+HDFN void tracker_reset_fields(TrackerState& st) {
+  st.boot_seed = 1u;
+  st.quality = 2; st.last_kf_dropped = -20; st.depth_mean = 1.0; st.depth_sigma = 1.0;       // jni/Tracker.cc:50-60
+  st.ba_accepted = -2; st.ba_countdown = -1;
+  st.ba_converged_recent = 1; st.ba_converged_full = 1;                                     // jni/MapMaker.cc:72-73
+  for (int i = 0; i < 9; i++) st.pose_final.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  st.pose_cur = st.pose_final; st.start_pose = st.pose_final;
+}
+HDFN TrackerState tracker_reset_state() { TrackerState st = {}; tracker_reset_fields(st); return st; }
 // jni/Tracker.cc:103-104 and :135-136: TrackMap runs for a stream that is not lost, or that the relocaliser has just recovered
 DEVFN bool trk_runs_track_map(const TrackerState* st) { return st->map_good && (st->lost_frames < 3 || st->recovered_now); }
 
@@ -225,6 +237,17 @@ struct vslam_system {
   bool have_sbi;            // a SmallBlurryImage of a previous frame exists (mpSBILastFrame)
   // KeyFrame::Level::vCandidates of the current frame (jni/KeyFrame.h:62-70), filled by vslam_make_keyframe_rest
   uint32_t* cand[NLEV]; double* cand_score[NLEV]; int* ncand; bool have_candidates;
+  // vslam_reset_streams (reset.hip)
+  unsigned char* reset_flags = nullptr;      // [S] device: the streams the reset kernels of the call in flight work on
+  unsigned char* reset_stage[4] = {nullptr, nullptr, nullptr, nullptr};   // pinned host copies of the flags, a ring: a call never waits for the one before it
+  hipEvent_t ev_reset_stage[4] = {nullptr, nullptr, nullptr, nullptr};    // ... the copy out of a ring entry has finished
+  long reset_calls = 0;
+  int* reset_info = nullptr;                 // [S][4] device: vslam_get_reset_info
+  unsigned char* sbi_restart = nullptr;      // [S] device (use_sbi): the stream's next frame is its first, "last frame" = itself (jni/Tracker.cc:90-92)
+  bool sbi_restart_pending = false;          // some flag of sbi_restart is set: the next frame launches k_sbi_restart once
+  hipEvent_t ev_reset_t[2] = {nullptr, nullptr};   // around the last call's work on the system's stream (vslam_get_reset_timing)
+  hipEvent_t ev_reset = nullptr;             // the reset kernels are done (the front-end and map-maker streams wait for it)
+  std::vector<hipEvent_t> ev_reset_ba;       // one per map-maker stream: what it held when the reset was called
   bool boot_key_pressed = false;   // vslam_press_spacebar since the last frame: that frame launches the start / InitFromStereo pipelines
   TrackParams tp;
   MapDev map;
@@ -276,6 +299,7 @@ int grow_levels(vslam_system* sys, const int* order, int n);              // Thi
 int ba_launch_add_keyframe(vslam_system* sys);                            // k_add_keyframe for the streams with kf_pending
 int mm_idle_job(vslam_system* sys, int job);                               // vslam_params.idle_iterations passes through MapMaker::run's idle jobs
 int fe_sbi(vslam_system* sys, const FrameDev& last);   // k_sbi on the front-end stream: this frame's SBI + rotation prior against `last`
+int fe_sbi_restart(vslam_system* sys);                 // ... again against the frame itself for the streams vslam_reset_streams flagged (once, then the flags are clear)
 void cam_fill(CamModel& c, const double cam5[5], double width, double height, int quirks);
 int fe_make_keyframe_rest(vslam_system* sys, double min_score);
 int fe_thin_candidates(vslam_system* sys, int keyframe);
@@ -296,6 +320,10 @@ int reloc_alloc(vslam_system* sys);
 int reloc_keyframe_sbi_pending(vslam_system* sys);                        // SmallBlurryImage of the keyframe k_add_keyframe has just stored (streams with kf_pending)
 int reloc_keyframe_sbi(vslam_system* sys, int s, int first, int n);       // ... of the uploaded keyframes [first, first + n) of stream s
 int reloc_attempt_recovery(vslam_system* sys);
+int ba_reset_streams(vslam_system* sys, const unsigned char* d_flags);   // the pool records (and work-list entries) of the flagged streams, as a new system's
 // map.hip
 int map_init_states(vslam_system* sys);
+// reset.hip
+int reset_alloc(vslam_system* sys);
+void reset_free(vslam_system* sys);
 
