@@ -44,7 +44,7 @@ typedef struct vslam_system vslam_system;
 
 /* Every tunable the reference hard-codes on the hot path. */
 typedef struct vslam_params {
-  int width, height;               /* jni/jni_part.cpp:41 (800x480 there) */
+  int width, height;               /* jni/jni_part.cpp:41 (800x480 there); 48..4096 each, any value, odd ones included */
   int n_streams;                   /* independent sequences batched on this GPU */
   int fast_threshold[VSLAM_LEVELS];/* jni/KeyFrame.cc:32-39: 10,15,15,10 */
   int nonmax_barrier;              /* jni/KeyFrame.cc:63: 10 */
@@ -127,7 +127,9 @@ int vslam_eval_transcendental(int fn, int n, const double* x, double* y, int on_
  * gray: n_streams images, image s at gray + s*stream_stride, rows row_stride bytes apart;
  * on_device != 0 means gray is device memory (borrowed until the next front-end call; with vslam_params.bootstrap until the
  * frame AFTER the next has been enqueued and this one's work has finished: the trail tracker reads the previous frame's level 0
- * in place, jni/Tracker.cc:294-346).  Asynchronous on the system's stream. */
+ * in place, jni/Tracker.cc:294-346).  Asynchronous on the system's stream.
+ * Any size vslam_create accepts and any alignment of gray, row_stride and stream_stride give the same bits; a width that is a multiple
+ * of 32 (and at least 128, with a height of at least 56) read from 16-B aligned memory takes the faster of the two forms of the kernels. */
 int vslam_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_stride,
                              size_t stream_stride, int on_device);
 

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from helpers import make_scene
+from oracle import binding as orc
 from visualslam_android_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -46,6 +47,24 @@ def assert_same_map(ga, gb, grow, tag):
     return sa
 
 
+KCAP_MAX = (16384, 8192, 4096, 2048)                               # a keyframe's stored corner list per level (vslam_c.h, vslam_get_keyframe_corners)
+
+
+def assert_keyframe_corners_equal_oracle(g, m, vp, tag):
+    """Level::vCorners of every uploaded keyframe (the band form of the front end on the stored image) == the oracle's FAST corners of that
+    image, cut in raster order at the keyframe capacity as k_store_kf_corners cuts them"""
+    thr = tuple(vp.fast_threshold[l] for l in range(4))
+    total = 0
+    for k, kf in enumerate(m["keyframes"]):
+        want = orc.make_keyframe_lite(np.ascontiguousarray(kf["image"], np.uint8), thr)
+        for l in range(4):
+            kcap = min(vp.max_corners[l], KCAP_MAX[l])
+            corners = want[l][1][:kcap]
+            assert np.array_equal(g.keyframe_corners(0, k, l), corners), (tag, k, l)
+            total += len(corners)
+    assert total > 100 * len(m["keyframes"]), (tag, total)
+
+
 @pytest.mark.parametrize("grow", [0, 3])
 def test_per_item_upload_equals_bulk_upload(grow):
     f, m, frames = make_scene(W, H, seed=5, n_frames=N_FRAMES, per_level=(120, 50, 20, 8))
@@ -54,6 +73,8 @@ def test_per_item_upload_equals_bulk_upload(grow):
     ga.load_map(0, m)
     upload_per_item(gb, 0, m)
     st = assert_same_map(ga, gb, grow, "uploaded")
+    if grow:
+        assert_keyframe_corners_equal_oracle(ga, m, vp, "uploaded")
     assert st.n_keyframes == len(m["keyframes"]) and st.n_points == len(m["packed"]["pos"]) > 100
     assert sum(len(ga.keyframe_meas(0, k)["pt"]) for k in range(st.n_keyframes)) == len(m["packed"]["m_kf"])
     for g in (ga, gb):

@@ -806,18 +806,31 @@ static void fe_launch_slide(vslam_system* sys, FeArgs& a, hipStream_t fs, int S)
 
 // The band form, k_pyr_fast0 then k_fast_lvl for S streams: the only statement of their dynamic LDS sizes, which follow the tile of
 // k_pyr_fast0 / k_fast_lvl and the layout of fast_band.  marks: the per-frame path's profile marks 0 and 1 (a keyframe upload records none).
-static void fe_launch_bands(vslam_system* sys, FeArgs& a, hipStream_t stream, int S, bool marks) {
+// A band is staged at its full width, about 37 B per padded level-0 pixel of width: 64 KiB, the most a kernel gets without asking, is passed
+// a little above 1,760 pixels (k_fast_lvl: level-1 widths from 2,033), so wider bands raise the kernel's limit first; 4096 pixels, the widest
+// vslam_create accepts, take 151,584 B of the CU's 160 KiB.
+#define FE_LDS_MAX (160 * 1024)
+static int fe_band_lds(const void* kernel, size_t lds) {
+  if (lds > FE_LDS_MAX) { vslam_set_error("front end: a band of %zu B does not fit the %d B of LDS", lds, FE_LDS_MAX); return VSLAM_E_INVALID; }
+  if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return VSLAM_OK;
+}
+static int fe_launch_bands(vslam_system* sys, FeArgs& a, hipStream_t stream, int S, bool marks) {
   const LevelGeom* g = sys->geom;
   const int lp0 = (g[0].w + 15) & ~15, lp1 = (g[1].w + 15) & ~15, lp2 = (g[2].w + 15) & ~15;
   const size_t lds0 = (size_t)(BAND + 2 * HALO) * lp0 + (BAND / 2) * lp1 + (BAND / 4) * lp2 + 16 + (size_t)BAND * g[0].nchunk * 8 + (size_t)FB_ROWS * lp0 * 2 + 16;
+  const size_t lds1 = (size_t)(BAND + 2 * HALO) * lp1 + 16 + (size_t)BAND * g[1].nchunk * 8 + (size_t)FB_ROWS * lp1 * 2 + 16;
+  int r = fe_band_lds((const void*)k_pyr_fast0, lds0);
+  if (!r) r = fe_band_lds((const void*)k_fast_lvl, lds1);
+  if (r) return r;
   if (marks) prof_mark(sys, 0);
   hipLaunchKernelGGL(k_pyr_fast0, dim3((g[0].h + BAND - 1) / BAND, S), dim3(FE_THREADS), lds0, stream, a, lp0, lp1, lp2);
   int nb = 0;
   a.band_first[0] = 0;
   for (int l = 1; l < NLEV; l++) { a.band_first[l] = nb; nb += (g[l].h + BAND - 1) / BAND; }
-  const size_t lds1 = (size_t)(BAND + 2 * HALO) * lp1 + 16 + (size_t)BAND * g[1].nchunk * 8 + (size_t)FB_ROWS * lp1 * 2 + 16;
   if (marks) prof_mark(sys, 1);
   hipLaunchKernelGGL(k_fast_lvl, dim3(nb, S), dim3(FE_THREADS), lds1, stream, a);
+  return VSLAM_OK;
 }
 
 int fe_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_stride, size_t stream_stride,
@@ -850,7 +863,7 @@ int fe_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_str
   sys->frbuf[b] = sys->fr;
 
   if (fe_slide_ok(sys, a)) fe_launch_slide(sys, a, fs, sys->S);
-  else fe_launch_bands(sys, a, fs, sys->S, true);
+  else { const int r = fe_launch_bands(sys, a, fs, sys->S, true); if (r) return r; }
   prof_mark(sys, 2);
   {
     static const int cb = getenv("VSLAM_COMPACT_BAND") ? atoi(getenv("VSLAM_COMPACT_BAND")) : 32;   // rows of a level per workgroup of the compaction (measured alone, 1024 frames: 16 rows 96 us, 32: 62, 64: 96, 128: 78, 256: 156)
@@ -970,7 +983,7 @@ int fe_keyframe_corners(vslam_system* sys, int s, int kf) {
   }
   a.ncorners = scr.ncorners; a.overflow = scr.overflow;
   a.in = a.lvl[0]; a.in_sstride = 0; a.in_pitch = g[0].pitch;
-  fe_launch_bands(sys, a, sys->stream, 1, false);
+  { const int r = fe_launch_bands(sys, a, sys->stream, 1, false); if (r) return r; }
   hipLaunchKernelGGL(k_compact, dim3((g[0].h + BAND - 1) / BAND, NLEV, 1), dim3(COMPACT_THREADS), 0, sys->stream, a, BAND);
   uint32_t* d[NLEV];
   for (int l = 0; l < NLEV; l++) d[l] = sys->map.kf_corners[l] + ((size_t)s * K + kf) * sys->tp.kcap[l];
