@@ -344,6 +344,45 @@ int vslam_set_boot_seed(vslam_system* sys, int stream, unsigned seed);
 int vslam_get_init_info(vslam_system* sys, int stream, int out[6]);
 /* the trails (jni/Tracker.h Trail): irInitialPos x, y, irCurrentPos x, y per trail, in list order */
 int vslam_get_trails(vslam_system* sys, int stream, int* out4, int cap, int* n);
+/* ---- the two mathematical stages of the bootstrap on their own: test and diagnosis entry points ----
+ * Both run the device functions InitFromStereo runs (csrc/boot.hip: boot_homography_stage, boot_plane_stage) in the work slices of one
+ * stream and write a record; no tracker, keyframe or map field is read or written.  Systems created with bootstrap = 1; VSLAM_E_STATE while
+ * the stream has an initialisation in progress (its trails are running) or a stage-wise frame is open.  Synchronous.  What a stage does not
+ * reach stays zero in the record (best_trial: -1). */
+#define VSLAM_PROBE_MAX_MATCHES 1000   /* MaxInitialTrails, jni/Tracker.cc:305 */
+typedef struct vslam_homography_probe {
+  int ok;                  /* HomographyInit::Compute succeeded and the translation has a length (InitFromStereo goes on) */
+  int n;                   /* matches given */
+  int best_trial;          /* first minimum of scores[] in trial order; -1 with fewer than ten matches (one direct fit, no trials) */
+  int n_inliers;
+  int choice;              /* ChooseBestDecomposition: 0 the visibility votes left no ambiguity, 1 / 2 the first / second of the ambiguous pair */
+  int reserved;
+  double scores[300];      /* the MLESAC score of every trial */
+  double H_mlesac[9];      /* the best trial's homography (row-major; sign and scale are free) */
+  double H_refined[9];     /* after the five refinements over the inliers */
+  double R[9], t[3], normal[3], d;   /* the chosen decomposition */
+  double t_scaled[3];      /* t at the length vslam_params.wiggle_scale: the second camera's translation */
+  int inliers[VSLAM_PROBE_MAX_MATCHES];        /* indices of the inliers of H_mlesac, in match order (n_inliers of them) */
+  double matches[VSLAM_PROBE_MAX_MATCHES * 8]; /* the HomographyMatch array the stage worked on: first xy, second xy, 2x2 pixel Jacobian at the second */
+} vslam_homography_probe;
+/* HomographyInit::Compute(vMatches, max_pixel_error, se3) and the scale of InitFromStereo (jni/MapMaker.cc:233-250) with `seed` in the place of the
+ * stream's boot seed.  The n <= VSLAM_PROBE_MAX_MATCHES matches are given either as level-0 pixel pairs (matches_xyxy, 4 ints each: they go through
+ * the kernel's own UnProject / GetProjectionDerivs as in InitFromStereo) or as ready HomographyMatch records (m8, 8 doubles each, laid out as
+ * vslam_homography_probe.matches); the other pointer is NULL. */
+int vslam_probe_homography_init(vslam_system* sys, int stream, int n, const int* matches_xyxy, const double* m8, unsigned seed, double max_pixel_error,
+                                vslam_homography_probe* out);
+typedef struct vslam_plane_probe {
+  int have;                /* an aligner was made (ten points or more, and the best plane has an inlier) */
+  int n;
+  int best_trial;          /* first minimum among the trials that were not skipped; -1: none, mean / normal hold the defaults 0 / (0, 0, 1) */
+  int reserved;
+  double sums[100];        /* the summed truncated distance of every RANSAC trial; negative: the three points were collinear, trial skipped */
+  double mean[3], normal[3];   /* of the best trial */
+  double R[9], t[3];       /* the aligner (new-from-old), R row-major */
+} vslam_plane_probe;
+/* MapMaker::CalcPlaneAligner (jni/MapMaker.cc:1104-1231) over n <= max_points positions (3 doubles each).  seed is the RANSAC's own: InitFromStereo
+ * runs it with the stream's boot seed + 1. */
+int vslam_probe_plane_aligner(vslam_system* sys, int stream, int n, const double* pos3, unsigned seed, vslam_plane_probe* out);
 /* Reads the directory vslam_save_map wrote (MapMaker "SaveMap", jni/MapMaker.cc:1254-1286: map.dump, keyframes/<i>.info) back: point
  * positions + source levels, keyframe poses as R (9, row-major) then t (3).  Arrays may be null to count only. */
 /* Writes the state such a dump holds (positions of the good points, keyframe poses; 6 significant digits) back into the map it was

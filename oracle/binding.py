@@ -513,3 +513,150 @@ def calc_plane_aligner(pos, seed=1):
     L.orc_calc_plane_aligner.restype = C.c_int
     ok = L.orc_calc_plane_aligner(_p(p), C.c_int(len(p)), C.c_uint(seed), _p(out))
     return bool(ok), out
+
+
+def boot_matches(cam5, w, h, matches_xyxy):
+    """The (n, 8) HomographyMatch array System::InitFromStereo makes of integer level-0 pixel pairs (x, y first, x, y second)."""
+    m = np.ascontiguousarray(matches_xyxy, np.int32).reshape(-1, 4)
+    out = np.zeros((len(m), 8))
+    L = lib(); L.orc_boot_matches.restype = None
+    L.orc_boot_matches(_p(_d(cam5)), C.c_int(w), C.c_int(h), _p(m), C.c_int(len(m)), _p(out))
+    return out
+
+
+def homography_init_stages(matches8, max_pixel_error=5.0, seed=1):
+    """homography_init with what Compute held on the way: dict(ok, pose, inliers (indices), H_mlesac, H_refined, choice)."""
+    L = lib()
+    m = np.ascontiguousarray(matches8, np.float64).reshape(-1, 8)
+    out = np.zeros(12); ninl = C.c_int(0); hm = np.zeros(9); hr = np.zeros(9); inl = np.zeros(max(len(m), 1), np.int32); choice = C.c_int(0)
+    L.orc_homography_init_stages.restype = C.c_int
+    ok = L.orc_homography_init_stages(_p(m), C.c_int(len(m)), C.c_double(max_pixel_error), C.c_uint(seed), _p(out), C.byref(ninl), _p(hm), _p(inl), _p(hr), C.byref(choice))
+    return {"ok": bool(ok), "pose": out, "inliers": inl[:ninl.value].copy(), "H_mlesac": hm, "H_refined": hr, "choice": choice.value}
+
+
+def calc_plane_aligner_stages(pos, seed=1):
+    """calc_plane_aligner with the RANSAC's best plane: dict(ok, aligner, mean, normal)."""
+    L = lib()
+    p = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+    out = np.zeros(12); mean = np.zeros(3); nrm = np.zeros(3)
+    L.orc_calc_plane_aligner_stages.restype = C.c_int
+    ok = L.orc_calc_plane_aligner_stages(_p(p), C.c_int(len(p)), C.c_uint(seed), _p(out), _p(mean), _p(nrm))
+    return {"ok": bool(ok), "aligner": out, "mean": mean, "normal": nrm}
+
+
+# ---- the product's csrc/bootstrap_math.h compiled for the host (oracle/bootmath_host.cpp) --------------------------------------
+BOOTMATH_LIB = os.path.join(HERE, "_build", "libbootmath_host.so")
+_bootmath = None
+
+
+def bootmath():
+    """libbootmath_host.so: NOT the oracle -- the product's own header on the host, for function-level tests and device == host bits."""
+    global _bootmath
+    if _bootmath is None:
+        if not os.path.exists(BOOTMATH_LIB):
+            build()
+        L = C.CDLL(BOOTMATH_LIB)
+        for f in ("bmh_pixel_error_squared", "bmh_mlesac_trial", "bmh_kth_smallest", "bmh_plane_trial"):
+            getattr(L, f).restype = C.c_double
+        for f in ("bmh_svd_onesided", "bmh_homography_from_matches", "bmh_refine_homography", "bmh_sym3_smallest_eigenvector", "bmh_homography_pipeline", "bmh_plane_pipeline"):
+            getattr(L, f).restype = None
+        _bootmath = L
+    return _bootmath
+
+
+class BootMath:
+    """numpy front of bootmath(): each bm:: function, and the two stages of csrc/boot.hip restated serially."""
+
+    @staticmethod
+    def svd_onesided(A):
+        """-> (U * diag(S) as left by the rotations [m, n], V [n, n], S [n] in column order, order [n]: columns by decreasing singular value)"""
+        A = np.array(A, np.float64, order="C")
+        m, n = A.shape
+        V = np.zeros((n, n)); S = np.zeros(n); order = np.zeros(n, np.int32)
+        bootmath().bmh_svd_onesided(_p(A), C.c_int(m), C.c_int(n), _p(V), _p(S), _p(order))
+        return A, V, S, order
+
+    @staticmethod
+    def homography_from_matches(m8, idx=None):
+        m = _d(m8).reshape(-1, 8); H = np.zeros(9)
+        if idx is None:
+            bootmath().bmh_homography_from_matches(_p(m), None, C.c_int(len(m)), _p(H))
+        else:
+            ix = np.ascontiguousarray(idx, np.int32)
+            bootmath().bmh_homography_from_matches(_p(m), _p(ix), C.c_int(len(ix)), _p(H))
+        return H
+
+    @staticmethod
+    def mlesac_trial(m8, seed, trial, max_err2=25.0):
+        m = _d(m8).reshape(-1, 8); H = np.zeros(9)
+        e = bootmath().bmh_mlesac_trial(_p(m), C.c_int(len(m)), C.c_uint(seed), C.c_int(trial), C.c_double(max_err2), _p(H))
+        return e, H
+
+    @staticmethod
+    def pixel_error_squared(H, m8):
+        return bootmath().bmh_pixel_error_squared(_p(_d(H)), _p(_d(m8)))
+
+    @staticmethod
+    def kth_smallest(v, k):
+        v = np.array(v, np.float64)
+        return bootmath().bmh_kth_smallest(_p(v), C.c_int(len(v)), C.c_int(k))
+
+    @staticmethod
+    def lu_solve(A, b):
+        A = np.array(A, np.float64, order="C"); b = np.array(b, np.float64)
+        ok = bootmath().bmh_lu_solve(_p(A), _p(b), C.c_int(len(b)))
+        return bool(ok), b
+
+    @staticmethod
+    def refine_homography(H, m8, inl):
+        H = np.array(H, np.float64).reshape(9); m = _d(m8).reshape(-1, 8); ix = np.ascontiguousarray(inl, np.int32)
+        bootmath().bmh_refine_homography(_p(H), _p(m), _p(ix), C.c_int(len(ix)))
+        return H
+
+    @staticmethod
+    def decompose_homography(H):
+        """-> list of (R [3, 3], t [3], n [3], d): eight, or none for the degenerate cases"""
+        R = np.zeros((8, 9)); t = np.zeros((8, 3)); nr = np.zeros((8, 3)); d = np.zeros(8)
+        k = bootmath().bmh_decompose_homography(_p(_d(H).reshape(9)), _p(R), _p(t), _p(nr), _p(d))
+        return [(R[i].reshape(3, 3), t[i], nr[i], d[i]) for i in range(k)]
+
+    @staticmethod
+    def choose_best_decomposition(H, m8, inl, max_err2=25.0):
+        m = _d(m8).reshape(-1, 8); ix = np.ascontiguousarray(inl, np.int32)
+        R = np.zeros(9); t = np.zeros(3); nr = np.zeros(3); d = C.c_double(0)
+        c = bootmath().bmh_choose_best_decomposition(_p(_d(H).reshape(9)), _p(m), C.c_int(len(m)), _p(ix), C.c_int(len(ix)), C.c_double(max_err2), _p(R), _p(t), _p(nr), C.byref(d))
+        return c, R.reshape(3, 3), t, nr, d.value
+
+    @staticmethod
+    def plane_trial(pos, seed, trial):
+        p = _d(pos).reshape(-1, 3); mean = np.zeros(3); nrm = np.zeros(3)
+        e = bootmath().bmh_plane_trial(_p(p), C.c_int(len(p)), C.c_uint(seed), C.c_int(trial), _p(mean), _p(nrm))
+        return e, mean, nrm
+
+    @staticmethod
+    def sym3_smallest_eigenvector(M):
+        out = np.zeros(3)
+        bootmath().bmh_sym3_smallest_eigenvector(_p(_d(M).reshape(9)), _p(out))
+        return out
+
+    @staticmethod
+    def plane_aligner(pos, mean, normal):
+        p = _d(pos).reshape(-1, 3); R = np.zeros(9); t = np.zeros(3)
+        ok = bootmath().bmh_plane_aligner(_p(p), C.c_int(len(p)), _p(_d(mean)), _p(_d(normal)), _p(R), _p(t))
+        return bool(ok), R.reshape(3, 3), t
+
+    @staticmethod
+    def homography_pipeline(m8, seed, max_pixel_error=5.0, wiggle_scale=0.1):
+        """boot_homography_stage serially -> visualslam_android_amd.capi.HomographyProbe, the record vslam_probe_homography_init fills"""
+        from visualslam_android_amd.capi import HomographyProbe
+        m = _d(m8).reshape(-1, 8); out = HomographyProbe()
+        bootmath().bmh_homography_pipeline(C.c_int(len(m)), _p(m), C.c_uint(seed), C.c_double(max_pixel_error), C.c_double(wiggle_scale), C.byref(out))
+        return out
+
+    @staticmethod
+    def plane_pipeline(pos, seed):
+        """boot_plane_stage serially -> visualslam_android_amd.capi.PlaneProbe"""
+        from visualslam_android_amd.capi import PlaneProbe
+        p = _d(pos).reshape(-1, 3); out = PlaneProbe()
+        bootmath().bmh_plane_pipeline(C.c_int(len(p)), _p(p), C.c_uint(seed), C.byref(out))
+        return out

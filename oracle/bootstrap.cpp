@@ -219,6 +219,47 @@ extern "C" int orc_homography_init(const double* m8, int n, double max_pixel_err
   return 1;
 }
 
+// ... and what it held on the way: the MLESAC homography, the indices of its inliers (inl: n ints), the refined homography, the branch
+// ChooseBestDecomposition took (0 no ambiguity, 1 / 2 the member of the ambiguous pair kept)
+extern "C" int orc_homography_init_stages(const double* m8, int n, double max_pixel_error, unsigned seed, double out12[12], int* n_inliers, double H_mlesac[9], int* inl,
+                                          double H_refined[9], int* choice) {
+  std::vector<orc::HMatch> m((size_t)n);
+  for (int i = 0; i < n; i++) { for (int k = 0; k < 2; k++) { m[i].first[k] = m8[8 * i + k]; m[i].second[k] = m8[8 * i + 2 + k]; } for (int k = 0; k < 4; k++) m[i].jac[k] = m8[8 * i + 4 + k]; }
+  orc::SE3 T;
+  orc::HInitStages st;
+  const bool ok = orc::homography_init_compute(m, max_pixel_error, seed, T, n_inliers, &st);
+  for (int i = 0; i < 9; i++) { H_mlesac[i] = st.H_mlesac[i]; H_refined[i] = st.H_refined[i]; }
+  for (size_t i = 0; i < st.inliers.size(); i++) inl[i] = st.inliers[i];
+  *choice = st.choice;
+  if (!ok) return 0;
+  for (int i = 0; i < 9; i++) out12[i] = T.R[i];
+  for (int i = 0; i < 3; i++) out12[9 + i] = T.t[i];
+  return 1;
+}
+
+// The HomographyMatch array of System::InitFromStereo (jni/MapMaker.cc:210-229) from n level-0 pixel pairs (x, y first, x, y second)
+extern "C" void orc_boot_matches(const double cam5[5], int w, int h, const int* xyxy, int n, double* m8) {
+  orc::Camera c; c.init(cam5, w, h, false);
+  for (int i = 0; i < n; i++) {
+    double j0[4];
+    orc::unproject_with_derivs(c, xyxy[4 * i], xyxy[4 * i + 1], m8 + 8 * i, j0);
+    orc::unproject_with_derivs(c, xyxy[4 * i + 2], xyxy[4 * i + 3], m8 + 8 * i + 2, m8 + 8 * i + 4);
+  }
+}
+
+extern "C" int orc_calc_plane_aligner_stages(const double* pos3, int n, unsigned seed, double out12[12], double best_mean[3], double best_normal[3]) {
+  std::vector<orc::V3> pos((size_t)n);
+  for (int i = 0; i < n; i++) pos[i] = orc::v3(pos3[3 * i], pos3[3 * i + 1], pos3[3 * i + 2]);
+  orc::SE3 T;
+  orc::PlaneStages st;
+  const bool ok = orc::calc_plane_aligner(pos, seed, T, &st);
+  for (int k = 0; k < 3; k++) { best_mean[k] = st.best_mean[k]; best_normal[k] = st.best_normal[k]; }
+  if (!ok) return 0;
+  for (int i = 0; i < 9; i++) out12[i] = T.R[i];
+  for (int i = 0; i < 3; i++) out12[9 + i] = T.t[i];
+  return 1;
+}
+
 extern "C" int orc_calc_plane_aligner(const double* pos3, int n, unsigned seed, double out12[12]) {
   std::vector<orc::V3> pos((size_t)n);
   for (int i = 0; i < n; i++) pos[i] = orc::v3(pos3[3 * i], pos3[3 * i + 1], pos3[3 * i + 2]);

@@ -148,6 +148,7 @@ struct Init {                                // the members of class HomographyI
   std::vector<HMatch> mvMatches, mvHomographyInliers;
   std::vector<HDecomposition> mvDecompositions;
   unsigned seed;
+  HInitStages* stages = nullptr;             // (not of the reference: where Compute leaves what it held on the way)
 
   static void unproject(const double v[2], double o[3]) { o[0] = v[0]; o[1] = v[1]; o[2] = 1.0; }                 // myUnproject :5-12
   static void project(const double v[3], double o[2]) { o[0] = v[0] / v[2]; o[1] = v[1] / v[2]; }                  // myProject :14-19
@@ -349,6 +350,7 @@ struct Init {                                // the members of class HomographyI
     std::stable_sort(mvDecompositions.begin(), mvDecompositions.end(), [](const HDecomposition& a, const HDecomposition& b) { return a.score < b.score; });
     mvDecompositions.resize(2);
     const double dRatio = (double)mvDecompositions[1].score / (double)mvDecompositions[0].score;
+    if (stages) stages->choice = 0;
     if (dRatio < 0.9) mvDecompositions.erase(mvDecompositions.begin() + 1);                                           // no ambiguity
     else {                                                                                                             // two-way ambiguity: Sampson score of all matches
       const double dErrorSquaredLimit = mdMaxPixelErrorSquared * 4;
@@ -370,6 +372,7 @@ struct Init {                                // the members of class HomographyI
         }
         adSampsonusScores[i] = dSumError;
       }
+      if (stages) stages->choice = adSampsonusScores[0] <= adSampsonusScores[1] ? 1 : 2;
       if (adSampsonusScores[0] <= adSampsonusScores[1]) mvDecompositions.erase(mvDecompositions.begin() + 1);
       else mvDecompositions.erase(mvDecompositions.begin());
     }
@@ -381,8 +384,10 @@ struct Init {                                // the members of class HomographyI
     if (mvMatches.size() < 4) return false;                                                                           // (the reference asserts in HomographyFromMatches)
     BestHomographyFromMatches_MLESAC();
     mvHomographyInliers.clear();
-    for (size_t i = 0; i < mvMatches.size(); i++) if (IsHomographyInlier(mm3BestHomography, mvMatches[i])) mvHomographyInliers.push_back(mvMatches[i]);
+    for (size_t i = 0; i < mvMatches.size(); i++) if (IsHomographyInlier(mm3BestHomography, mvMatches[i])) { mvHomographyInliers.push_back(mvMatches[i]); if (stages) stages->inliers.push_back((int)i); }
+    if (stages) memcpy(stages->H_mlesac, mm3BestHomography.m, sizeof(stages->H_mlesac));
     for (int iteration = 0; iteration < 5; iteration++) RefineHomographyWithInliers();
+    if (stages) memcpy(stages->H_refined, mm3BestHomography.m, sizeof(stages->H_refined));
     DecomposeHomography();
     if (mvDecompositions.size() != 8) return false;
     ChooseBestDecomposition();
@@ -394,9 +399,11 @@ struct Init {                                // the members of class HomographyI
 
 }  // namespace hinit
 
-bool homography_init_compute(const std::vector<HMatch>& m, double max_pixel_error, unsigned seed, SE3& second_from_first, int* n_inliers) {
+bool homography_init_compute(const std::vector<HMatch>& m, double max_pixel_error, unsigned seed, SE3& second_from_first, int* n_inliers, HInitStages* stages) {
   hinit::Init h;
   h.seed = seed;
+  h.stages = stages;
+  if (stages) { memset(stages->H_mlesac, 0, sizeof(stages->H_mlesac)); memset(stages->H_refined, 0, sizeof(stages->H_refined)); stages->inliers.clear(); stages->choice = 0; }
   const bool ok = h.Compute(m, max_pixel_error, second_from_first);
   if (n_inliers) *n_inliers = (int)h.mvHomographyInliers.size();
   return ok;
@@ -431,8 +438,9 @@ static void sym3_least_eigenvector(const double A[9], double out[3]) {
 }
 
 // MapMaker::CalcPlaneAligner, jni/MapMaker.cc:1104-1231, over the world positions of all map points
-bool calc_plane_aligner(const std::vector<V3>& vpPoints, unsigned seed, SE3& se3Aligner) {
+bool calc_plane_aligner(const std::vector<V3>& vpPoints, unsigned seed, SE3& se3Aligner, PlaneStages* stages) {
   se3Aligner = SE3();
+  if (stages) for (int k = 0; k < 3; k++) { stages->best_mean[k] = 0.0; stages->best_normal[k] = k == 2 ? 1.0 : 0.0; }
   const unsigned nPoints = (unsigned)vpPoints.size();
   if (nPoints < 10) return false;                                                                                      // :1107-1110
   const int nRansacs = 100;
@@ -461,6 +469,7 @@ bool calc_plane_aligner(const std::vector<V3>& vpPoints, unsigned seed, SE3& se3
     }
     if (dSumError < dBestDistSquared) { dBestDistSquared = dSumError; v3BestMean = v3Mean; v3BestNormal = v3Normal; }
   }
+  if (stages) for (int k = 0; k < 3; k++) { stages->best_mean[k] = v3BestMean[k]; stages->best_normal[k] = v3BestNormal[k]; }
   std::vector<V3> vv3Inliers;                                                                                          // :1165-1178
   for (unsigned i = 0; i < nPoints; i++) {
     const V3 v3Diff = vpPoints[i] - v3BestMean;

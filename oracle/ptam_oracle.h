@@ -133,8 +133,16 @@ void orc_sys_get_init_info(void* sys, int out[6]);   /* stage, trails, InitFromS
 int orc_sys_get_trails(void* sys, int* out4 /* initial x, y, current x, y */, int cap);
 /* HomographyInit::Compute (jni/HomographyInit.cc:43-71) on n matches given as 8 doubles each: first (z = 1 plane), second, d pixel / d plane (2x2 row-major) */
 int orc_homography_init(const double* matches8, int n, double max_pixel_error, unsigned seed, double out12[12], int* n_inliers);
+/* ... with what Compute held on the way: the MLESAC homography, the indices of its inliers (inl: room for n), the refined homography, the branch of
+ * ChooseBestDecomposition (0 no ambiguity, 1 / 2 the member of the ambiguous pair kept) */
+int orc_homography_init_stages(const double* matches8, int n, double max_pixel_error, unsigned seed, double out12[12], int* n_inliers, double H_mlesac[9], int* inl,
+                               double H_refined[9], int* choice);
+/* the HomographyMatch array InitFromStereo makes of n level-0 pixel pairs (jni/MapMaker.cc:210-229): 8 doubles per match */
+void orc_boot_matches(const double cam5[5], int w, int h, const int* xyxy, int n, double* matches8);
 /* MapMaker::CalcPlaneAligner (jni/MapMaker.cc:1104-1231) on n points */
 int orc_calc_plane_aligner(const double* pos3, int n, unsigned seed, double out12[12]);
+/* ... with the RANSAC's best mean and normal */
+int orc_calc_plane_aligner_stages(const double* pos3, int n, unsigned seed, double out12[12], double best_mean[3], double best_normal[3]);
 void orc_sys_idle_job(void* sys, int job);   /* one of them: 0 idle BundleAdjustRecent, 1 ReFindNewlyMade, 2 BundleAdjustAll, 3 ReFindFromFailureQueue */
 void orc_sys_idle_iteration(void* sys);        /* one pass through the idle jobs of MapMaker::run, jni/MapMaker.cc:94-117 */
 void orc_sys_get_idle_stats(void* sys, int out[6]);   /* points re-found by ReFindNewlyMade / ReFindFromFailureQueue, BundleAdjustAll / idle BundleAdjustRecent calls, queue lengths */

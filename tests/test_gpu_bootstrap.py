@@ -6,7 +6,12 @@ cyclic Jacobi); only the definition of the random draws is common.  So the integ
 matching, list order), the homography's inlier count, which trails become stereo points, their sub-pixel positions -- are compared
 exactly, and everything computed FROM the homography (second camera pose, triangulated points, the adjusted map) to a tolerance; the
 tracking that follows to the pose tolerance in units of the map's own baseline.  PARITY UNPINNED against the reference: it draws
-from rand() and holds no fixture for this."""
+from rand() and holds no fixture for this.
+
+What this file sees of HomographyInit and the plane aligner is the map AFTER 55 bundle adjustments, which repair a slightly wrong
+second camera pose.  The two stages themselves are observed in tests/test_gpu_bootstrap_stages.py (every stage of the device functions
+against a host build of csrc/bootstrap_math.h bit for bit, and against the oracle's stages), tied to the product path here by
+test_init_from_stereo_with_host_keyframes_and_matches."""
 import numpy as np
 import pytest
 
@@ -118,6 +123,14 @@ def test_init_from_stereo_with_host_keyframes_and_matches():
     io, ig = o.init_info(), g.init_info(0)
     assert (io["stage"], io["init_ok"], io["map_good"], io["hom_inliers"], io["stereo_points"]) == (ig["stage"], ig["init_ok"], ig["map_good"], ig["hom_inliers"], ig["stereo_points"]), (io, ig)
     assert io["stereo_points"] > 100
+    # the tie to tests/test_gpu_bootstrap_stages.py: the homography stage alone, on a second system, with the same matches and the default
+    # boot seed, is the device function the product ran -- same inlier count.  (Its scaled pose cannot be read back from the map: the 55
+    # adjustments between the homography and the plane aligner have moved the second keyframe, so undoing the aligner does not return it.)
+    g2 = capi.System(capi.default_params(w, h, 1, bootstrap=1, **kw))
+    rec = g2.probe_homography_init(0, 1, matches_xyxy=matches)
+    assert rec.ok == 1 and rec.n == len(matches) and rec.n_inliers == ig["hom_inliers"], (rec.n_inliers, ig)
+    assert g2.init_info(0) == dict(stage=0, trails=0, init_ok=0, hom_inliers=0, stereo_points=0, map_good=0)       # a probe leaves the tracker alone
+    g2.close()
     mo, mg = o.keyframe_meas(1), g.keyframe_meas(0, 1)
     tr_o, tr_g = mo["source"] == 3, mg["source"] == 3
     assert np.array_equal(mo["pt"][tr_o], mg["pt"][tr_g]) and np.array_equal(mo["root"][tr_o], mg["root"][tr_g])      # sub-pixel positions of the stereo points

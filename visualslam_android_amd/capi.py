@@ -46,6 +46,23 @@ class TrackState(C.Structure):
                 ("n_zmssd", C.c_longlong), ("n_ba_trials", C.c_longlong)]
 
 
+PROBE_MAX_MATCHES = 1000
+
+
+class HomographyProbe(C.Structure):
+    """Mirror of struct vslam_homography_probe."""
+    _fields_ = [("ok", C.c_int), ("n", C.c_int), ("best_trial", C.c_int), ("n_inliers", C.c_int), ("choice", C.c_int), ("reserved", C.c_int),
+                ("scores", C.c_double * 300), ("H_mlesac", C.c_double * 9), ("H_refined", C.c_double * 9),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("normal", C.c_double * 3), ("d", C.c_double), ("t_scaled", C.c_double * 3),
+                ("inliers", C.c_int * PROBE_MAX_MATCHES), ("matches", C.c_double * (PROBE_MAX_MATCHES * 8))]
+
+
+class PlaneProbe(C.Structure):
+    """Mirror of struct vslam_plane_probe."""
+    _fields_ = [("have", C.c_int), ("n", C.c_int), ("best_trial", C.c_int), ("reserved", C.c_int), ("sums", C.c_double * 100),
+                ("mean", C.c_double * 3), ("normal", C.c_double * 3), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
 _lib = None
 
 # name -> (restype, argtypes); every symbol include/vslam_c.h declares
@@ -116,6 +133,8 @@ SYMBOLS = {
     "vslam_set_boot_seed": (_i, [_sys, _i, C.c_uint]),
     "vslam_get_init_info": (_i, [_sys, _i, _vp]),
     "vslam_get_trails": (_i, [_sys, _i, _vp, _i, _vp]),
+    "vslam_probe_homography_init": (_i, [_sys, _i, _i, _vp, _vp, C.c_uint, _d, _vp]),
+    "vslam_probe_plane_aligner": (_i, [_sys, _i, _i, _vp, C.c_uint, _vp]),
     "vslam_read_map_dump": (_i, [C.c_char_p, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "vslam_load_map": (_i, [_sys, _i, C.c_char_p]),
     "vslam_get_keyframe_measurements": (_i, [_sys, _i, _i, _vp, _vp, _vp, _vp, _i]),
@@ -544,6 +563,24 @@ class System:
         n = C.c_int(0)
         _check(self.lib.vslam_get_trails(self.h, stream, o.ctypes.data, 1000, C.byref(n)))
         return o[:n.value]
+
+    def probe_homography_init(self, stream, seed, matches_xyxy=None, m8=None, max_pixel_error=5.0):
+        """vslam_probe_homography_init: the homography stage alone on integer pixel pairs (n, 4) or ready matches (n, 8) -> HomographyProbe"""
+        out = HomographyProbe()
+        if m8 is not None:
+            a = np.ascontiguousarray(m8, np.float64).reshape(-1, 8)
+            _check(self.lib.vslam_probe_homography_init(self.h, stream, len(a), None, a.ctypes.data, seed, max_pixel_error, C.addressof(out)))
+        else:
+            a = np.ascontiguousarray(matches_xyxy, np.int32).reshape(-1, 4)
+            _check(self.lib.vslam_probe_homography_init(self.h, stream, len(a), a.ctypes.data, None, seed, max_pixel_error, C.addressof(out)))
+        return out
+
+    def probe_plane_aligner(self, stream, seed, pos3):
+        """vslam_probe_plane_aligner: CalcPlaneAligner alone on (n, 3) positions -> PlaneProbe"""
+        a = np.ascontiguousarray(pos3, np.float64).reshape(-1, 3)
+        out = PlaneProbe()
+        _check(self.lib.vslam_probe_plane_aligner(self.h, stream, len(a), a.ctypes.data, seed, C.addressof(out)))
+        return out
 
     def idle_stats(self, stream):
         o = np.zeros(6, np.int32)

@@ -14,6 +14,7 @@
 //                  k_boot_scene_depth, AddSomeMapPoints(0, 3, 1, 2), BundleAdjustAll until converged, k_boot_plane.
 // The existing map-maker kernels are gated on kf_pending and address "the keyframe being added" as slot n_kf: k_boot_phase sets
 // those two for the streams InitFromStereo runs for, and back.
+#include <string.h>
 #include "vslam_internal.h"
 #include "grow_dev.h"
 #include "bootstrap_math.h"
@@ -244,36 +245,41 @@ DEVFN void unproject_with_derivs(const CamModel& c, double ix, double iy, double
   jac[1] = c.focal[0] * (fy * x); jac[3] = c.focal[1] * (fy * y + last_factor);
 }
 
-// InitFromStereo up to the second camera's pose (jni/MapMaker.cc:204-258): the matches, HomographyInit::Compute, the scale
-__global__ __launch_bounds__(BOOT_THREADS) void k_boot_homography(MapDev m, TrackParams tp) {
-  const int s = blockIdx.x;
-  TrackerState* st = &m.st[s];
-  if (!st->boot_run) return;
+// A stream's slices of InitFromStereo's work arrays
+DEVFN bm::Match* boot_matches(const MapDev& m, int s) { return (bm::Match*)(m.boot_match + (size_t)s * BOOT_MAX_TRAILS * 8); }
+DEVFN int* boot_inliers(const MapDev& m, int s) { return m.boot_inl + (size_t)s * BOOT_MAX_TRAILS; }
+HDFN size_t boot_ws_stride(size_t max_points) { return 3 * max_points > BOOT_MAX_TRAILS ? 3 * max_points : BOOT_MAX_TRAILS; }
+DEVFN double* boot_workspace(const MapDev& m, const TrackParams& tp, int s) { return m.boot_ws + (size_t)s * boot_ws_stride((size_t)tp.max_points); }
+
+// The matches of InitFromStereo (jni/MapMaker.cc:210-229) from level-0 pixel pairs; the derivatives of the second position are the ones kept
+DEVFN void boot_fill_matches(const CamModel& cam, const int* pos, int n, bm::Match* mt) {
+  for (int i = threadIdx.x; i < n; i += BOOT_THREADS) {
+    bm::Match q; double j0[4];
+    unproject_with_derivs(cam, (double)pos[4 * i], (double)pos[4 * i + 1], q.first, j0);
+    unproject_with_derivs(cam, (double)pos[4 * i + 2], (double)pos[4 * i + 3], q.second, q.jac);
+    mt[i] = q;
+  }
+}
+
+// HomographyInit::Compute (jni/HomographyInit.cc:43-71) and the scale of the translation (jni/MapMaker.cc:243-250) by one workgroup
+// of BOOT_THREADS: mt[0..n) is filled and a barrier has passed.  The 300 MLESAC trials go round the threads, the inlier list is
+// compacted in match order into inl, lane 0 refines, decomposes and chooses (ws: n doubles).  scores (may be null) receives every
+// trial's score.  *out (LDS or global) is written by thread 0 and complete for the whole workgroup on return.
+DEVFN void boot_homography_stage(const bm::Match* mt, int n, unsigned seed, double max2, double wiggle_scale, int* inl, double* ws, double* scores, bm::HomographyStages* out) {
   __shared__ double sh_err[BOOT_THREADS];
   __shared__ int sh_trial[BOOT_THREADS];
   __shared__ double sh_H[9];
-  __shared__ int wsum[BOOT_WAVES], sh_ninl;
+  __shared__ int wsum[BOOT_WAVES], sh_ninl, sh_best;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n = st->n_trails;
-  const int* pos = trail_positions(m, s, st->trail_buf);
-  bm::Match* mt = (bm::Match*)(m.boot_match + (size_t)s * BOOT_MAX_TRAILS * 8);
-  int* inl = m.boot_inl + (size_t)s * BOOT_MAX_TRAILS;
-  for (int i = threadIdx.x; i < n; i += BOOT_THREADS) {              // :210-229 (the derivatives of the second position are the ones kept)
-    bm::Match q; double j0[4];
-    unproject_with_derivs(tp.cam, (double)pos[4 * i], (double)pos[4 * i + 1], q.first, j0);
-    unproject_with_derivs(tp.cam, (double)pos[4 * i + 2], (double)pos[4 * i + 3], q.second, q.jac);
-    mt[i] = q;
-  }
-  __syncthreads();
-  const double max2 = 5.0 * 5.0;                                     // HomographyInit.Compute(vMatches, 5.0, se3), :236
-  bool ok = n >= 4;
-  if (ok) {
+  if (threadIdx.x == 0) { bm::HomographyStages z = {}; z.best_trial = -1; *out = z; sh_best = -1; }
+  if (n >= 4) {
     if (n < 10) { if (threadIdx.x == 0) bm::homography_from_matches(mt, nullptr, n, sh_H); }
     else {                                                           // BestHomographyFromMatches_MLESAC, :232-262
       double best = 999999999999999999.9; int bt = 0x7fffffff;
       for (int t = threadIdx.x; t < 300; t += BOOT_THREADS) {
         double H[9];
-        const double e = bm::mlesac_trial(mt, n, st->boot_seed, t, max2, H);
+        const double e = bm::mlesac_trial(mt, n, seed, t, max2, H);
+        if (scores) scores[t] = e;
         if (e < best) { best = e; bt = t; }
       }
       sh_err[threadIdx.x] = best; sh_trial[threadIdx.x] = bt;
@@ -287,7 +293,8 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_boot_homography(MapDev m, Trac
         // a thread's best is its FIRST minimum, and a later trial of the same thread can only have won with a strictly smaller
         // error: the scan above sees every trial that could be the global first minimum
         for (int i = 0; i < 9; i++) sh_H[i] = i % 4 == 0 ? 1.0 : 0.0;
-        if (t0 >= 0) { double H[9]; bm::mlesac_trial(mt, n, st->boot_seed, t0, max2, H); for (int i = 0; i < 9; i++) sh_H[i] = H[i]; }
+        if (t0 >= 0) { double H[9]; bm::mlesac_trial(mt, n, seed, t0, max2, H); for (int i = 0; i < 9; i++) sh_H[i] = H[i]; }
+        sh_best = t0;
       }
     }
     __syncthreads();
@@ -307,32 +314,46 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_boot_homography(MapDev m, Trac
     }
     if (threadIdx.x == 0) sh_ninl = base;
     __syncthreads();
+    if (threadIdx.x == 0) { out->best_trial = sh_best; bm::homography_finish(sh_H, mt, n, inl, sh_ninl, max2, wiggle_scale, ws, *out); }
   }
+  __syncthreads();
+}
+
+// InitFromStereo up to the second camera's pose (jni/MapMaker.cc:204-258): the matches, HomographyInit::Compute, the scale
+__global__ __launch_bounds__(BOOT_THREADS) void k_boot_homography(MapDev m, TrackParams tp) {
+  const int s = blockIdx.x;
+  TrackerState* st = &m.st[s];
+  if (!st->boot_run) return;
+  __shared__ bm::HomographyStages r;
+  const int n = st->n_trails;
+  bm::Match* mt = boot_matches(m, s);
+  boot_fill_matches(tp.cam, trail_positions(m, s, st->trail_buf), n, mt);
+  __syncthreads();
+  boot_homography_stage(mt, n, st->boot_seed, 5.0 * 5.0 /* HomographyInit.Compute(vMatches, 5.0, se3), :236 */, tp.wiggle_scale, boot_inliers(m, s),
+                        boot_workspace(m, tp, s), nullptr, &r);
   if (threadIdx.x != 0) return;
-  Pose se3 = pose_identity();
-  if (ok) {
-    double H[9];
-    for (int i = 0; i < 9; i++) H[i] = sh_H[i];
-    double* ws = m.boot_ws + (size_t)s * (3 * (size_t)tp.max_points > BOOT_MAX_TRAILS ? 3 * (size_t)tp.max_points : BOOT_MAX_TRAILS);
-    for (int it = 0; it < 5; it++) bm::refine_homography(H, mt, inl, sh_ninl, ws);   // :58-59
-    bm::Decomposition d[8];
-    if (bm::decompose_homography(H, d) != 8) ok = false;             // :62-66
-    else {
-      bm::choose_best_decomposition(d, H, mt, n, inl, sh_ninl, max2);
-      for (int i = 0; i < 9; i++) se3.R[i] = d[0].R[i];
-      for (int i = 0; i < 3; i++) se3.t[i] = d[0].t[i];
-      const double mag = sqrt(se3.t[0] * se3.t[0] + se3.t[1] * se3.t[1] + se3.t[2] * se3.t[2]);
-      if (mag == 0) ok = false;                                      // :243-248
-      else for (int i = 0; i < 3; i++) se3.t[i] *= tp.wiggle_scale / mag;   // :250
-    }
-    st->n_hom_inliers = sh_ninl;
-  }
-  if (!ok) { st->boot_run = 0; st->boot_ok = 0; st->init_stage = 2; return; }        // the tracker's stage is COMPLETE either way, jni/Tracker.cc:279
+  if (n >= 4) st->n_hom_inliers = r.n_inliers;
+  if (!r.ok) { st->boot_run = 0; st->boot_ok = 0; st->init_stage = 2; return; }      // the tracker's stage is COMPLETE either way, jni/Tracker.cc:279
+  Pose se3;
+  for (int i = 0; i < 9; i++) se3.R[i] = r.R[i];
+  for (int i = 0; i < 3; i++) se3.t[i] = r.t_scaled[i];
   st->boot_ok = 1;
   const size_t K = tp.max_keyframes;
   m.kf_pose[(size_t)s * K + 0] = pose_identity(); m.kf_fixed[(size_t)s * K + 0] = 1;   // pkFirst, :256-257
   st->pose_final = se3; st->depth_mean = 0; st->depth_sigma = 0;                       // pkSecond's pose for k_add_keyframe (slot n_kf = 1)
   st->kf_pending = 1;
+}
+
+// The same stage with nothing of the tracker or the map around it (vslam_probe_homography_init): stream s's work slices, the matches
+// either made from pixel pairs as above (pos) or already in the stream's match slice; writes *out and scores only.
+__global__ __launch_bounds__(BOOT_THREADS) void k_probe_homography(MapDev m, TrackParams tp, int s, int n, const int* pos, unsigned seed, double max2, double* scores,
+                                                                   bm::HomographyStages* out) {
+  __shared__ bm::HomographyStages r;
+  bm::Match* mt = boot_matches(m, s);
+  if (pos) boot_fill_matches(tp.cam, pos, n, mt);
+  __syncthreads();
+  boot_homography_stage(mt, n, seed, max2, tp.wiggle_scale, boot_inliers(m, s), boot_workspace(m, tp, s), scores, &r);
+  if (threadIdx.x == 0) *out = r;
 }
 
 // The points of the stereo pair (jni/MapMaker.cc:263-337), one wavefront per match: template of the first keyframe, sub-pixel
@@ -350,7 +371,7 @@ __global__ __launch_bounds__(BOOT_THREADS) __attribute__((amdgpu_waves_per_eu(2,
   const int K = tp.max_keyframes, P = tp.max_points;
   const int n = st->n_trails;
   const int* pos = trail_positions(m, s, st->trail_buf);
-  const bm::Match* mt = (const bm::Match*)(m.boot_match + (size_t)s * BOOT_MAX_TRAILS * 8);
+  const bm::Match* mt = boot_matches(m, s);
   const uint8_t* img0 = m.kf_img[0] + ((size_t)s * K + 0) * a.kf_stride;
   const uint8_t* img1 = m.kf_img[0] + ((size_t)s * K + 1) * a.kf_stride;
   const Pose se3 = m.kf_pose[(size_t)s * K + 1];
@@ -446,36 +467,42 @@ __global__ void k_boot_scene_depth(MapDev m, TrackParams tp) {
   if (k == 0) st->wiggle_depth_norm = tp.wiggle_scale / mean;        // mdWiggleScaleDepthNormalized
 }
 
+// CalcPlaneAligner (jni/MapMaker.cc:1104-1231) over pos[0..n) by one workgroup of BOOT_THREADS (pos is filled and a barrier has
+// passed): one thread per RANSAC trial, thread 0 picks the plane and makes the aligner.  sums (may be null) receives the 100 trial
+// sums.  *out (LDS or global) is written by thread 0 and complete for the whole workgroup on return.
+DEVFN void boot_plane_stage(const double* pos, int n, unsigned seed, double* sums, bm::PlaneStages* out) {
+  __shared__ double sh_err[128];
+  if (threadIdx.x == 0) { bm::PlaneStages z = {}; z.best_trial = -1; *out = z; }
+  if (n >= 10) {                                                     // :1107-1110
+    if (threadIdx.x < 100) {
+      double mean[3], nrm[3];
+      const double e = bm::plane_trial(pos, n, seed, (int)threadIdx.x, mean, nrm);
+      sh_err[threadIdx.x] = e;
+      if (sums) sums[threadIdx.x] = e;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) bm::plane_finish(pos, n, seed, sh_err, *out);
+  }
+  __syncthreads();
+}
+
 // CalcPlaneAligner + ApplyGlobalTransformationToMap, then the end of InitFromStereo (:366-372) and the tracker's side of it
 __global__ __launch_bounds__(BOOT_THREADS) void k_boot_plane(MapDev m, TrackParams tp) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
   if (!st->boot_run) return;
-  __shared__ double sh_err[128];
-  __shared__ double sh_T[12];
-  __shared__ int sh_have;
+  __shared__ bm::PlaneStages r;
   const size_t K = tp.max_keyframes, P = tp.max_points;
   const int n = st->n_points, nk = st->n_kf;
   MapPointDev* pts = m.pts + (size_t)s * P;
-  double* pos = m.boot_ws + (size_t)s * (3 * P > BOOT_MAX_TRAILS ? 3 * P : BOOT_MAX_TRAILS);
+  double* pos = boot_workspace(m, tp, s);
   for (int i = threadIdx.x; i < n; i += BOOT_THREADS) for (int k = 0; k < 3; k++) pos[3 * i + k] = pts[i].pos[k];
   __syncthreads();
-  if (n >= 10) {                                                     // :1107-1110
-    if (threadIdx.x < 100) { double mean[3], nrm[3]; sh_err[threadIdx.x] = bm::plane_trial(pos, n, st->boot_seed + 1u, (int)threadIdx.x, mean, nrm); }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double best = 9999999999999999.9; int bt = -1;
-      for (int t = 0; t < 100; t++) if (!(sh_err[t] < 0.0) && sh_err[t] < best) { best = sh_err[t]; bt = t; }
-      double mean[3] = {0, 0, 0}, nrm[3] = {0, 0, 1};
-      if (bt >= 0) bm::plane_trial(pos, n, st->boot_seed + 1u, bt, mean, nrm);
-      sh_have = bm::plane_aligner(pos, n, mean, nrm, sh_T, sh_T + 9) ? 1 : 0;
-    }
-  } else if (threadIdx.x == 0) sh_have = 0;
-  __syncthreads();
-  if (sh_have) {                                                     // ApplyGlobalTransformationToMap, :440-449
+  boot_plane_stage(pos, n, st->boot_seed + 1u, nullptr, &r);
+  if (r.have) {                                                      // ApplyGlobalTransformationToMap, :440-449
     Pose T;
-    for (int i = 0; i < 9; i++) T.R[i] = sh_T[i];
-    for (int i = 0; i < 3; i++) T.t[i] = sh_T[9 + i];
+    for (int i = 0; i < 9; i++) T.R[i] = r.R[i];
+    for (int i = 0; i < 3; i++) T.t[i] = r.t[i];
     const Pose Tinv = pose_inverse(T);
     for (int k = threadIdx.x; k < nk; k += BOOT_THREADS) m.kf_pose[(size_t)s * K + k] = pose_mul(m.kf_pose[(size_t)s * K + k], Tinv);
     __syncthreads();
@@ -511,6 +538,13 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_boot_plane(MapDev m, TrackPara
   }
 }
 
+// The plane stage alone (vslam_probe_plane_aligner): the positions are in stream s's workspace slice; writes *out and sums only.
+__global__ __launch_bounds__(BOOT_THREADS) void k_probe_plane(MapDev m, TrackParams tp, int s, int n, unsigned seed, double* sums, bm::PlaneStages* out) {
+  __shared__ bm::PlaneStages r;
+  boot_plane_stage(boot_workspace(m, tp, s), n, seed, sums, &r);
+  if (threadIdx.x == 0) *out = r;
+}
+
 __global__ void k_boot_press(MapDev m, int S, int stream, unsigned seed, int set_seed) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S || (stream >= 0 && s != stream)) return;
@@ -528,7 +562,7 @@ int boot_alloc(vslam_system* sys) {
   if ((r = get(S * 2 * BOOT_MAX_TRAILS * 4 * sizeof(int), (void**)&sys->map.trail_pos))) return r;
   if ((r = get(S * BOOT_MAX_TRAILS * 8 * sizeof(double), (void**)&sys->map.boot_match))) return r;
   if ((r = get(S * BOOT_MAX_TRAILS * sizeof(int), (void**)&sys->map.boot_inl))) return r;
-  if ((r = get(S * (3 * P > BOOT_MAX_TRAILS ? 3 * P : BOOT_MAX_TRAILS) * sizeof(double), (void**)&sys->map.boot_ws))) return r;
+  if ((r = get(S * boot_ws_stride(P) * sizeof(double), (void**)&sys->map.boot_ws))) return r;
   return VSLAM_OK;
 }
 
@@ -653,5 +687,79 @@ extern "C" int vslam_get_trails(vslam_system* sys, int stream, int* out4, int ca
   if (n) *n = st.n_trails;
   const int k = st.n_trails < cap ? st.n_trails : cap;
   if (k > 0) HIPCHK(hipMemcpy(out4, sys->map.trail_pos + ((size_t)stream * 2 + st.trail_buf) * BOOT_MAX_TRAILS * 4, sizeof(int) * 4 * (size_t)k, hipMemcpyDeviceToHost));
+  return VSLAM_OK;
+}
+
+// ---- the two stages on their own (vslam_probe_homography_init, vslam_probe_plane_aligner) ------------------------------------
+namespace {
+struct ProbeBuf {            // device memory of one probe call
+  void* p = nullptr;
+  ~ProbeBuf() { if (p) (void)hipFree(p); }
+};
+// a probe works in the stream's InitFromStereo slices: not inside a frame, not while the stream's trails are running
+int probe_admissible(vslam_system* sys, int stream, const char* who) {
+  if (!sys->p.bootstrap) { vslam_set_error("%s: created with bootstrap = 0", who); return VSLAM_E_STATE; }
+  if (sys->frame_open) { vslam_set_error("%s: a stage-wise frame is open", who); return VSLAM_E_STATE; }
+  int info[6];
+  const int r = vslam_get_init_info(sys, stream, info); if (r) return r;
+  if (info[0] == 1) { vslam_set_error("%s: the stream has an initialisation in progress", who); return VSLAM_E_STATE; }
+  return VSLAM_OK;
+}
+}  // namespace
+
+extern "C" int vslam_probe_homography_init(vslam_system* sys, int stream, int n, const int* matches_xyxy, const double* m8, unsigned seed, double max_pixel_error,
+                                           vslam_homography_probe* out) {
+  if (!sys || stream < 0 || stream >= sys->S || n < 0 || !out || (matches_xyxy && m8) || (n > 0 && !matches_xyxy && !m8)) { vslam_set_error("probe_homography_init: bad argument"); return VSLAM_E_INVALID; }
+  if (n > BOOT_MAX_TRAILS) { vslam_set_error("probe_homography_init: at most %d matches", BOOT_MAX_TRAILS); return VSLAM_E_CAPACITY; }
+  int r = probe_admissible(sys, stream, "probe_homography_init"); if (r) return r;
+  static_assert(VSLAM_PROBE_MAX_MATCHES == BOOT_MAX_TRAILS && sizeof(bm::Match) == 8 * sizeof(double), "vslam_homography_probe holds a stream's match slice");
+  const size_t off_scores = sizeof(bm::HomographyStages), off_pos = off_scores + 300 * sizeof(double);
+  ProbeBuf buf;
+  HIPCHK(hipMalloc(&buf.p, off_pos + sizeof(int) * 4 * (size_t)(n > 0 ? n : 1)));
+  hipStream_t q = sys->stream;
+  HIPCHK(hipMemsetAsync(buf.p, 0, off_pos, q));
+  int* d_pos = nullptr;
+  double* d_match = sys->map.boot_match + (size_t)stream * BOOT_MAX_TRAILS * 8;
+  int* d_inl = sys->map.boot_inl + (size_t)stream * BOOT_MAX_TRAILS;
+  if (n > 0 && matches_xyxy) { d_pos = (int*)((char*)buf.p + off_pos); HIPCHK(hipMemcpyAsync(d_pos, matches_xyxy, sizeof(int) * 4 * (size_t)n, hipMemcpyHostToDevice, q)); }
+  else if (n > 0) HIPCHK(hipMemcpyAsync(d_match, m8, sizeof(double) * 8 * (size_t)n, hipMemcpyHostToDevice, q));
+  hipLaunchKernelGGL(k_probe_homography, dim3(1), dim3(BOOT_THREADS), 0, q, sys->map, sys->tp, stream, n, (const int*)d_pos, seed, max_pixel_error * max_pixel_error,
+                     (double*)((char*)buf.p + off_scores), (bm::HomographyStages*)buf.p);
+  HIPCHK(hipGetLastError());
+  bm::HomographyStages hs;
+  memset(out, 0, sizeof(*out));
+  HIPCHK(hipMemcpyAsync(&hs, buf.p, sizeof(hs), hipMemcpyDeviceToHost, q));
+  HIPCHK(hipMemcpyAsync(out->scores, (char*)buf.p + off_scores, 300 * sizeof(double), hipMemcpyDeviceToHost, q));
+  if (n > 0) HIPCHK(hipMemcpyAsync(out->matches, d_match, sizeof(double) * 8 * (size_t)n, hipMemcpyDeviceToHost, q));
+  HIPCHK(hipStreamSynchronize(q));
+  if (hs.n_inliers < 0 || hs.n_inliers > n) { vslam_set_error("probe_homography_init: inlier count %d of %d matches", hs.n_inliers, n); return VSLAM_E_CAPACITY; }
+  if (hs.n_inliers > 0) HIPCHK(hipMemcpy(out->inliers, d_inl, sizeof(int) * (size_t)hs.n_inliers, hipMemcpyDeviceToHost));
+  out->ok = hs.ok; out->n = n; out->best_trial = hs.best_trial; out->n_inliers = hs.n_inliers; out->choice = hs.choice;
+  for (int i = 0; i < 9; i++) { out->H_mlesac[i] = hs.H_mlesac[i]; out->H_refined[i] = hs.H_refined[i]; out->R[i] = hs.R[i]; }
+  for (int i = 0; i < 3; i++) { out->t[i] = hs.t[i]; out->normal[i] = hs.n[i]; out->t_scaled[i] = hs.t_scaled[i]; }
+  out->d = hs.d;
+  return VSLAM_OK;
+}
+
+extern "C" int vslam_probe_plane_aligner(vslam_system* sys, int stream, int n, const double* pos3, unsigned seed, vslam_plane_probe* out) {
+  if (!sys || stream < 0 || stream >= sys->S || n < 0 || !out || (n > 0 && !pos3)) { vslam_set_error("probe_plane_aligner: bad argument"); return VSLAM_E_INVALID; }
+  if (n > sys->p.max_points) { vslam_set_error("probe_plane_aligner: at most max_points = %d points", sys->p.max_points); return VSLAM_E_CAPACITY; }
+  int r = probe_admissible(sys, stream, "probe_plane_aligner"); if (r) return r;
+  const size_t off_sums = sizeof(bm::PlaneStages);
+  ProbeBuf buf;
+  HIPCHK(hipMalloc(&buf.p, off_sums + 100 * sizeof(double)));
+  hipStream_t q = sys->stream;
+  HIPCHK(hipMemsetAsync(buf.p, 0, off_sums + 100 * sizeof(double), q));
+  if (n > 0) HIPCHK(hipMemcpyAsync(sys->map.boot_ws + (size_t)stream * boot_ws_stride((size_t)sys->p.max_points), pos3, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, q));
+  hipLaunchKernelGGL(k_probe_plane, dim3(1), dim3(BOOT_THREADS), 0, q, sys->map, sys->tp, stream, n, seed, (double*)((char*)buf.p + off_sums), (bm::PlaneStages*)buf.p);
+  HIPCHK(hipGetLastError());
+  bm::PlaneStages ps;
+  memset(out, 0, sizeof(*out));
+  HIPCHK(hipMemcpyAsync(&ps, buf.p, sizeof(ps), hipMemcpyDeviceToHost, q));
+  HIPCHK(hipMemcpyAsync(out->sums, (char*)buf.p + off_sums, 100 * sizeof(double), hipMemcpyDeviceToHost, q));
+  HIPCHK(hipStreamSynchronize(q));
+  out->have = ps.have; out->n = n; out->best_trial = ps.best_trial;
+  for (int i = 0; i < 3; i++) { out->mean[i] = ps.mean[i]; out->normal[i] = ps.normal[i]; out->t[i] = ps.t[i]; }
+  for (int i = 0; i < 9; i++) out->R[i] = ps.R[i];
   return VSLAM_OK;
 }

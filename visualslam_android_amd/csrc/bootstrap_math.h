@@ -15,7 +15,10 @@
 //  * Eigen::EigenSolver(m3Cov).eigenvectors().col(2) (MapMaker.cc:1197-1198) is an unspecified column for a general solver;
 //    the intent (PTAM: the eigenvector of least variance) is what is computed: cyclic Jacobi on the symmetric 3x3.
 // None of this is covered by a fixture of the reference: PARITY UNPINNED; the tests hold the results against the ground truth of
-// synthetic planar scenes and hold host and device to the same bits.
+// synthetic planar scenes.  Host and device are held to the same bits stage by stage: oracle/bootmath_host.cpp compiles this header
+// for the host (tests/test_bootmath_host.py holds every function of it to a high-precision statement of its operation), and
+// tests/test_gpu_bootstrap_stages.py compares the records the device stages of boot.hip leave (vslam_probe_homography_init,
+// vslam_probe_plane_aligner) with that host build, every integer and every double.
 #pragma once
 #include <math.h>
 #include "vslam_libm.h"
@@ -33,6 +36,22 @@ struct Match {                       // HomographyMatch, jni/HomographyInit.h: z
 };
 struct Decomposition {               // HomographyDecomposition
   double Rp[9], Tp[3], n[3], d; double R[9], t[3]; int score;
+};
+// What the two stages leave behind (boot.hip: boot_homography_stage / boot_plane_stage; oracle/bootmath_host.cpp restates them
+// serially).  A cleared record is all zero with best_trial = -1; what a stage does not reach stays cleared.
+struct HomographyStages {
+  int ok;                            // HomographyInit::Compute succeeded and the translation has a length
+  int best_trial;                    // the first minimum of the 300 MLESAC scores in trial order; -1 with fewer than ten matches
+  int n_inliers;
+  int choice;                        // ChooseBestDecomposition: 0 no ambiguity, 1 / 2 the first / second of the ambiguous pair by Sampson score
+  double H_mlesac[9], H_refined[9];
+  double R[9], t[3], n[3], d;        // the chosen decomposition
+  double t_scaled[3];                // t at the length wiggle_scale (jni/MapMaker.cc:243-250)
+};
+struct PlaneStages {
+  int have, best_trial;              // best_trial -1: every trial was skipped, the defaults below went into the aligner
+  double mean[3], normal[3];         // of the best trial (defaults: 0, (0, 0, 1))
+  double R[9], t[3];                 // the aligner
 };
 
 BM_FN unsigned bm_rand(unsigned seed, unsigned trial, unsigned draw) {   // 32-bit mix (splitmix-style finaliser), >> 1 like rand()'s range
@@ -263,8 +282,9 @@ BM_FN double sampsonus_error(const double dash[2], const double E[9], const doub
   return err * err / ((f[0] * f[0] + f[1] * f[1]) + (ft[0] * ft[0] + ft[1] * ft[1]));
 }
 
-// ChooseBestDecomposition, :405-499: visibility votes of the inliers, then the Sampson score of all matches for a tie.  Result in d[0].
-BM_FN void choose_best_decomposition(Decomposition d[8], const double H[9], const Match* m, int n, const int* inl, int ninl, double max_err2) {
+// ChooseBestDecomposition, :405-499: visibility votes of the inliers, then the Sampson score of all matches for a tie.  Result in d[0];
+// returns 0 when the votes left no ambiguity, else 1 / 2 for the member of the ambiguous pair the Sampson scores kept.
+BM_FN int choose_best_decomposition(Decomposition d[8], const double H[9], const Match* m, int n, const int* inl, int ninl, double max_err2) {
   for (int i = 0; i < 8; i++) {
     int pos = 0;
     for (int k = 0; k < ninl; k++) { const Match& q = m[inl[k]]; if ((H[6] * q.first[0] + H[7] * q.first[1] + H[8]) / d[i].d > 0.0) pos++; }
@@ -278,7 +298,7 @@ BM_FN void choose_best_decomposition(Decomposition d[8], const double H[9], cons
   }
   stable_sort_by_score(d, 4);
   const double ratio = (double)d[1].score / (double)d[0].score;
-  if (ratio < 0.9) return;                                           // no ambiguity, :447-448
+  if (ratio < 0.9) return 0;                                         // no ambiguity, :447-448
   const double limit = max_err2 * 4;
   double sc[2];
   for (int i = 0; i < 2; i++) {
@@ -291,7 +311,29 @@ BM_FN void choose_best_decomposition(Decomposition d[8], const double H[9], cons
     for (int k = 0; k < n; k++) { double e = sampsonus_error(m[k].second, E, m[k].first); if (e > limit) e = limit; sum += e; }
     sc[i] = sum;
   }
-  if (!(sc[0] <= sc[1])) d[0] = d[1];
+  if (sc[0] <= sc[1]) return 1;
+  d[0] = d[1];
+  return 2;
+}
+
+// HomographyInit::Compute from the inlier set on (:58-70) and InitFromStereo's scale (jni/MapMaker.cc:243-250): serial.  Hm: the
+// MLESAC (or direct) homography; inl: its inliers in match order; ws: ninl doubles.
+BM_FN void homography_finish(const double Hm[9], const Match* m, int n, const int* inl, int ninl, double max_err2, double wiggle_scale, double* ws, HomographyStages& o) {
+  double H[9];
+  for (int i = 0; i < 9; i++) { H[i] = Hm[i]; o.H_mlesac[i] = Hm[i]; }
+  o.n_inliers = ninl;
+  for (int it = 0; it < 5; it++) refine_homography(H, m, inl, ninl, ws);   // :58-59
+  for (int i = 0; i < 9; i++) o.H_refined[i] = H[i];
+  Decomposition d[8];
+  if (decompose_homography(H, d) != 8) return;                       // :62-66
+  o.choice = choose_best_decomposition(d, H, m, n, inl, ninl, max_err2);
+  for (int i = 0; i < 9; i++) o.R[i] = d[0].R[i];
+  for (int i = 0; i < 3; i++) { o.t[i] = d[0].t[i]; o.n[i] = d[0].n[i]; }
+  o.d = d[0].d;
+  const double mag = sqrt(o.t[0] * o.t[0] + o.t[1] * o.t[1] + o.t[2] * o.t[2]);
+  if (mag == 0) return;                                              // MapMaker.cc:243-248
+  for (int i = 0; i < 3; i++) o.t_scaled[i] = o.t[i] * (wiggle_scale / mag);   // :250
+  o.ok = 1;
 }
 
 // ---- MapMaker::CalcPlaneAligner, jni/MapMaker.cc:1104-1231 ------------------------------------------------------------------
@@ -385,6 +427,18 @@ BM_FN bool plane_aligner(const double* pos, int n, const double best_mean[3], co
     }
   }
   return true;
+}
+
+// CalcPlaneAligner from the 100 trial sums on: the first strict minimum among the trials that were not skipped (:1156-1162), that
+// trial's plane again, the aligner.
+BM_FN void plane_finish(const double* pos, int n, unsigned seed, const double* sums, PlaneStages& o) {
+  double best = 9999999999999999.9; int bt = -1;
+  for (int t = 0; t < 100; t++) if (!(sums[t] < 0.0) && sums[t] < best) { best = sums[t]; bt = t; }
+  double mean[3] = {0, 0, 0}, nrm[3] = {0, 0, 1};
+  if (bt >= 0) plane_trial(pos, n, seed, bt, mean, nrm);
+  o.best_trial = bt;
+  for (int k = 0; k < 3; k++) { o.mean[k] = mean[k]; o.normal[k] = nrm[k]; }
+  o.have = plane_aligner(pos, n, mean, nrm, o.R, o.t) ? 1 : 0;
 }
 
 }  // namespace bm
