@@ -100,6 +100,11 @@ void orc_sys_get_state(void* sv, orc_track_state* o) {
   o->ba_accepted = s->last_ba_accepted; o->n_zmssd = s->n_zmssd; o->n_ba_trials = s->n_ba_trials;
 }
 
+void orc_sys_get_window_counts(void* sv, long long out[3]) {
+  System* s = (System*)sv;
+  for (int i = 0; i < 3; i++) out[i] = s->n_win[i];
+}
+
 int orc_sys_get_point_tracks(void* sv, int* found, int* searched, int* level, int* subpix, double* vfound, double* image, int cap) {
   System* s = (System*)sv;
   const int n = (int)s->pts.size();

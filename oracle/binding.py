@@ -209,7 +209,7 @@ class OracleSystem:
         for f in ("orc_sys_destroy", "orc_sys_add_meas", "orc_sys_set_map_good", "orc_sys_set_pose", "orc_sys_set_velocity",
                   "orc_sys_track_frame", "orc_sys_get_state", "orc_sys_get_keyframe_pose", "orc_sys_frame_begin", "orc_sys_search_stage",
                   "orc_sys_pose_stage", "orc_sys_frame_end", "orc_sys_idle_iteration", "orc_sys_idle_job", "orc_sys_get_idle_stats",
-                  "orc_sys_press_spacebar", "orc_sys_set_last_keyframe_dropped", "orc_sys_set_boot_seed", "orc_sys_get_init_info"):
+                  "orc_sys_press_spacebar", "orc_sys_set_last_keyframe_dropped", "orc_sys_set_boot_seed", "orc_sys_get_init_info", "orc_sys_get_window_counts"):
             getattr(L, f).restype = None
         self.L = L
         self.p = params
@@ -310,6 +310,13 @@ class OracleSystem:
         out = np.zeros((cap, 3), np.int32)
         n = self.L.orc_sys_get_grow_log(self.h, _p(out), cap)
         return out[:n]
+
+    def window_counts(self):
+        """of this frame's patch searches so far: windows that reach the bottom row of their level, that hold no candidate corner, and
+        that hold a candidate closer than half a patch to a border (counted inside FindPatchCoarse)"""
+        o = np.zeros(3, np.int64)
+        self.L.orc_sys_get_window_counts(self.h, _p(o))
+        return dict(zip(("bottom", "empty", "border"), (int(x) for x in o)))
 
     def point_tracks(self):
         n = self.state().n_points

@@ -116,8 +116,10 @@ bool finder_find_coarse(Finder& f, const double irPosIn[2], const KeyFrame& kf, 
   const int nRight = (int)(irPos[0] + nRange);
   const int l = f.level, rows = kf.h[l];
   if (nTop < 0) nTop = 0;
-  if (nTop >= rows) return false;
-  if (nBottomPlusOne <= 0) return false;
+  if (nTop >= rows) { f.n_win[1]++; return false; }
+  if (nBottomPlusOne <= 0) { f.n_win[1]++; return false; }
+  if (nBottomPlusOne >= rows) f.n_win[0]++;
+  int nCandidates = 0; bool bBorderCandidate = false;   // statistics only
   int i = kf.lut[l][nTop];
   const int i_end = nBottomPlusOne >= rows ? (int)kf.corners[l].size() : kf.lut[l][nBottomPlusOne];
   int best_x = -1, best_y = -1;
@@ -129,8 +131,12 @@ bool finder_find_coarse(Finder& f, const double irPosIn[2], const KeyFrame& kf, 
     if (dx * dx + dy * dy > (double)(nRange * nRange)) continue;
     const int nSSD = finder_zmssd(f, kf.im[l].data(), kf.w[l], kf.h[l], kf.w[l], cx, cy);
     f.n_zmssd++;
+    nCandidates++;
+    if (!(cx >= f.P / 2 && cy >= f.P / 2 && cx < kf.w[l] - f.P / 2 && cy < kf.h[l] - f.P / 2)) bBorderCandidate = true;
     if (nSSD < nBestSSD) { best_x = cx; best_y = cy; nBestSSD = nSSD; }
   }
+  if (nCandidates == 0) f.n_win[1]++;
+  if (bBorderCandidate) f.n_win[2]++;
   if (nBestSSD < f.max_ssd) {
     f.coarse[0] = level_zero_pos(best_x, l); f.coarse[1] = level_zero_pos(best_y, l);
     f.found = true;

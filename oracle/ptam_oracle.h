@@ -148,6 +148,8 @@ void orc_sys_idle_iteration(void* sys);        /* one pass through the idle jobs
 void orc_sys_get_idle_stats(void* sys, int out[6]);   /* points re-found by ReFindNewlyMade / ReFindFromFailureQueue, BundleAdjustAll / idle BundleAdjustRecent calls, queue lengths */
 void orc_sys_get_state(void* sys, orc_track_state* out);
 /* per map point: found flag, searched flag, search level, did-subpix, found position (L0), projected position */
+/* this frame's search windows: reach the bottom row of their level / hold no candidate corner / hold a candidate closer than half a patch to a border */
+void orc_sys_get_window_counts(void* sys, long long out[3]);
 int orc_sys_get_point_tracks(void* sys, int* found, int* searched, int* level, int* subpix, double* vfound, double* image, int cap);
 int orc_sys_get_points(void* sys, double* pos3, int* bad, int* n_in, int* n_out, int cap);
 void orc_sys_get_keyframe_pose(void* sys, int kf, double pose12[12]);

@@ -47,6 +47,7 @@ struct Finder {
   bool have_last = false;     // mpLastTemplateMapPoint == &p
   double last_warp[4] = {9999.9, 0, 0, 9999.9};   // :23
   long n_zmssd = 0;           // statistics: ZMSSD evaluations (K of SURVEY 8(d))
+  long n_win[3] = {0, 0, 0};  // statistics: FindPatchCoarse windows that reach the bottom row / hold no candidate / hold a candidate no patch fits around
 };
 
 struct MapPoint {     // jni/MapPoint.h:22-69 + TrackerData (jni/TrackerData.h:36-66)
@@ -130,6 +131,7 @@ struct System {
   int attempted[4], found[4];
   bool kf_added_this_frame = false;
   long n_zmssd = 0, n_ba_trials = 0; int last_ba_accepted = -2;
+  long n_win[3] = {0, 0, 0};  // this frame's sums of Finder::n_win over SearchForPoints
   std::vector<int> iteration_set;
 
   explicit System(const Params& pp);

@@ -224,9 +224,10 @@ int System::SearchForPoints(std::vector<int>& vTD, int nRange, int nSubPixIts) {
     finder_make_template(F, TD, *kfs[TD.src_kf]);
     if (F.bad) { TD.in_image = TD.pot_visible = TD.found = false; continue; }
     attempted[F.level]++;
-    const long before = F.n_zmssd;
+    const long before = F.n_zmssd, win_before[3] = {F.n_win[0], F.n_win[1], F.n_win[2]};
     const bool bFound = finder_find_coarse(F, TD.image, cur, (unsigned)nRange);
     n_zmssd += F.n_zmssd - before;
+    for (int i = 0; i < 3; i++) n_win[i] += F.n_win[i] - win_before[i];
     TD.searched = true;
     if (!bFound) { TD.found = false; continue; }
     TD.found = true;
@@ -288,10 +289,14 @@ void System::TrackMap() {
 void System::SearchStage(int stage) {
   if (stage == 0) {
     for (int i = 0; i < 4; i++) attempted[i] = found[i] = 0;
+    for (int i = 0; i < 3; i++) n_win[i] = 0;
     for (int l = 0; l < 4; l++) tm_pvs[l].clear();
     std::vector<int>* avPVS = tm_pvs;
     for (size_t i = 0; i < pts.size(); i++) {         // :369-392
       MapPoint& TD = *pts[i];
+      // PTAM leaves nSearchLevel (and bSearched, bFound) of a point outside this frame's PVS stale; the level is reset here for
+      // reporting only (orc_sys_get_point_tracks: -1 = not in the PVS).  Nothing below reads it for such a point.
+      TD.search_level = -1;
       if (TD.bad) continue;                           // bad points live in the trash list (jni/Map.cc:16-27)
       Camera::Proj pr; bool projected;
       td_project(TD, pose, camera, pr, projected);
