@@ -174,10 +174,13 @@ class Tracker {
  public:
   // bBootstrap: no map is uploaded, the tracker makes its own like the reference's (spacebar, spacebar: jni/Tracker.cc:247-288), and the
   // map-maker grows it on every keyframe (AddKeyFrameFromTopOfQueue, jni/MapMaker.cc:481-506)
-  Tracker(int width, int heigth, const ATANCamera& c, Map& m, MapMaker& mm, bool bBootstrap = false) : mMap(m), mMapMaker(mm) {   // jni/Tracker.cc:16-40
+  // nPVSShuffleSeed: TrackMap's random_shuffle of the potentially visible set (jni/Tracker.cc:396-397, 525) as the seeded permutation of
+  // vslam_params.pvs_shuffle_seed; 0 keeps map order
+  Tracker(int width, int heigth, const ATANCamera& c, Map& m, MapMaker& mm, bool bBootstrap = false, unsigned nPVSShuffleSeed = 0) : mMap(m), mMapMaker(mm) {   // jni/Tracker.cc:16-40
     vslam_params p;
     vslam_detail::check(vslam_default_params(&p, width, heigth, 1));
     if (bBootstrap) { p.bootstrap = 1; p.grow_map = 3; }
+    p.pvs_shuffle_seed = nPVSShuffleSeed;
     for (int i = 0; i < 5; i++) p.cam[i] = c.params[i];
     vslam_detail::check(vslam_create(&p, &mMap.sys));
     mCurrentKF.sys = mMap.sys;

@@ -105,6 +105,12 @@ typedef struct vslam_params {
                                       stays lost, no kernel is launched and nothing is allocated for it */
   double reloc_blur;               /* jni/SmallBlurryImage.h:19-20 dBlur of the relocaliser's images: 2.5.  <= 2: 9 x 9 Gaussian, > 2: 17 x 17
                                       (jni/SmallBlurryImage.cc:51-54) */
+  unsigned pvs_shuffle_seed;       /* jni/Tracker.cc:396-397,525: TrackMap shuffles every level's list of the potentially visible set before the coarse
+                                      selection, and the list of the remaining points before it cuts it to max_patches_per_frame, so that a map
+                                      larger than the cap is measured all over and not at the head of its lists.  The reference draws from rand();
+                                      here the order is the seeded permutation of csrc/pvs_perm.h, a function of (seed, frame, list, length).
+                                      0 (default): the identity order, map order.  Non-zero: every stream starts with this seed
+                                      (vslam_set_pvs_seed changes one stream's) */
 } vslam_params;
 
 const char* vslam_last_error(void);
@@ -339,6 +345,23 @@ int vslam_init_from_stereo(vslam_system* sys, const uint8_t* gray_first, const u
                            const int* matches_xyxy, double pose12_out[12]);
 /* the seed that stands in for the reference's rand() state in HomographyInit's MLESAC and CalcPlaneAligner's RANSAC (default 1) */
 int vslam_set_boot_seed(vslam_system* sys, int stream, unsigned seed);
+
+/* ---- the shuffle of the potentially visible set (vslam_params.pvs_shuffle_seed; jni/Tracker.cc:396-397, 525) ----
+ * The seed of one stream, or of every stream (stream < 0), from its next frame on; 0 gives that stream the identity order.  VSLAM_E_STATE on a
+ * system created with pvs_shuffle_seed = 0: it runs the planning kernel that has no shuffle.  vslam_reset_streams puts a stream's seed back
+ * to the value of vslam_params. */
+int vslam_set_pvs_seed(vslam_system* sys, int stream, unsigned seed);
+/* vIterationSet of the stream's current frame, in order, as far as it is planned: after vslam_patch_search(sys, 0) the coarse set, after
+ * vslam_patch_search(sys, 1) and after the frame also the level-3 points and the rest (jni/Tracker.cc:465, 507, 536-539).  iter_idx receives
+ * map-point indices, at most cap; counts (may be NULL) = coarse entries, level-3 fine entries, other fine entries, total.  Returns the total.
+ * Synchronises. */
+int vslam_get_search_plan(vslam_system* sys, int stream, int* iter_idx, int cap, int counts[4]);
+/* The permutation of csrc/pvs_perm.h on its own: out[j] = the position of the identity order that lands at j, for a list of n entries
+ * (0..4096, else VSLAM_E_INVALID) with list = 0..3 for a level and 4 for the remaining points.  keys_or_null (n values) takes the place
+ * of the generated keys: equal keys keep the identity order.  on_host != 0: the header's host form, no GPU needed; otherwise the device
+ * routine the planning kernel calls, on one workgroup.  Both must return the same list. */
+int vslam_pvs_permutation(unsigned seed, int frame, int list, int n, const unsigned* keys_or_null, int* out, int on_host);
+
 /* out[0..5] = mnInitialStage (0 not started, 1 trails running, 2 complete), trails alive, InitFromStereo succeeded, homography inliers,
  * map points made from the stereo pair, map good */
 int vslam_get_init_info(vslam_system* sys, int stream, int out[6]);

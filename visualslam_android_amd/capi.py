@@ -33,7 +33,7 @@ class Params(C.Structure):
         ("ba_min_tukey_sigma", C.c_double), ("ba_window", C.c_int), ("ba_min_keyframes", C.c_int),
         ("cam", C.c_double * 5), ("quirks", C.c_int), ("device", C.c_int), ("ba_delay_frames", C.c_int),
         ("grow_map", C.c_int), ("ba_batch_frames", C.c_int), ("idle_iterations", C.c_int), ("bootstrap", C.c_int), ("ba_sum_order", C.c_int),
-        ("relocalise", C.c_int), ("reloc_blur", C.c_double),
+        ("relocalise", C.c_int), ("reloc_blur", C.c_double), ("pvs_shuffle_seed", C.c_uint),
     ]
 
 
@@ -132,6 +132,9 @@ SYMBOLS = {
     "vslam_init_from_stereo": (_i, [_sys, _vp, _vp, _sz, _i, _vp, _vp]),
     "vslam_set_boot_seed": (_i, [_sys, _i, C.c_uint]),
     "vslam_get_init_info": (_i, [_sys, _i, _vp]),
+    "vslam_set_pvs_seed": (_i, [_sys, _i, C.c_uint]),
+    "vslam_get_search_plan": (_i, [_sys, _i, _vp, _i, _vp]),
+    "vslam_pvs_permutation": (_i, [C.c_uint, _i, _i, _i, _vp, _vp, _i]),
     "vslam_get_trails": (_i, [_sys, _i, _vp, _i, _vp]),
     "vslam_probe_homography_init": (_i, [_sys, _i, _i, _vp, _vp, C.c_uint, _d, _vp]),
     "vslam_probe_plane_aligner": (_i, [_sys, _i, _i, _vp, C.c_uint, _vp]),
@@ -241,6 +244,16 @@ def eval_transcendental(name, x, on_host=False):
     y = np.zeros_like(x)
     _check(load_library().vslam_eval_transcendental(TRANSCENDENTALS.index(name), len(x), x.ctypes.data, y.ctypes.data, int(on_host)))
     return y
+
+
+def pvs_permutation(seed, frame, lst, n, keys=None, on_host=False):
+    """csrc/pvs_perm.h: the order in which a list of n entries is taken -> int32 [n], out[j] = the identity-order position that lands at j
+    (vslam_pvs_permutation; keys replaces the generated keys)"""
+    out = np.zeros(max(n, 0), np.int32)
+    k = None if keys is None else np.ascontiguousarray(keys, np.uint32)
+    assert k is None or len(k) == n
+    _check(load_library().vslam_pvs_permutation(seed, frame, lst, n, None if k is None else k.ctypes.data, out.ctypes.data, int(on_host)))
+    return out
 
 
 class System:
@@ -552,6 +565,17 @@ class System:
 
     def set_boot_seed(self, stream, seed):
         _check(self.lib.vslam_set_boot_seed(self.h, stream, seed))
+
+    def set_pvs_seed(self, stream, seed):
+        """the seed of the stream's PVS shuffle (stream < 0: every stream's); 0 = identity order (vslam_set_pvs_seed)"""
+        _check(self.lib.vslam_set_pvs_seed(self.h, stream, seed))
+
+    def search_plan(self, stream):
+        """-> (vIterationSet as planned so far, int32 map-point indices in order; {coarse, level3, other, total}) (vslam_get_search_plan)"""
+        idx = np.zeros(self.params.max_points, np.int32)
+        c = np.zeros(4, np.int32)
+        n = _check(self.lib.vslam_get_search_plan(self.h, stream, idx.ctypes.data, len(idx), c.ctypes.data))
+        return idx[:n].copy(), dict(zip(("coarse", "level3", "other", "total"), (int(x) for x in c)))
 
     def init_info(self, stream):
         o = np.zeros(6, np.int32)

@@ -182,7 +182,7 @@ extern "C" int vslam_map_set_good(vslam_system* sys, int s) {
 }
 
 static void reset_tracker_fields(TrackerState& st) {   // Tracker::Reset, jni/Tracker.cc:45-62 (first call for a stream)
-  if (st.frame == 0 && st.last_kf_dropped == 0 && st.depth_mean == 0.0) tracker_reset_fields(st);
+  if (st.frame == 0 && st.last_kf_dropped == 0 && st.depth_mean == 0.0) tracker_reset_fields(st, st.pvs_seed);
 }
 
 extern "C" int vslam_set_pose(vslam_system* sys, int s, const double pose12[12]) {
@@ -224,7 +224,7 @@ extern "C" int vslam_set_last_keyframe_dropped(vslam_system* sys, int s, int fra
 int map_init_states(vslam_system* sys) {
   std::vector<TrackerState> v(sys->S);
   memset(v.data(), 0, sizeof(TrackerState) * sys->S);
-  for (auto& st : v) tracker_reset_fields(st);
+  for (auto& st : v) tracker_reset_fields(st, sys->p.pvs_shuffle_seed);
   HIPCHK(hipMemcpy(sys->map.st, v.data(), sizeof(TrackerState) * sys->S, hipMemcpyHostToDevice));
   return VSLAM_OK;
 }

@@ -3,7 +3,8 @@
 // read-back and every frame tracked on it after a new map give the bits a new system gives; the other streams are not touched.
 //
 // What a new system holds zeroed and a later reader may read before anything rewrites it is cleared here, and nothing else:
-//   TrackerState                  whole, = tracker_reset_state() (the one statement of Tracker::Reset's and MapMaker::Reset's members)
+//   TrackerState                  whole, = tracker_reset_state() (the one statement of Tracker::Reset's and MapMaker::Reset's members; the
+//                                 boot seed 1 and the PVS shuffle seed of vslam_params with them)
 //   kf_meas [< n_kf][< n_points]  a keyframe the tracker adds writes its row only up to the points of that moment, a point the host
 //                                 uploads later relies on zeros above it (24 bytes per cell: only the part that was used)
 //   cur_meas [< n_points]         vslam_add_keyframe before the stream's first tracked frame copies it
@@ -58,13 +59,13 @@ __global__ __launch_bounds__(RESET_THREADS) void k_reset_clear(MapDev m, TrackPa
 }
 
 // one lane per stream: what the reset dropped, then the state of a new system's stream
-__global__ void k_reset_state(MapDev m, int S, const unsigned char* flags, int* info, unsigned char* sbi_restart) {
+__global__ void k_reset_state(MapDev m, int S, const unsigned char* flags, int* info, unsigned char* sbi_restart, unsigned pvs_seed) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S || !flags[s]) return;
   TrackerState* st = &m.st[s];
   int* o = info + 4 * (size_t)s;
   o[0]++; o[1] = st->frame; o[2] = st->n_kf; o[3] = st->n_points;
-  *st = tracker_reset_state();
+  *st = tracker_reset_state(pvs_seed);
   if (sbi_restart) sbi_restart[s] = 1;
 }
 
@@ -113,7 +114,7 @@ extern "C" int vslam_reset_streams(vslam_system* sys, const int* streams, int n)
   HIPCHK(hipEventRecord(sys->ev_reset_stage[q], sys->stream));
   int r = ba_reset_streams(sys, sys->reset_flags); if (r) return r;
   hipLaunchKernelGGL(k_reset_clear, dim3(RESET_BLOCKS, sys->S), dim3(RESET_THREADS), 0, sys->stream, sys->map, sys->tp, sys->reset_flags, sys->reloc.info);
-  hipLaunchKernelGGL(k_reset_state, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->S, sys->reset_flags, sys->reset_info, sys->sbi_restart);
+  hipLaunchKernelGGL(k_reset_state, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->S, sys->reset_flags, sys->reset_info, sys->sbi_restart, sys->p.pvs_shuffle_seed);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(sys->ev_reset_t[1], sys->stream));
   // whatever the other streams of the system launch from now on comes after the reset

@@ -53,6 +53,7 @@ extern "C" int vslam_default_params(vslam_params* p, int width, int height, int 
   p->ba_sum_order = 0;
   p->relocalise = 0;
   p->reloc_blur = 2.5;                                  // jni/SmallBlurryImage.h:19-20
+  p->pvs_shuffle_seed = 0;                              // identity order (jni/Tracker.cc:396-397, 525 shuffle with rand())
   return VSLAM_OK;
 }
 

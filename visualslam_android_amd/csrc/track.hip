@@ -4,8 +4,10 @@
 //   k_motion   ApplyMotionModel (:781-798), one lane per stream
 //   k_pvs      per map point TrackerData::Project / GetDerivsUnsafe
 //              (jni/TrackerData.h:69-95) + PatchFinder::CalcSearchLevelAndWarpMatrix (jni/PatchFinder.cc:31-68)
-//   k_plan     potentially-visible-set lists per level in map order (the reference's random_shuffle is the
-//              identity permutation here), coarse-stage selection (:399-461) / fine-stage selection (:493-535)
+//   k_plan     potentially-visible-set lists per level in map order, the reference's random_shuffle of them (:396-397, :525) as the
+//              seeded permutation of pvs_perm.h -- k_plan<true>, sorted in LDS; a system created with pvs_shuffle_seed = 0 launches
+//              k_plan<false>, the identity, which holds no sort buffer --, coarse-stage selection (:399-461) / fine-stage
+//              selection (:493-535)
 //   k_searchN  4 (11x11) or 8 (8x8) patches per wavefront, one lane per template row: warped template
 //              (MakeTemplateCoarseCont, transform_image), ZMSSD at the FAST corners of the row-LUT window
 //              (FindPatchCoarse/ZMSSDAtPoint) with packed-byte dot products and group shuffles
@@ -19,9 +21,11 @@
 // Transcendentals come from vslam_libm.h (one source for this file and the oracle); nothing here may be contracted into FMAs.
 #include "vslam_internal.h"
 #include "patch_dev.h"
+#include "pvs_perm.h"
 
 #define TRK_THREADS 256
 #define SORT_CAP 4096
+static_assert(SORT_CAP == PVS_SORT_CAP, "a level's list (at most max_points entries) fits the permutation's sort buffer");
 
 // ---------------------------------------------------------------------------------------------------------------
 // TrackerData::Project (jni/TrackerData.h:69-87).  Returns true when Cam.Project ran (pr valid).
@@ -156,7 +160,31 @@ __global__ __launch_bounds__(TRK_THREADS) VSLAM_PVS_ATTR void k_pvs(MapDev m, Tr
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+DEVFN int* pvs_chopped() { __shared__ int flag; return &flag; }                      // stage 1 of k_plan<true>: the remaining list is shuffled
+DEVFN uint64_t* pvs_sortbuf() { __shared__ uint64_t buf[SORT_CAP]; return buf; }   // the one sort buffer of a workgroup of k_plan<true>
+// random_shuffle(list) (jni/Tracker.cc:396-397) as pvs_perm.h's permutation, in place: list[j] = the entry whose identity-order
+// position lands at j.  All threads of the workgroup; n is uniform.
+DEVFN void pvs_shuffle_list(uint64_t* buf, int* list, int n, uint64_t h, int L) {
+  if (n < 2) return;
+  pvs_block_fill<TRK_THREADS>(buf, n, h, L, nullptr);
+  pvs_block_sort<TRK_THREADS>(buf, n);
+  for (int j = threadIdx.x; j < n; j += TRK_THREADS) buf[j] = (uint64_t)(uint32_t)list[(uint32_t)buf[j]];
+  __syncthreads();
+  for (int j = threadIdx.x; j < n; j += TRK_THREADS) list[j] = (int)(uint32_t)buf[j];
+  __syncthreads();
+}
+
+// The four level lists of a stream (:396-397).  A function of its own (not inlined), like pose_accumulate: with the four sorts inlined
+// into k_plan's first stage the register allocator reserves scratch memory for the kernel.
+__device__ __attribute__((noinline)) void pvs_shuffle_levels(int* pvs, int P, const int* cnt, unsigned seed, int frame) {
+  const uint64_t h = pvs_frame_hash(seed, frame);
+  for (int l = 0; l < NLEV; l++) pvs_shuffle_list(pvs_sortbuf(), pvs + l * P, cnt[l], h, l);
+}
+
 // stage 0: PVS lists + coarse selection; stage 1: fine selection (after the coarse pose update).
+// SHUFFLE: the lists are shuffled with the stream's seed (TrackerState::pvs_seed; 0 = this stream keeps the identity); the sort
+// buffer exists in that form only.
+template <bool SHUFFLE>
 __global__ __launch_bounds__(TRK_THREADS) void k_plan(MapDev m, TrackParams tp, int stage) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
@@ -170,7 +198,7 @@ __global__ __launch_bounds__(TRK_THREADS) void k_plan(MapDev m, TrackParams tp, 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __shared__ int cnt[NLEV];
   __shared__ int wcnt[TRK_THREADS / 64][NLEV];
-  __shared__ int plan[8];
+  __shared__ int plan[4];
   if (stage == 0) {
     if (threadIdx.x < NLEV) cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -207,6 +235,10 @@ __global__ __launch_bounds__(TRK_THREADS) void k_plan(MapDev m, TrackParams tp, 
       __syncthreads();
       if (threadIdx.x < NLEV) { int t = cnt[threadIdx.x]; for (int w = 0; w < TRK_THREADS / 64; w++) t += wcnt[w][threadIdx.x]; cnt[threadIdx.x] = t; }
       __syncthreads();
+    }
+    if constexpr (SHUFFLE) {                                         // :396-397: the selection below then works on the shuffled lists
+      const unsigned seed = st->pvs_seed;
+      if (seed) pvs_shuffle_levels(pvs, P, cnt, seed, st->frame);
     }
     if (threadIdx.x == 0) {
       for (int l = 0; l < NLEV; l++) { st->pvs_count[l] = cnt[l]; st->pvs_head[l] = 0; }
@@ -248,7 +280,8 @@ __global__ __launch_bounds__(TRK_THREADS) void k_plan(MapDev m, TrackParams tp, 
       int nother = (st->pvs_count[2] - st->pvs_head[2]) + st->pvs_count[1] + st->pvs_count[0];
       int nFine = tp.max_patches - (nit + n3);                       // :519-521
       if (nFine < 0) nFine = 0;
-      if (nother > nFine) nother = nFine;                            // :522-526 (identity shuffle, then chop)
+      if constexpr (SHUFFLE) *pvs_chopped() = nother > nFine && nFine > 0 && st->pvs_seed != 0;   // :523-525: shuffled only when it is chopped
+      if (nother > nFine) nother = nFine;                            // :522-526 (shuffle, then chop)
       plan[0] = nit; plan[1] = n3; plan[2] = nother;
       st->fine_range = st->did_coarse ? 5 : 10;                      // :495-497
       st->n_l3 = n3; st->n_search = n3 + nother; st->n_iter = nit + n3 + nother;
@@ -258,11 +291,22 @@ __global__ __launch_bounds__(TRK_THREADS) void k_plan(MapDev m, TrackParams tp, 
     const int h3 = st->pvs_head[3], h2 = st->pvs_head[2];
     const int r2 = st->pvs_count[2] - h2, r1 = st->pvs_count[1];
     const int did_coarse = st->did_coarse;
+    const uint64_t* rest_order = nullptr;                            // SHUFFLE: the :525 order of the remaining list, when it is chopped
+    if constexpr (SHUFFLE) {
+      uint64_t* sortbuf = pvs_sortbuf();
+      if (*pvs_chopped()) {
+        const int nrest = r2 + r1 + st->pvs_count[0];
+        pvs_block_fill<TRK_THREADS>(sortbuf, nrest, pvs_frame_hash(st->pvs_seed, st->frame), PVS_LIST_REST, nullptr);
+        pvs_block_sort<TRK_THREADS>(sortbuf, nrest);
+        rest_order = sortbuf;
+      }
+    }
     for (int e = threadIdx.x; e < n3 + nother; e += TRK_THREADS) {
       int idx, its;
       if (e < n3) { idx = pvs[3 * P + h3 + e]; its = tp.fine_subpix_its; }
       else {
-        const int k = e - n3;                                        // order: level 2, 1, 0 (:512-514)
+        int k = e - n3;                                              // order: level 2, 1, 0 (:512-514)
+        if constexpr (SHUFFLE) if (rest_order) k = (int)(uint32_t)rest_order[k];
         if (k < r2) idx = pvs[2 * P + h2 + k];
         else if (k < r2 + r1) idx = pvs[1 * P + (k - r2)];
         else idx = pvs[0 * P + (k - r2 - r1)];
@@ -1168,6 +1212,10 @@ static void trk_search_args(vslam_system* sys, SearchArgs& a) {
   a.ncorners = sys->fr.ncorners;
 }
 
+// a system created with pvs_shuffle_seed = 0 has the identity form of k_plan, whatever is asked of it later (vslam_set_pvs_seed refuses)
+typedef void (*PlanKernel)(MapDev, TrackParams, int);
+static PlanKernel plan_kernel(const vslam_system* sys) { return sys->p.pvs_shuffle_seed ? k_plan<true> : k_plan<false>; }
+
 // One search stage of TrackMap on the current frame.  stage 0: ApplyMotionModel + the potentially visible set (:369-392),
 // coarse selection (:399-461) and SearchForPoints of the coarse set; stage 1: fine selection (:493-535) and SearchForPoints of
 // the level-3 points (with sub-pixel refinement) and of the rest.
@@ -1183,7 +1231,7 @@ int trk_search_stage(vslam_system* sys, int stage) {
     hipLaunchKernelGGL(k_motion, dim3((S + 63) / 64), dim3(64), 0, sys->stream, m, S, sys->p.use_sbi ? (const double*)sys->fr.sbi_rot : (const double*)nullptr);
     hipLaunchKernelGGL(k_pvs, dim3((P + TRK_THREADS - 1) / TRK_THREADS, S), dim3(TRK_THREADS), 0, sys->stream, m, tp);
     prof_mark(sys, 4);
-    hipLaunchKernelGGL(k_plan, dim3(S), dim3(TRK_THREADS), 0, sys->stream, m, tp, 0);
+    hipLaunchKernelGGL(plan_kernel(sys), dim3(S), dim3(TRK_THREADS), 0, sys->stream, m, tp, 0);
     prof_mark(sys, 5);
     if (!tp.coarse_disabled || sys->p.relocalise) {                  // a recovered frame has a coarse stage whatever the switch says (:432-433)
       const int nc = 2 * tp.coarse_max;
@@ -1199,7 +1247,7 @@ int trk_search_stage(vslam_system* sys, int stage) {
   } else {
     const int maxSearch = tp.max_patches + 2 * tp.coarse_max < P ? tp.max_patches + 2 * tp.coarse_max : P;
     prof_mark(sys, 7);
-    hipLaunchKernelGGL(k_plan, dim3(S), dim3(TRK_THREADS), 0, sys->stream, m, tp, 1);
+    hipLaunchKernelGGL(plan_kernel(sys), dim3(S), dim3(TRK_THREADS), 0, sys->stream, m, tp, 1);
     prof_mark(sys, 8);
     if (tp.P == 8) {
       a.nblk = (maxSearch + 7) / 8; hipLaunchKernelGGL((k_searchN<8, 8>), dim3(xcd_grid(a.nblk, S)), dim3(64), 0, sys->stream, m, tp, a, 1);
@@ -1229,4 +1277,64 @@ int trk_track_map(vslam_system* sys) {
   if (!r) r = trk_search_stage(sys, 1);
   if (!r) r = trk_pose_stage(sys, 1);
   return r;
+}
+
+// ---- the PVS permutation's entry points (include/vslam_c.h) ---------------------------------------------------------------------
+__global__ void k_set_pvs_seed(MapDev m, int S, int stream, unsigned seed) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S || (stream >= 0 && s != stream)) return;
+  m.st[s].pvs_seed = seed;
+}
+
+extern "C" int vslam_set_pvs_seed(vslam_system* sys, int stream, unsigned seed) {
+  if (!sys || stream >= sys->S) { vslam_set_error("set_pvs_seed: bad argument"); return VSLAM_E_INVALID; }
+  if (!sys->p.pvs_shuffle_seed) { vslam_set_error("set_pvs_seed: created with pvs_shuffle_seed = 0 (the identity form of the planning kernel)"); return VSLAM_E_STATE; }
+  hipLaunchKernelGGL(k_set_pvs_seed, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->S, stream, seed);
+  HIPCHK(hipGetLastError());
+  return VSLAM_OK;
+}
+
+extern "C" int vslam_get_search_plan(vslam_system* sys, int stream, int* iter_idx, int cap, int counts[4]) {
+  if (!sys || stream < 0 || stream >= sys->S || cap < 0 || (cap > 0 && !iter_idx)) { vslam_set_error("get_search_plan: bad argument"); return VSLAM_E_INVALID; }
+  TrackerState st;
+  HIPCHK(hipStreamSynchronize(sys->stream));
+  HIPCHK(hipMemcpy(&st, sys->map.st + stream, sizeof(st), hipMemcpyDeviceToHost));
+  int n = st.n_iter < 0 ? 0 : st.n_iter;
+  if (n > sys->p.max_points) n = sys->p.max_points;
+  if (counts) { counts[0] = st.n_coarse; counts[1] = st.n_l3; counts[2] = n - st.n_coarse - st.n_l3; counts[3] = n; }
+  const int ncopy = n < cap ? n : cap;
+  if (ncopy > 0) HIPCHK(hipMemcpy(iter_idx, sys->map.iter_list + (size_t)stream * sys->p.max_points, sizeof(int) * (size_t)ncopy, hipMemcpyDeviceToHost));
+  return n;
+}
+
+// the device routine of k_plan<true> on its own: one workgroup, the same fill and sort, out[j] = the position that lands at j
+__global__ __launch_bounds__(TRK_THREADS) void k_pvs_permutation(unsigned seed, int frame, int list, int n, const unsigned* keys, int* out) {
+  __shared__ uint64_t sortbuf[SORT_CAP];
+  pvs_block_fill<TRK_THREADS>(sortbuf, n, pvs_frame_hash(seed, frame), list, keys);
+  pvs_block_sort<TRK_THREADS>(sortbuf, n);
+  for (int j = threadIdx.x; j < n; j += TRK_THREADS) out[j] = (int)(uint32_t)sortbuf[j];
+}
+
+extern "C" int vslam_pvs_permutation(unsigned seed, int frame, int list, int n, const unsigned* keys_or_null, int* out, int on_host) {
+  if (n < 0 || n > PVS_SORT_CAP || list < 0 || list > PVS_LIST_REST || (n > 0 && !out)) { vslam_set_error("pvs_permutation: n 0..%d, list 0..%d", PVS_SORT_CAP, PVS_LIST_REST); return VSLAM_E_INVALID; }
+  if (on_host) { pvs_permutation_host(seed, frame, list, n, keys_or_null, out); return VSLAM_OK; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { vslam_set_error("pvs_permutation: no HIP device visible"); return VSLAM_E_HIP; }
+  if (n == 0) return VSLAM_OK;
+  unsigned* dk = nullptr; int* dout = nullptr;
+  auto run = [&]() -> int {
+    HIPCHK(hipMalloc((void**)&dout, sizeof(int) * n));
+    if (keys_or_null) {
+      HIPCHK(hipMalloc((void**)&dk, sizeof(unsigned) * n));
+      HIPCHK(hipMemcpy(dk, keys_or_null, sizeof(unsigned) * n, hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(k_pvs_permutation, dim3(1), dim3(TRK_THREADS), 0, 0, seed, frame, list, n, (const unsigned*)dk, dout);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(out, dout, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return VSLAM_OK;
+  };
+  const int rc = run();
+  if (dk) (void)hipFree(dk);
+  if (dout) (void)hipFree(dout);
+  return rc;
 }

@@ -120,19 +120,20 @@ struct TrackerState {       // Tracker members, jni/Tracker.h:77-150 (+ MapMaker
   unsigned boot_seed;       // stands in for the reference's rand() state
   int boot_host_matches;    // vslam_init_from_stereo: the trails are the caller's matches; this frame's TrailTracking_Advance does not search
   int recovered_now;        // vslam_params.relocalise: AttemptRecovery succeeded in this frame (jni/Tracker.cc:133-139), cleared at the frame's end
+  unsigned pvs_seed;        // seed of the PVS shuffle (pvs_perm.h; jni/Tracker.cc:396-397, 525); 0: this stream keeps the identity order
 };
 // Tracker::Reset (jni/Tracker.cc:45-62) and MapMaker::Reset (jni/MapMaker.cc:60-74) on a zeroed TrackerState: the members that do not
 // start at zero.  The only statement of them: a new system's streams (map_init_states) and a reset stream (k_reset_state) both hold
-// tracker_reset_state().
-HDFN void tracker_reset_fields(TrackerState& st) {
-  st.boot_seed = 1u;
+// tracker_reset_state(); pvs_seed is vslam_params.pvs_shuffle_seed.
+HDFN void tracker_reset_fields(TrackerState& st, unsigned pvs_seed) {
+  st.boot_seed = 1u; st.pvs_seed = pvs_seed;
   st.quality = 2; st.last_kf_dropped = -20; st.depth_mean = 1.0; st.depth_sigma = 1.0;       // jni/Tracker.cc:50-60
   st.ba_accepted = -2; st.ba_countdown = -1;
   st.ba_converged_recent = 1; st.ba_converged_full = 1;                                     // jni/MapMaker.cc:72-73
   for (int i = 0; i < 9; i++) st.pose_final.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
   st.pose_cur = st.pose_final; st.start_pose = st.pose_final;
 }
-HDFN TrackerState tracker_reset_state() { TrackerState st = {}; tracker_reset_fields(st); return st; }
+HDFN TrackerState tracker_reset_state(unsigned pvs_seed) { TrackerState st = {}; tracker_reset_fields(st, pvs_seed); return st; }
 // jni/Tracker.cc:103-104 and :135-136: TrackMap runs for a stream that is not lost, or that the relocaliser has just recovered
 DEVFN bool trk_runs_track_map(const TrackerState* st) { return st->map_good && (st->lost_frames < 3 || st->recovered_now); }
 
