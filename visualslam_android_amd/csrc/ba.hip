@@ -449,13 +449,13 @@ DEVFN double kfdist(const Pose& a, const Pose& b) {   // KeyFrameLinearDist :705
   return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
 }
 
-// mode 0: after AddKeyFrame (only streams with kf_pending) -> BundleAdjustRecent; 1: BundleAdjustRecent on every
-// stream; 2: BundleAdjustAll on every stream.  Two kernels build the Bundle problem of BundleAdjust (:854-902) in the pool:
+// The job (BaJob, vslam_internal.h) says which streams are adjusted and whether all their keyframes or the window around the
+// newest one.  Two kernels build the Bundle problem of BundleAdjust (:854-902) in the pool:
 // k_ba_select (one lane per stream, on the tracker's stream) takes the decisions that the next frame's tracking must see --
 // the keyframe joins the map (n_kf), which cameras are adjusted (:803-820), the countdown of the asynchronous map-maker --
 // and k_ba_assemble does the long part (point set, fixed set, measurement list), which with the asynchronous map-maker runs
 // on the map-maker's stream beside the following frames: nothing it reads changes while the stream's adjustment is pending.
-__global__ __launch_bounds__(64) void k_ba_select(MapDev m, TrackParams tp, BaPool pool, int mode, int token) {
+__global__ __launch_bounds__(64) void k_ba_select(MapDev m, TrackParams tp, BaPool pool, BaJob job, int token) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= pool.N) return;
   TrackerState* st = &m.st[s];
@@ -468,19 +468,14 @@ __global__ __launch_bounds__(64) void k_ba_select(MapDev m, TrackParams tp, BaPo
   int go = 0, nadj_out = 0;
   const bool in_flight = st->ba_countdown > 0;     // asynchronous map-maker: the pool still belongs to the last keyframe
   if (!in_flight) R->active = 0;
-  if (mode == 0 && st->kf_pending) {
+  if (job == BaJob::Keyframe && st->kf_pending) {
     st->n_kf++;                                                       // mMap.vpKeyFrames.push_back (:489)
     st->kf_added = 1;
     st->ba_converged_full = 0; st->ba_converged_recent = 0;           // :504-505
   }
-  bool want = st->map_good && (mode != 0 || st->kf_pending) && !in_flight;
-  if (mode == 5 || mode == 6) want = want && st->boot_run;                                  // InitFromStereo's BundleAdjustAll calls, jni/MapMaker.cc:344-345, 361-365
-  if (mode == 6) want = want && !st->ba_converged_full;
-  if (mode == 3) want = want && !st->ba_converged_recent;                                   // MapMaker::run :97-98
-  if (mode == 4) want = want && st->ba_converged_recent && !st->ba_converged_full;          // :107-108
-  const bool all = mode == 2 || mode == 4 || mode == 5 || mode == 6;
-  if (want && mode == 3) st->n_ba_recent_idle++;
-  if (want && mode == 4) st->n_ba_all++;
+  const bool want = st->map_good && !in_flight && ba_job_gate(job, *st);
+  const bool all = ba_job_all(job);
+  if (want) if (int* n = ba_job_idle_counter(job, st)) ++*n;
   const int nk = st->n_kf;
   if (want) for (int k = 0; k < BA_MAX_KF; k++) view_of_kf[k] = -1;
   if (want && !all) {
@@ -516,10 +511,10 @@ __global__ __launch_bounds__(64) void k_ba_select(MapDev m, TrackParams tp, BaPo
   // stream and may start after this launch (of a LATER frame).  `go` carries the token of the ba_run call that wants the problem,
   // so an assemble launched for another call never picks it up.
   if (!in_flight) { R->go = go ? token : 0; R->nadj = nadj_out; }
-  if (go && mode == 0 && tp.ba_delay > 0) st->ba_countdown = tp.ba_delay;   // results are applied ba_delay frames from now
+  if (go && job == BaJob::Keyframe && tp.ba_delay > 0) st->ba_countdown = tp.ba_delay;   // results are applied ba_delay frames from now
 }
 
-__global__ __launch_bounds__(BA_THREADS) void k_ba_assemble(MapDev m, TrackParams tp, BaPool pool, int mode, int slot /* work list to enter, or -1 */, int token) {
+__global__ __launch_bounds__(BA_THREADS) void k_ba_assemble(MapDev m, TrackParams tp, BaPool pool, bool all /* every keyframe (BundleAdjustAll) or the window */, int slot /* work list to enter, or -1 */, int token) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
   const BaView v = ba_view(pool, s);
@@ -546,7 +541,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_assemble(MapDev m, TrackParam
     const int i = i0 + threadIdx.x;
     bool in = false;
     if (i < npts) {
-      if (mode == 2) in = !pts[i].bad;
+      if (all) in = !pts[i].bad;
       else for (int k = 0; k < nk && !in; k++) if (view_of_kf[k] >= 0 && kfm[(size_t)k * P + i].valid) in = true;
     }
     const unsigned long long bm = __ballot(in);
@@ -566,7 +561,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_assemble(MapDev m, TrackParam
   const int np = base;
   const int* pid_of = (const int*)v.scratch;
   // ---- fixed set (:834-848): other keyframes measuring any point of the set; appended in keyframe order ----
-  if (mode != 2) {
+  if (!all) {
     for (int k = 0; k < nk; k++) {
       if (view_of_kf[k] >= 0) continue;
       int any = 0;
@@ -579,7 +574,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_assemble(MapDev m, TrackParam
   if (threadIdx.x == 0) {
     int c = nadj;
     for (int k = 0; k < nk; k++) {
-      const bool fixed_member = mode == 2 ? (kff[k] != 0) : (view_of_kf[k] < 0 && kf_cnt[k]);
+      const bool fixed_member = all ? (kff[k] != 0) : (view_of_kf[k] < 0 && kf_cnt[k]);
       if (fixed_member && c < pool.max_cams) { view_of_kf[k] = c; v.cam_fixed[c] = 1; v.cam_pose[c] = kfp[k]; pool.id_view[(size_t)s * pool.max_cams + c] = k; c++; }
     }
     sh_nc = c;
@@ -634,8 +629,17 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_assemble(MapDev m, TrackParam
   }
 }
 
-// BundleAdjust tail (:904-959) + HandleBadPoints (:140-164)
-__global__ __launch_bounds__(BA_THREADS) void k_ba_writeback(MapDev m, TrackParams tp, BaPool pool, int mode) {
+// HandleBadPoints (:140-164) of one stream, by its whole workgroup
+DEVFN void handle_bad_points(const TrackerState* st, MapPointDev* pts, MeasDev* kfm, int P) {
+  const int nk = st->n_kf;
+  for (int i = threadIdx.x; i < st->n_points; i += BA_THREADS) {
+    if (pts[i].n_out > 20 && pts[i].n_out > pts[i].n_in) pts[i].bad = 1;
+    if (pts[i].bad) for (int k = 0; k < nk; k++) kfm[(size_t)k * P + i].valid = 0;
+  }
+}
+
+// BundleAdjust tail (:904-959) + HandleBadPoints
+__global__ __launch_bounds__(BA_THREADS) void k_ba_writeback(MapDev m, TrackParams tp, BaPool pool, BaWriteback wb) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
   const BaView v = ba_view(pool, s);
@@ -644,17 +648,18 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_writeback(MapDev m, TrackPara
   MapPointDev* pts = m.pts + (size_t)s * P;
   MeasDev* kfm = m.kf_meas + (size_t)s * K * P;
   __shared__ int sh_due;
-  if (mode == 5) { if (!st->boot_run) return; mode = 2; }   // InitFromStereo's adjustments: only the streams it runs for
-  if (mode >= 3) {                         // asynchronous map-maker: is this stream's pending result due?
+  if (wb == BaWriteback::Boot && !st->boot_run) return;   // InitFromStereo's adjustments: only the streams it runs for
+  const bool all = wb == BaWriteback::All || wb == BaWriteback::Boot;
+  if (wb == BaWriteback::IfDue || wb == BaWriteback::Drain) {   // asynchronous map-maker: is this stream's pending result due?
     if (threadIdx.x == 0) {
       int due = 0;
-      if (st->ba_countdown > 0) { if (mode == 4) st->ba_countdown = 1; if (--st->ba_countdown == 0) { due = 1; st->ba_countdown = -1; } }
+      if (st->ba_countdown > 0) { if (wb == BaWriteback::Drain) st->ba_countdown = 1; if (--st->ba_countdown == 0) { due = 1; st->ba_countdown = -1; } }
       sh_due = due;
     }
     __syncthreads();
     if (!sh_due) return;
   }
-  const bool deferred = mode == 0 && tp.ba_delay > 0;   // the results of this keyframe's BA are written back ba_delay frames later
+  const bool deferred = wb == BaWriteback::Keyframe && tp.ba_delay > 0;   // the results of this keyframe's BA are written back ba_delay frames later
   if (R->active && !deferred) {
     const int* idp = pool.id_point + (size_t)s * pool.max_pts;
     const int* idv = pool.id_view + (size_t)s * pool.max_cams;
@@ -705,35 +710,25 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_writeback(MapDev m, TrackPara
       st->ba_accepted = acc;
       st->n_ba_trials += (unsigned long long)R->trials;
       if (acc >= 0) {
-        if (acc > 0) { if (mode != 2) st->ba_converged_recent = 0; st->ba_converged_full = 0; }
-        if (R->converged) { st->ba_converged_recent = 1; if (mode == 2) st->ba_converged_full = 1; }   // :931-935
+        if (acc > 0) { if (!all) st->ba_converged_recent = 0; st->ba_converged_full = 0; }
+        if (R->converged) { st->ba_converged_recent = 1; if (all) st->ba_converged_full = 1; }   // :931-935
       }
       R->active = 0;
     }
     __syncthreads();
   }
-  if (!(st->map_good && (mode != 0 || st->kf_pending))) return;
-  if (mode == 0 && tp.ba_delay > 0 && st->ba_countdown > 0) return;   // deferred: HandleBadPoints runs with the delayed write-back
-  // HandleBadPoints :140-164
-  const int nk = st->n_kf;
-  for (int i = threadIdx.x; i < st->n_points; i += BA_THREADS) {
-    if (pts[i].n_out > 20 && pts[i].n_out > pts[i].n_in) pts[i].bad = 1;
-    if (pts[i].bad) for (int k = 0; k < nk; k++) kfm[(size_t)k * P + i].valid = 0;
-  }
+  if (!(st->map_good && (wb != BaWriteback::Keyframe || st->kf_pending))) return;
+  if (deferred && st->ba_countdown > 0) return;   // HandleBadPoints runs with the delayed write-back
+  handle_bad_points(st, pts, kfm, P);
 }
 
-// HandleBadPoints (:140-164) on its own: MapMaker::run :117 calls it after every pass through the idle jobs
+// HandleBadPoints on its own: MapMaker::run :117 calls it after every pass through the idle jobs
 __global__ __launch_bounds__(BA_THREADS) void k_handle_bad_points(MapDev m, TrackParams tp) {
   const int s = blockIdx.x;
   const TrackerState* st = &m.st[s];
   if (!st->map_good) return;
-  const int P = tp.max_points, K = tp.max_keyframes, nk = st->n_kf;
-  MapPointDev* pts = m.pts + (size_t)s * P;
-  MeasDev* kfm = m.kf_meas + (size_t)s * K * P;
-  for (int i = threadIdx.x; i < st->n_points; i += BA_THREADS) {
-    if (pts[i].n_out > 20 && pts[i].n_out > pts[i].n_in) pts[i].bad = 1;
-    if (pts[i].bad) for (int k = 0; k < nk; k++) kfm[(size_t)k * P + i].valid = 0;
-  }
+  const int P = tp.max_points, K = tp.max_keyframes;
+  handle_bad_points(st, m.pts + (size_t)s * P, m.kf_meas + (size_t)s * K * P, P);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
@@ -788,7 +783,7 @@ static int ba_launch_batch(vslam_system* sys) {
   sys->ba_stream = sys->ba_streams[(size_t)(sys->ba_batch_id % (long)sys->ba_streams.size())];
   int lrec = -1, lord = 0;
   { int rr = ba_next_launch_record(sys, sys->ba_stream, &lrec, &lord); if (rr) return rr; }
-  prof_mark(sys, 12);                                  // the batch's assemblies precede on this very stream
+  prof_mark(sys, PROF_BA_COMPUTE);                     // the batch's assemblies precede on this very stream
   // one workgroup per problem up to two per compute unit; the grid walks the batch's work list
   const int cap = 2 * (sys->n_cu > 0 ? sys->n_cu : 256);
   const int ba_grid = sys->S < cap ? sys->S : cap;
@@ -809,7 +804,7 @@ int ba_frame_start(vslam_system* sys) {
   if (D <= 0) return VSLAM_OK;
   BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
   const int R = (int)sys->ev_ba.size(), FB = (int)sys->frame_batch.size();
-  prof_mark(sys, 13);
+  prof_mark(sys, PROF_BA_WRITEBACK);
   if (sys->frame_no >= D) {
     const long b = sys->frame_batch[(size_t)((sys->frame_no - D) % FB)];
     if (b >= 0) {
@@ -817,7 +812,7 @@ int ba_frame_start(vslam_system* sys) {
       HIPCHK(hipStreamWaitEvent(sys->stream, sys->ev_ba[(size_t)(b % R)], 0));
     }
   }
-  hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, sys->tp, ws->pool, 3);
+  hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, sys->tp, ws->pool, BaWriteback::IfDue);
   HIPCHK(hipGetLastError());
   return VSLAM_OK;
 }
@@ -864,95 +859,100 @@ static int ba_drain(vslam_system* sys) {
   if (sys->tp.ba_delay <= 0) return VSLAM_OK;
   BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
   { int rs = ba_sync_streams(sys); if (rs) return rs; }
-  hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, sys->tp, ws->pool, 4);
+  hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, sys->tp, ws->pool, BaWriteback::Drain);
   HIPCHK(hipGetLastError());
   return VSLAM_OK;
 }
 
-// mode 0: tracker-driven AddKeyFrame + BundleAdjustRecent; 1: BundleAdjustRecent; 2: BundleAdjustAll; 3 / 4: the same two as idle jobs of
-// MapMaker::run, for the streams whose adjustment has not converged (gated on device)
-int ba_run(vslam_system* sys, int mode, bool host_driven_keyframe) {
-  const int base = mode == 3 ? 1 : (mode == 4 || mode >= 5 ? 2 : mode);   // what the assembly does; 5 / 6: InitFromStereo's BundleAdjustAll (boot.hip)
-  const int wb = mode >= 5 ? 5 : base;                                    // ... and the write-back
+// The AddKeyFrame prologue for the streams with kf_pending: the keyframe, its SmallBlurryImage (MakeKeyFrame_Rest, jni/KeyFrame.cc:97-100;
+// vslam_params.relocalise) and, with `grow`, AddSomeMapPoints (vslam_params.grow_map) before the bundle adjustment sees the keyframe
+static int ba_add_keyframe_prologue(vslam_system* sys, bool grow) {
+  KfCopyArgs a; fill_kfcopy(sys, a);
+  hipLaunchKernelGGL(k_add_keyframe, dim3(32, sys->S), dim3(256), 0, sys->stream, sys->map, sys->tp, a);
+  HIPCHK(hipGetLastError());
+  { int rs = reloc_keyframe_sbi_pending(sys); if (rs) return rs; }
+  return grow ? grow_on_keyframe(sys) : VSLAM_OK;
+}
+
+int ba_launch_add_keyframe(vslam_system* sys) { return ba_add_keyframe_prologue(sys, false); }
+
+// The tracker's keyframes with the asynchronous map-maker (ba_delay > 0):
+// Bundle::Compute on a map-maker stream, beside the next frames; its write-back is launched by ba_frame_start D frames later.
+// The keyframe frames of independent sequences do not coincide, so a frame brings only a few problems, and an adjustment
+// outlasts a frame (one persistent workgroup per problem, latency-bound): the problems of ba_batch consecutive frames are
+// collected in one work list and launched together; successive launches go to a ring of streams and may overlap.
+// A launch walks exactly its batch's list -- never a problem a later frame's k_ba_assemble is writing beside it.
+static int ba_adjust_keyframe_async(vslam_system* sys, int token) {
   BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
-  const BaConfig cfg = make_cfg(sys->tp);
-  const bool async = mode == 0 && sys->tp.ba_delay > 0 && !host_driven_keyframe;
-  const int token = (int)(++sys->ba_token & 0x3fffffff) + 1;   // names this call's problems (k_ba_select -> k_ba_assemble)
-  if (mode == 1 || mode == 2) { int r = ba_drain(sys); if (r) return r; }
-  if (mode == 0) {
-    KfCopyArgs a; fill_kfcopy(sys, a);
-    prof_mark(sys, 10);
-    hipLaunchKernelGGL(k_add_keyframe, dim3(32, sys->S), dim3(256), 0, sys->stream, sys->map, sys->tp, a);
-    { int rs = reloc_keyframe_sbi_pending(sys); if (rs) return rs; }   // MakeKeyFrame_Rest's SmallBlurryImage (jni/KeyFrame.cc:97-100; vslam_params.relocalise)
-    int rg = grow_on_keyframe(sys);                      // AddSomeMapPoints (vslam_params.grow_map), before the bundle adjustment sees the keyframe
-    if (rg) return rg;
-  }
-  if (mode == 0) prof_mark(sys, 11);
-  if (async) {
-    // Bundle::Compute on a map-maker stream, beside the next frames; its write-back is launched by ba_frame_start D frames later.
-    // The keyframe frames of independent sequences do not coincide, so a frame brings only a few problems, and an adjustment
-    // outlasts a frame (one persistent workgroup per problem, latency-bound): the problems of ba_batch consecutive frames are
-    // collected in one work list and launched together; successive launches go to a ring of streams and may overlap.
-    // A launch walks exactly its batch's list -- never a problem a later frame's k_ba_assemble is writing beside it.
-    const int R = (int)sys->ev_ba.size(), slot = (int)(sys->ba_batch_id % R);
-    hipStream_t bs = sys->ba_streams[(size_t)(sys->ba_batch_id % (long)sys->ba_streams.size())];
-    hipLaunchKernelGGL(k_ba_select, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->tp, ws->pool, mode, token);
-    // the long part of the assembly leaves the tracker's stream: behind this frame's keyframe copy / map growth, on the batch's
-    // map-maker stream (every frame of a batch uses the same stream, so the batch's launch follows all its assemblies)
-    const int FBn = (int)sys->frame_batch.size(), es = (int)(sys->frame_no % FBn);
-    HIPCHK(hipEventRecord(sys->ev_asm[es], sys->stream));
-    HIPCHK(hipStreamWaitEvent(bs, sys->ev_asm[es], 0));
-    if (sys->ba_batch_fill == 0)
-      HIPCHK(hipMemsetAsync(ws->pool.work_n + slot, 0, sizeof(int), bs));   // the launch that read this slot R batches ago was waited for (ba_frame_start)
-    if (sys->ba_batch_fill == 0) HIPCHK(hipMemsetAsync(ws->pool.work_n + ws->pool.work_slots + slot, 0, sizeof(int), bs));
-    hipLaunchKernelGGL(k_ba_assemble, dim3(sys->S), dim3(BA_THREADS), 0, bs, sys->map, sys->tp, ws->pool, mode, slot, token);
-    sys->frame_batch[(size_t)(sys->frame_no % (long)sys->frame_batch.size())] = sys->ba_batch_id;
-    sys->ba_batch_fill++;
-    if (sys->ba_batch_fill >= sys->tp.ba_batch) { int rl = ba_launch_batch(sys); if (rl) return rl; }
-    hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, sys->tp, ws->pool, 0);   // HandleBadPoints of streams without a pending BA
-    HIPCHK(hipGetLastError());
-    return VSLAM_OK;
-  }
-  // host-driven calls (BundleAdjustRecent / BundleAdjustAll / AddKeyFrame on request): HIP events around the three parts, read by
-  // vslam_get_mapmaker_timing.  A host-driven AddKeyFrame is adjusted here and now even when the tracker-driven ones run on the
-  // map-maker streams (the pending ones were collected by the caller): the kernels see ba_delay = 0.
-  const bool timed = (mode == 1 || mode == 2 || host_driven_keyframe) && sys->ev_mm[0];
+  const int R = (int)sys->ev_ba.size(), slot = (int)(sys->ba_batch_id % R);
+  hipStream_t bs = sys->ba_streams[(size_t)(sys->ba_batch_id % (long)sys->ba_streams.size())];
+  hipLaunchKernelGGL(k_ba_select, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->tp, ws->pool, BaJob::Keyframe, token);
+  // the long part of the assembly leaves the tracker's stream: behind this frame's keyframe copy / map growth, on the batch's
+  // map-maker stream (every frame of a batch uses the same stream, so the batch's launch follows all its assemblies)
+  const int FBn = (int)sys->frame_batch.size(), es = (int)(sys->frame_no % FBn);
+  HIPCHK(hipEventRecord(sys->ev_asm[es], sys->stream));
+  HIPCHK(hipStreamWaitEvent(bs, sys->ev_asm[es], 0));
+  if (sys->ba_batch_fill == 0)
+    HIPCHK(hipMemsetAsync(ws->pool.work_n + slot, 0, sizeof(int), bs));   // the launch that read this slot R batches ago was waited for (ba_frame_start)
+  if (sys->ba_batch_fill == 0) HIPCHK(hipMemsetAsync(ws->pool.work_n + ws->pool.work_slots + slot, 0, sizeof(int), bs));
+  hipLaunchKernelGGL(k_ba_assemble, dim3(sys->S), dim3(BA_THREADS), 0, bs, sys->map, sys->tp, ws->pool, ba_job_all(BaJob::Keyframe), slot, token);
+  sys->frame_batch[(size_t)(sys->frame_no % (long)sys->frame_batch.size())] = sys->ba_batch_id;
+  sys->ba_batch_fill++;
+  if (sys->ba_batch_fill >= sys->tp.ba_batch) { int rl = ba_launch_batch(sys); if (rl) return rl; }
+  hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, sys->tp, ws->pool, BaWriteback::Keyframe);   // HandleBadPoints of streams without a pending BA
+  HIPCHK(hipGetLastError());
+  return VSLAM_OK;
+}
+
+// Every other job is adjusted here and now, on the system's stream.  Host-driven calls (BundleAdjustRecent / BundleAdjustAll /
+// AddKeyFrame on request): HIP events around the three parts, read by vslam_get_mapmaker_timing.  A host-driven AddKeyFrame is
+// adjusted here and now even when the tracker-driven ones run on the map-maker streams (the pending ones were collected by the
+// caller): the kernels see ba_delay = 0.
+static int ba_adjust_now(vslam_system* sys, BaJob job, bool host_driven_keyframe, int token) {
+  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  const bool keyframe = job == BaJob::Keyframe;          // part of a frame: its stages are profiled
+  const bool timed = (ba_job_on_request(job) || host_driven_keyframe) && sys->ev_mm[0];
   TrackParams tps = sys->tp;
   if (host_driven_keyframe) tps.ba_delay = 0;
   int lrec = -1, lord = 0;
   { int rr = ba_next_launch_record(sys, sys->stream, &lrec, &lord); if (rr) return rr; }
   if (timed) HIPCHK(hipEventRecord(sys->ev_mm[0], sys->stream));
-  hipLaunchKernelGGL(k_ba_select, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, tps, ws->pool, mode, token);
-  hipLaunchKernelGGL(k_ba_assemble, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, tps, ws->pool, base, -1, token);
-  if (mode == 0) prof_mark(sys, 12);
+  hipLaunchKernelGGL(k_ba_select, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, tps, ws->pool, job, token);
+  hipLaunchKernelGGL(k_ba_assemble, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, tps, ws->pool, ba_job_all(job), -1, token);
+  if (keyframe) prof_mark(sys, PROF_BA_COMPUTE);
   if (timed) HIPCHK(hipEventRecord(sys->ev_mm[1], sys->stream));
-  ba_launch_compute(ws->pool, cfg, sys->S, sys->stream, -1, lrec);
-  if (mode == 0) prof_mark(sys, 13);
+  ba_launch_compute(ws->pool, make_cfg(sys->tp), sys->S, sys->stream, -1, lrec);
+  if (keyframe) prof_mark(sys, PROF_BA_WRITEBACK);
   if (timed) HIPCHK(hipEventRecord(sys->ev_mm[2], sys->stream));
-  hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, tps, ws->pool, wb);
+  hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, tps, ws->pool, ba_job_writeback(job));
   if (timed) { HIPCHK(hipEventRecord(sys->ev_mm[3], sys->stream)); sys->mm_lrec = lrec; }
-  if (mode == 0 && sys->prof_on && sys->prof_frame < sys->prof_cap && sys->prof_frame < (int)sys->prof_ba_launched.size()) sys->prof_ba_launched[sys->prof_frame] = lord + 1;
+  if (keyframe && sys->prof_on && sys->prof_frame < sys->prof_cap && sys->prof_frame < (int)sys->prof_ba_launched.size()) sys->prof_ba_launched[sys->prof_frame] = lord + 1;
   HIPCHK(hipGetLastError());
   return VSLAM_OK;
 }
 
-int ba_launch_add_keyframe(vslam_system* sys) {
-  KfCopyArgs a; fill_kfcopy(sys, a);
-  hipLaunchKernelGGL(k_add_keyframe, dim3(32, sys->S), dim3(256), 0, sys->stream, sys->map, sys->tp, a);
-  HIPCHK(hipGetLastError());
-  return reloc_keyframe_sbi_pending(sys);
+int ba_run(vslam_system* sys, BaJob job, bool host_driven_keyframe) {
+  const int token = (int)(++sys->ba_token & 0x3fffffff) + 1;   // names this call's problems (k_ba_select -> k_ba_assemble)
+  if (ba_job_on_request(job)) { int r = ba_drain(sys); if (r) return r; }
+  if (job == BaJob::Keyframe) {
+    prof_mark(sys, PROF_ADD_KEYFRAME);
+    { int r = ba_add_keyframe_prologue(sys, true); if (r) return r; }
+    prof_mark(sys, PROF_BA_ASSEMBLE);
+    if (sys->tp.ba_delay > 0 && !host_driven_keyframe) return ba_adjust_keyframe_async(sys, token);
+  }
+  return ba_adjust_now(sys, job, host_driven_keyframe, token);
 }
 
-int ba_add_keyframe_and_adjust(vslam_system* sys) { return ba_run(sys, 0, false); }
+int ba_add_keyframe_and_adjust(vslam_system* sys) { return ba_run(sys, BaJob::Keyframe, false); }
 
 // vslam_params.idle_iterations passes through the idle jobs of MapMaker::run (jni/MapMaker.cc:94-117), every stream deciding on
 // device which of them it runs: BundleAdjustRecent until converged, ReFindNewlyMade, BundleAdjustAll until converged, every 20th
 // time ReFindFromFailureQueue, HandleBadPoints (the tail of the write-back kernels).  Synchronous map-maker only.
 int mm_idle_job(vslam_system* sys, int job) {
-  if (job < 0 || job > 3) { vslam_set_error("mapmaker_idle_job: job must be 0..3"); return VSLAM_E_INVALID; }
-  if (job == 0) return ba_run(sys, 3, false);                 // the write-back ends with HandleBadPoints
-  if (job == 2) return ba_run(sys, 4, false);
-  const int r = grow_idle_refind(sys, job == 1 ? 0 : 1);
+  if (job < 0 || job >= IDLE_N_JOBS) { vslam_set_error("mapmaker_idle_job: job must be 0..3"); return VSLAM_E_INVALID; }
+  if (job == IDLE_BA_RECENT) return ba_run(sys, BaJob::IdleRecent);   // the write-back ends with HandleBadPoints
+  if (job == IDLE_BA_ALL) return ba_run(sys, BaJob::IdleAll);
+  const int r = grow_idle_refind(sys, job == IDLE_REFIND_NEW ? REFIND_NEWLY_MADE : REFIND_FAILURE_QUEUE);
   if (r) return r;
   hipLaunchKernelGGL(k_handle_bad_points, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, sys->tp);   // :117
   HIPCHK(hipGetLastError());
@@ -960,7 +960,7 @@ int mm_idle_job(vslam_system* sys, int job) {
 }
 int mm_idle(vslam_system* sys) {
   for (int it = 0; it < sys->p.idle_iterations; it++)
-    for (int job = 0; job < 4; job++) { const int r = mm_idle_job(sys, job); if (r) return r; }
+    for (int job = 0; job < IDLE_N_JOBS; job++) { const int r = mm_idle_job(sys, job); if (r) return r; }
   return VSLAM_OK;
 }
 
@@ -1049,5 +1049,5 @@ extern "C" int vslam_add_keyframe(vslam_system* sys, int stream) {
   if (!sys->have_frame) { vslam_set_error("add_keyframe: no current frame"); return VSLAM_E_STATE; }
   { int r = ba_drain(sys); if (r) return r; }        // asynchronous map-maker: collect the adjustments in flight first
   hipLaunchKernelGGL(k_request_keyframe, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->tp, sys->S, stream);
-  return ba_run(sys, 0, true);
+  return ba_run(sys, BaJob::Keyframe, true);
 }

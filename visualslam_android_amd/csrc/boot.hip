@@ -604,13 +604,13 @@ int boot_frame(vslam_system* sys) {
     if (sys->tp.P == 8) hipLaunchKernelGGL(k_boot_points<8>, dim3(S), dim3(BOOT_THREADS), 0, q, sys->map, sys->tp, a);
     else hipLaunchKernelGGL(k_boot_points<11>, dim3(S), dim3(BOOT_THREADS), 0, q, sys->map, sys->tp, a);
     hipLaunchKernelGGL(k_boot_phase, gs, bs, 0, q, sys->map, S, 1);
-    for (int i = 0; i < 5; i++) if ((r = ba_run(sys, 5))) return r;  // :344-345
+    for (int i = 0; i < 5; i++) if ((r = ba_run(sys, BaJob::BootAll))) return r;  // :344-345
     hipLaunchKernelGGL(k_boot_scene_depth, dim3(S), dim3(64), 0, q, sys->map, sys->tp);
     hipLaunchKernelGGL(k_boot_phase, gs, bs, 0, q, sys->map, S, 2);
     const int order[NLEV] = {0, 3, 1, 2};                            // :353-356
     if ((r = grow_levels(sys, order, NLEV))) return r;
     hipLaunchKernelGGL(k_boot_phase, gs, bs, 0, q, sys->map, S, 3);
-    for (int i = 0; i < 50; i++) if ((r = ba_run(sys, 6))) return r; // while (!mbBundleConverged_Full) BundleAdjustAll(), :361-365 (bounded)
+    for (int i = 0; i < 50; i++) if ((r = ba_run(sys, BaJob::BootAllUntilConverged))) return r; // while (!mbBundleConverged_Full) BundleAdjustAll(), :361-365 (bounded)
     hipLaunchKernelGGL(k_boot_plane, dim3(S), dim3(BOOT_THREADS), 0, q, sys->map, sys->tp);
   }
   HIPCHK(hipGetLastError());

@@ -798,9 +798,9 @@ static void fe_launch_slide(vslam_system* sys, FeArgs& a, hipStream_t fs, int S)
   q.wg_first[0] = 0; q.wg_first[1] = 0;
   for (int l = 1; l < NLEV; l++) q.wg_first[l + 1] = q.wg_first[l] + nwg[l];
   size_t lds123 = lds[1]; if (lds[2] > lds123) lds123 = lds[2]; if (lds[3] > lds123) lds123 = lds[3];
-  prof_mark(sys, 0);
+  prof_mark(sys, PROF_PYR_FAST0);
   hipLaunchKernelGGL(k_fast_slide<true>, dim3(nwg[0]), dim3(SL_THREADS), lds[0], fs, a, q);
-  prof_mark(sys, 1);
+  prof_mark(sys, PROF_FAST_LVL);
   hipLaunchKernelGGL(k_fast_slide<false>, dim3(q.wg_first[NLEV]), dim3(SL_THREADS), lds123, fs, a, q);
 }
 
@@ -823,12 +823,12 @@ static int fe_launch_bands(vslam_system* sys, FeArgs& a, hipStream_t stream, int
   int r = fe_band_lds((const void*)k_pyr_fast0, lds0);
   if (!r) r = fe_band_lds((const void*)k_fast_lvl, lds1);
   if (r) return r;
-  if (marks) prof_mark(sys, 0);
+  if (marks) prof_mark(sys, PROF_PYR_FAST0);
   hipLaunchKernelGGL(k_pyr_fast0, dim3((g[0].h + BAND - 1) / BAND, S), dim3(FE_THREADS), lds0, stream, a, lp0, lp1, lp2);
   int nb = 0;
   a.band_first[0] = 0;
   for (int l = 1; l < NLEV; l++) { a.band_first[l] = nb; nb += (g[l].h + BAND - 1) / BAND; }
-  if (marks) prof_mark(sys, 1);
+  if (marks) prof_mark(sys, PROF_FAST_LVL);
   hipLaunchKernelGGL(k_fast_lvl, dim3(nb, S), dim3(FE_THREADS), lds1, stream, a);
   return VSLAM_OK;
 }
@@ -864,7 +864,7 @@ int fe_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_str
 
   if (fe_slide_ok(sys, a)) fe_launch_slide(sys, a, fs, sys->S);
   else { const int r = fe_launch_bands(sys, a, fs, sys->S, true); if (r) return r; }
-  prof_mark(sys, 2);
+  prof_mark(sys, PROF_COMPACT);
   {
     static const int cb = getenv("VSLAM_COMPACT_BAND") ? atoi(getenv("VSLAM_COMPACT_BAND")) : 32;   // rows of a level per workgroup of the compaction (measured alone, 1024 frames: 16 rows 96 us, 32: 62, 64: 96, 128: 78, 256: 156)
     hipLaunchKernelGGL(k_compact, dim3((g[0].h + cb - 1) / cb, NLEV, sys->S), dim3(COMPACT_THREADS), 0, fs, a, cb);

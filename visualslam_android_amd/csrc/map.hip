@@ -261,7 +261,7 @@ extern "C" int vslam_finish_frame(vslam_system* sys) {
   int r = ba_add_keyframe_and_adjust(sys);                                             // :128-132 -> MapMaker::AddKeyFrame
   if (!r && sys->p.idle_iterations > 0) r = mm_idle(sys);                              // the map-maker's idle jobs
   if (!r && sys->p.bootstrap) r = boot_frame(sys);                                     // jni/Tracker.cc:144-145: TrackForInitialMap for the streams without a map
-  prof_mark(sys, VSLAM_N_STAGES);
+  prof_mark(sys, PROF_FRAME_END);
   if (sys->prof_on && sys->prof_frame < sys->prof_cap) sys->prof_frame++;
   if (!r) HIPCHK(hipEventRecord(sys->ev_track_done[sys->fr_idx], sys->stream));       // the front-end may now reuse this buffer
   sys->frame_no++;
@@ -310,8 +310,9 @@ extern "C" int vslam_map_set_keyframe_pose(vslam_system* sys, int s, int keyfram
   return VSLAM_OK;
 }
 
-static const char* kStageNames[VSLAM_N_STAGES] = {"pyr_fast0", "fast_lvl", "compact", "pvs", "plan_coarse", "search_coarse", "pose_coarse",
+static const char* kStageNames[] = {"pyr_fast0", "fast_lvl", "compact", "pvs", "plan_coarse", "search_coarse", "pose_coarse",
                                                   "plan_fine", "search_fine", "pose_fine", "add_keyframe", "ba_assemble", "ba_compute", "ba_writeback"};
+static_assert(sizeof(kStageNames) / sizeof(kStageNames[0]) == PROF_FRAME_END, "one name per ProfStage, in its order");
 extern "C" const char* vslam_stage_name(int stage) { return stage >= 0 && stage < VSLAM_N_STAGES ? kStageNames[stage] : ""; }
 
 extern "C" int vslam_profile_begin(vslam_system* sys, int max_frames) {
@@ -333,9 +334,11 @@ extern "C" int vslam_profile_end(vslam_system* sys, double* stage_ms, int* n_fra
   for (int f = 0; f < sys->prof_frame; f++)
     for (int k = 0; k < VSLAM_N_STAGES; k++) {
       float ms = 0.f;
-      int end = k == 2 ? PROF_FE_END : k + 1;   // stages 0..2 run on the front-end stream
-      if (sys->tp.ba_delay > 0) { if (k == 11) end = VSLAM_N_STAGES; else if (k == 12) end = PROF_BA_END; else if (k == 13) end = 3; }
-      if (sys->tp.ba_delay > 0 && k == 12 && !(f < (int)sys->prof_ba_launched.size() && sys->prof_ba_launched[f])) continue;   // no launch in this frame
+      int end = k == PROF_COMPACT ? PROF_FE_END : k + 1;   // the stages up to PROF_COMPACT run on the front-end stream
+      // asynchronous map-maker: the assembly lasts to the end of the frame, Bundle::Compute runs on a map-maker stream, and the
+      // write-back of the results that are due opens the frame, before the tracker
+      if (sys->tp.ba_delay > 0) { if (k == PROF_BA_ASSEMBLE) end = PROF_FRAME_END; else if (k == PROF_BA_COMPUTE) end = PROF_BA_END; else if (k == PROF_BA_WRITEBACK) end = PROF_PVS; }
+      if (sys->tp.ba_delay > 0 && k == PROF_BA_COMPUTE && !(f < (int)sys->prof_ba_launched.size() && sys->prof_ba_launched[f])) continue;   // no launch in this frame
       HIPCHK(hipEventElapsedTime(&ms, sys->prof_ev[(size_t)f * PROF_MARKS + k], sys->prof_ev[(size_t)f * PROF_MARKS + end]));
       stage_ms[k] += ms;
     }
@@ -349,7 +352,7 @@ extern "C" int vslam_profile_launches(vslam_system* sys, int* launches) {
   if (sys->tp.ba_delay > 0) {
     int n = 0;
     for (int f = 0; f < sys->prof_frame && f < (int)sys->prof_ba_launched.size(); f++) n += sys->prof_ba_launched[f] ? 1 : 0;
-    launches[12] = n;
+    launches[PROF_BA_COMPUTE] = n;
   }
   return VSLAM_OK;
 }
@@ -367,8 +370,8 @@ extern "C" int vslam_touch(vslam_system* sys) {
   return sys->p.bootstrap ? vslam_press_spacebar(sys, -1) : VSLAM_OK;
 }
 
-extern "C" int vslam_bundle_adjust_recent(vslam_system* sys) { if (!sys) return VSLAM_E_INVALID; return ba_run(sys, 1); }
-extern "C" int vslam_bundle_adjust_all(vslam_system* sys) { if (!sys) return VSLAM_E_INVALID; return ba_run(sys, 2); }
+extern "C" int vslam_bundle_adjust_recent(vslam_system* sys) { if (!sys) return VSLAM_E_INVALID; return ba_run(sys, BaJob::Recent); }
+extern "C" int vslam_bundle_adjust_all(vslam_system* sys) { if (!sys) return VSLAM_E_INVALID; return ba_run(sys, BaJob::All); }
 
 // ---- read-back ------------------------------------------------------------------------------------------------------
 static void export_state(const vslam_system* sys, const TrackerState& st, vslam_track_state* o);

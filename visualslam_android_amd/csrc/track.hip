@@ -1227,12 +1227,12 @@ int trk_search_stage(vslam_system* sys, int stage) {
   trk_search_args(sys, a);
   a.S = S; a.nblk = 1;
   if (stage == 0) {
-    prof_mark(sys, 3);
+    prof_mark(sys, PROF_PVS);
     hipLaunchKernelGGL(k_motion, dim3((S + 63) / 64), dim3(64), 0, sys->stream, m, S, sys->p.use_sbi ? (const double*)sys->fr.sbi_rot : (const double*)nullptr);
     hipLaunchKernelGGL(k_pvs, dim3((P + TRK_THREADS - 1) / TRK_THREADS, S), dim3(TRK_THREADS), 0, sys->stream, m, tp);
-    prof_mark(sys, 4);
+    prof_mark(sys, PROF_PLAN_COARSE);
     hipLaunchKernelGGL(plan_kernel(sys), dim3(S), dim3(TRK_THREADS), 0, sys->stream, m, tp, 0);
-    prof_mark(sys, 5);
+    prof_mark(sys, PROF_SEARCH_COARSE);
     if (!tp.coarse_disabled || sys->p.relocalise) {                  // a recovered frame has a coarse stage whatever the switch says (:432-433)
       const int nc = 2 * tp.coarse_max;
       if (tp.P == 8) {
@@ -1243,12 +1243,12 @@ int trk_search_stage(vslam_system* sys, int stage) {
         if (tp.coarse_subpix_its > 0) { a.nblk = SUBPIX_GRID; hipLaunchKernelGGL((k_subpixN<11, 16>), dim3(xcd_grid(a.nblk, S)), dim3(64), 0, sys->stream, m, tp, a, 0); }
       }
     }
-    prof_mark(sys, 6);
+    prof_mark(sys, PROF_POSE_COARSE);
   } else {
     const int maxSearch = tp.max_patches + 2 * tp.coarse_max < P ? tp.max_patches + 2 * tp.coarse_max : P;
-    prof_mark(sys, 7);
+    prof_mark(sys, PROF_PLAN_FINE);
     hipLaunchKernelGGL(plan_kernel(sys), dim3(S), dim3(TRK_THREADS), 0, sys->stream, m, tp, 1);
-    prof_mark(sys, 8);
+    prof_mark(sys, PROF_SEARCH_FINE);
     if (tp.P == 8) {
       a.nblk = (maxSearch + 7) / 8; hipLaunchKernelGGL((k_searchN<8, 8>), dim3(xcd_grid(a.nblk, S)), dim3(64), 0, sys->stream, m, tp, a, 1);
       if (tp.fine_subpix_its > 0) { a.nblk = SUBPIX_GRID; hipLaunchKernelGGL((k_subpixN<8, 8>), dim3(xcd_grid(a.nblk, S)), dim3(64), 0, sys->stream, m, tp, a, 1); }
@@ -1256,7 +1256,7 @@ int trk_search_stage(vslam_system* sys, int stage) {
       a.nblk = (maxSearch + 3) / 4; hipLaunchKernelGGL((k_searchN<11, 16>), dim3(xcd_grid(a.nblk, S)), dim3(64), 0, sys->stream, m, tp, a, 1);
       if (tp.fine_subpix_its > 0) { a.nblk = SUBPIX_GRID; hipLaunchKernelGGL((k_subpixN<11, 16>), dim3(xcd_grid(a.nblk, S)), dim3(64), 0, sys->stream, m, tp, a, 1); }
     }
-    prof_mark(sys, 9);
+    prof_mark(sys, PROF_POSE_FINE);
   }
   HIPCHK(hipGetLastError());
   return VSLAM_OK;

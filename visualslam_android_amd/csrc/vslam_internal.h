@@ -271,14 +271,21 @@ static inline int dev_alloc(vslam_system* sys, T** out, size_t count) {
   return VSLAM_OK;
 }
 
-#define PROF_MARKS (VSLAM_N_STAGES + 3)   // marks 0..2 + PROF_FE_END on the front-end stream, 3..VSLAM_N_STAGES on the main stream
+// The profile's stages, in the order of vslam_stage_name (kStageNames, map.hip); a stage's mark is the event at its start, and
+// PROF_FRAME_END, the mark after the last stage, closes the frame.
+enum ProfStage : int {
+  PROF_PYR_FAST0, PROF_FAST_LVL, PROF_COMPACT, PROF_PVS, PROF_PLAN_COARSE, PROF_SEARCH_COARSE, PROF_POSE_COARSE, PROF_PLAN_FINE,
+  PROF_SEARCH_FINE, PROF_POSE_FINE, PROF_ADD_KEYFRAME, PROF_BA_ASSEMBLE, PROF_BA_COMPUTE, PROF_BA_WRITEBACK, PROF_FRAME_END
+};
+static_assert(PROF_FRAME_END == VSLAM_N_STAGES, "ProfStage names every stage of include/vslam_c.h");
+#define PROF_MARKS (VSLAM_N_STAGES + 3)   // the front end's marks + PROF_FE_END on the front-end stream, PROF_PVS..PROF_FRAME_END on the main stream
 #define PROF_FE_END (VSLAM_N_STAGES + 1)
-#define PROF_BA_END (VSLAM_N_STAGES + 2)  // asynchronous map-maker: marks 12 and PROF_BA_END live on the BA stream
+#define PROF_BA_END (VSLAM_N_STAGES + 2)  // asynchronous map-maker: PROF_BA_COMPUTE and PROF_BA_END live on the BA stream
 static inline void prof_mark(vslam_system* sys, int k) {
   if (!(sys->prof_on && sys->prof_frame < sys->prof_cap)) return;
   hipStream_t st = sys->stream;
-  if (k < 3 || k == PROF_FE_END) st = sys->fe_stream;
-  else if (sys->tp.ba_delay > 0 && (k == 12 || k == PROF_BA_END)) st = sys->ba_stream;
+  if (k <= PROF_COMPACT || k == PROF_FE_END) st = sys->fe_stream;
+  else if (sys->tp.ba_delay > 0 && (k == PROF_BA_COMPUTE || k == PROF_BA_END)) st = sys->ba_stream;
   (void)hipEventRecord(sys->prof_ev[(size_t)sys->prof_frame * PROF_MARKS + k], st);
 }
 
@@ -291,13 +298,15 @@ int fe_keyframe_rest_gated(vslam_system* sys);               // non-max + candid
 int fe_thin_new_keyframe(vslam_system* sys, int level);      // ThinCandidates(new keyframe, level) for the streams with kf_pending
 int grow_alloc(vslam_system* sys);
 int grow_on_keyframe(vslam_system* sys);                      // AddSomeMapPoints(3, 0, 1, 2) for the streams with kf_pending
-int grow_idle_refind(vslam_system* sys, int mode);            // idle jobs: 0 ReFindNewlyMade, 1 ReFindFromFailureQueue (gated per stream on device)
+enum IdleRefind : int { REFIND_NEWLY_MADE = 0, REFIND_FAILURE_QUEUE = 1 };
+int grow_idle_refind(vslam_system* sys, int mode);            // idle jobs: an IdleRefind (gated per stream on device)
 int mm_idle(vslam_system* sys);
 int boot_alloc(vslam_system* sys);
 int boot_frame(vslam_system* sys);                                        // TrackForInitialMap for the streams without a map (vslam_params.bootstrap)
 int grow_copy_corners(vslam_system* sys);                                 // Level::vCorners of the current frame into the keyframe slot n_kf (streams with kf_pending)
 int grow_levels(vslam_system* sys, const int* order, int n);              // ThinCandidates + AddPointEpipolar per level, in this order (streams with kf_pending)
 int ba_launch_add_keyframe(vslam_system* sys);                            // k_add_keyframe for the streams with kf_pending
+enum IdleJob : int { IDLE_BA_RECENT = 0, IDLE_REFIND_NEW = 1, IDLE_BA_ALL = 2, IDLE_REFIND_FAILED = 3, IDLE_N_JOBS };   // the job numbers of vslam_mapmaker_idle_job
 int mm_idle_job(vslam_system* sys, int job);                               // vslam_params.idle_iterations passes through MapMaker::run's idle jobs
 int fe_sbi(vslam_system* sys, const FrameDev& last);   // k_sbi on the front-end stream: this frame's SBI + rotation prior against `last`
 int fe_sbi_restart(vslam_system* sys);                 // ... again against the frame itself for the streams vslam_reset_streams flagged (once, then the flags are clear)
@@ -311,11 +320,49 @@ int trk_track_map(vslam_system* sys);
 int trk_search_stage(vslam_system* sys, int stage);
 int trk_pose_stage(vslam_system* sys, int stage);
 // ba.hip
+// What a caller asks of the map-maker (ba_run; k_ba_select gates it per stream).  Line numbers: jni/MapMaker.cc.
+enum class BaJob : int {
+  Keyframe = 0,        // AddKeyFrame + BundleAdjustRecent for the streams with kf_pending (tracker- or host-driven)
+  Recent = 1,          // BundleAdjustRecent, every stream
+  All = 2,             // BundleAdjustAll, every stream (:776-851)
+  IdleRecent = 3,      // idle job of MapMaker::run: Recent for the streams whose adjustment has not converged (:97-98)
+  IdleAll = 4,         // ... All for the streams whose Recent has converged and whose All has not (:107-108)
+  BootAll = 5,         // InitFromStereo's five BundleAdjustAll, for the streams it runs for (:344-345)
+  BootAllUntilConverged = 6,   // ... and its BundleAdjustAll until mbBundleConverged_Full (:361-365)
+};
+// What k_ba_writeback is asked to do with the results in the pool
+enum class BaWriteback : int {
+  Keyframe = 0,        // this frame's keyframe (streams with kf_pending); left to IfDue / Drain when ba_delay > 0
+  Recent = 1,          // apply now: a BundleAdjustRecent
+  All = 2,             // apply now: a BundleAdjustAll
+  IfDue = 3,           // asynchronous map-maker: apply a stream's pending (Recent) result if its countdown says it is due
+  Drain = 4,           // ... make the pending result due now
+  Boot = 5,            // a BundleAdjustAll of InitFromStereo: only the streams it runs for
+};
+// What each job implies, stated once:
+constexpr bool ba_job_all(BaJob j) { return j == BaJob::All || j == BaJob::IdleAll || j >= BaJob::BootAll; }   // all keyframes, or the window around the newest
+constexpr bool ba_job_on_request(BaJob j) { return j == BaJob::Recent || j == BaJob::All; }   // vslam_bundle_adjust_recent / _all: drains first, is timed
+constexpr BaWriteback ba_job_writeback(BaJob j) {
+  return j == BaJob::Keyframe ? BaWriteback::Keyframe : j >= BaJob::BootAll ? BaWriteback::Boot : ba_job_all(j) ? BaWriteback::All : BaWriteback::Recent;
+}
+DEVFN bool ba_job_gate(BaJob j, const TrackerState& st) {   // the streams it runs for, beside map_good and no adjustment in flight
+  switch (j) {
+    case BaJob::Keyframe: return st.kf_pending;
+    case BaJob::IdleRecent: return !st.ba_converged_recent;
+    case BaJob::IdleAll: return st.ba_converged_recent && !st.ba_converged_full;
+    case BaJob::BootAll: return st.boot_run;
+    case BaJob::BootAllUntilConverged: return st.boot_run && !st.ba_converged_full;
+    default: return true;
+  }
+}
+DEVFN int* ba_job_idle_counter(BaJob j, TrackerState* st) {   // the counter of vslam_get_idle_stats it bumps for them
+  return j == BaJob::IdleRecent ? &st->n_ba_recent_idle : j == BaJob::IdleAll ? &st->n_ba_all : nullptr;
+}
 int ba_alloc(vslam_system* sys);
 int ba_add_keyframe_and_adjust(vslam_system* sys);
-int ba_run(vslam_system* sys, int mode, bool host_driven_keyframe = false);
-int ba_frame_start(vslam_system* sys);
-int ba_sync_streams(vslam_system* sys);   // launches an open batch first, then   // host wait for every map-maker stream   // asynchronous map-maker: apply the results that are due at this frame
+int ba_run(vslam_system* sys, BaJob job, bool host_driven_keyframe = false);
+int ba_frame_start(vslam_system* sys);    // asynchronous map-maker: apply the results that are due at this frame
+int ba_sync_streams(vslam_system* sys);   // host wait for every map-maker stream (an open batch is launched first)
 // reloc.hip
 int reloc_alloc(vslam_system* sys);
 int reloc_keyframe_sbi_pending(vslam_system* sys);                        // SmallBlurryImage of the keyframe k_add_keyframe has just stored (streams with kf_pending)
