@@ -161,7 +161,13 @@ int vslam_make_keyframe_rest(vslam_system* sys, double min_shi_tomasi_score);
  * measurements of `keyframe` of each stream (keyframe < 0: the tracker's measurements of the current frame, i.e. what
  * MapMaker::AddKeyFrame copies into the new keyframe). */
 int vslam_thin_candidates(vslam_system* sys, int keyframe);
-/* Candidate::irLevelPos (packed x | y<<16) and dSTScore of one level, raster order; *n = count (may exceed cap). */
+/* Candidate::irLevelPos (packed x | y<<16) and dSTScore of one level, raster order; *n = count (may exceed cap).
+ * After a keyframe with grow_map bit 0 the list is what ThinCandidates left, and a candidate AddPointEpipolar (jni/MapMaker.cc:525-703)
+ * turned away has its score replaced by the negated stage at which it gave up: -1 the ray ends before it starts or behind the target
+ * camera, -2 the epipolar line segment is shorter than 1e-4, -3 the line lies outside the camera's largest radius, -4 the template touches
+ * the source level's border, -5 no target corner on the line scores below the limit, -6 the sub-pixel iterations did not converge,
+ * -7 the map already holds max_points points (a limit of this build, not of PTAM; the remaining candidates are still looked at).  A
+ * candidate that became a map point keeps its Shi-Tomasi score (> 0). */
 int vslam_read_candidates(vslam_system* sys, int stream, int level, uint32_t* pos, double* score, int cap, int* n);
 /* grow_map = 1: Level::vCorners (packed x | y << 16, raster order) of a stored keyframe -- the epipolar search's target list.
  * At most 16384 / 8192 / 4096 / 2048 corners per level are kept (a longer list is cut in raster order); *n = stored count. */

@@ -25,6 +25,7 @@ void* orc_sys_create(const orc_params* q) {
   p.use_sbi = q->use_sbi;
   p.grow_map = q->grow_map;
   p.idle_iterations = q->idle_iterations;
+  p.max_points = q->max_points;
   return new System(p);
 }
 void orc_sys_destroy(void* s) { delete (System*)s; }

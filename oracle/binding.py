@@ -167,7 +167,7 @@ class OrcParams(C.Structure):
                 ("min_frames_between_kf", C.c_int), ("max_kf_dist_wiggle_mult", C.c_double), ("wiggle_scale", C.c_double),
                 ("ba_max_iterations", C.c_int), ("ba_convergence_limit", C.c_double), ("ba_min_tukey_sigma", C.c_double),
                 ("ba_window", C.c_int), ("ba_min_keyframes", C.c_int), ("cam", C.c_double * 5), ("quirks", C.c_int),
-                ("ba_delay_frames", C.c_int), ("use_sbi", C.c_int), ("grow_map", C.c_int), ("idle_iterations", C.c_int)]
+                ("ba_delay_frames", C.c_int), ("use_sbi", C.c_int), ("grow_map", C.c_int), ("idle_iterations", C.c_int), ("max_points", C.c_int)]
 
 
 class TrackState(C.Structure):
@@ -189,7 +189,7 @@ def params_from_vslam(vp):
     for f in ("coarse_min", "coarse_max", "coarse_range", "coarse_subpix_its", "coarse_disabled", "coarse_min_vel",
               "fine_subpix_its", "wls_prior", "min_frames_between_kf", "max_kf_dist_wiggle_mult", "wiggle_scale",
               "ba_max_iterations", "ba_convergence_limit", "ba_min_tukey_sigma", "ba_window", "ba_min_keyframes", "quirks",
-              "ba_delay_frames", "use_sbi", "grow_map", "idle_iterations"):
+              "ba_delay_frames", "use_sbi", "grow_map", "idle_iterations", "max_points"):
         setattr(p, f, getattr(vp, f))
     for i in range(5):
         p.cam[i] = vp.cam[i]
@@ -310,6 +310,25 @@ class OracleSystem:
         out = np.zeros((cap, 3), np.int32)
         n = self.L.orc_sys_get_grow_log(self.h, _p(out), cap)
         return out[:n]
+
+    def grow_detail(self, cap=65536):
+        """one row per row of grow_log: survivors of the line filter, the most of them in one aligned block of 64 entries of the target's
+        corner list, blocks that hold one, the minimum had an equal-ZMSSD rival later in the list, the ray start was clipped, the rank of the
+        minimum among the survivors of its block"""
+        out = np.zeros((cap, 6), np.int32)
+        n = self.L.orc_sys_get_grow_detail(self.h, _p(out), cap)
+        return {k: out[:n, i].copy() for i, k in enumerate(("survivors", "block_max", "blocks", "tie", "clipped", "best_rank"))}
+
+    REFIND_JOBS = ("single keyframe", "newly made", "failure queue")
+    REFIND_OUTCOMES = ("measured", "template bad", "window outside", "not found")
+
+    def refind_log(self, cap=262144):
+        """every ReFind_Common call that reached the template: job (index of REFIND_JOBS), keyframe, point, cache hit, search level, list span of
+        the search window, outcome (index of REFIND_OUTCOMES), run number of the job"""
+        out = np.zeros((cap, 8), np.int32)
+        n = self.L.orc_sys_get_refind_log(self.h, _p(out), cap)
+        assert n <= cap
+        return {k: out[:n, i].copy() for i, k in enumerate(("job", "kf", "pt", "hit", "level", "span", "outcome", "run"))}
 
     def window_counts(self):
         """of this frame's patch searches so far: windows that reach the bottom row of their level, that hold no candidate corner, and

@@ -145,6 +145,8 @@ bool System::AddPointEpipolar(int ksrc, int ktgt, int nLevel, int nCandidate) {
   KeyFrame& kSrc = *kfs[ksrc]; KeyFrame& kTarget = *kfs[ktgt];
   grow_log.push_back(nLevel); grow_log.push_back((int)kSrc.cand[nLevel][nCandidate]); grow_log.push_back(0);
   int& why = grow_log.back();
+  grow_detail.insert(grow_detail.end(), 6, 0);
+  int* detail = &grow_detail[grow_detail.size() - 6];
   const int nLevelScale = level_scale(nLevel);
   const uint32_t cpos = kSrc.cand[nLevel][nCandidate];
   const double irLevelPos[2] = {(double)(cpos & 0xFFFF), (double)(cpos >> 16)};
@@ -161,6 +163,7 @@ bool System::AddPointEpipolar(int ksrc, int ktgt, int nLevel, int nCandidate) {
   if (v3RayEnd_TC[2] <= v3RayStart_TC[2]) { why = 1; return false; }
   if (v3RayEnd_TC[2] <= 0.0) { why = 1; return false; }
   if (v3RayStart_TC[2] <= 0.0) {
+    detail[4] = 1;
     const double f = 0.001 - v3RayStart_TC[2] / v3LineDirn_TC[2];
     for (int i = 0; i < 3; i++) v3RayStart_TC[i] += v3LineDirn_TC[i] * f;
   }
@@ -193,7 +196,9 @@ bool System::AddPointEpipolar(int ksrc, int ktgt, int nLevel, int nCandidate) {
   int nBest = -1, nBestZMSSD = f.max_ssd + 1;
   const double dMaxDistDiff = one_pixel_dist(camera) * (4.0 + 1.0 * nLevelScale);
   const double dMaxDistSq = dMaxDistDiff * dMaxDistDiff;
+  int nInBlock = 0;                                                     // statistics only: survivors of the line filter per aligned block of 64 list entries
   for (size_t i = 0; i < vIR.size(); i++) {
+    if (i % 64 == 0) nInBlock = 0;
     const int cx = vIR[i] & 0xFFFF, cy = vIR[i] >> 16;
     // vImplaneCorners (:612-620): UnProject of the level-zero position TRUNCATED to integer pixels (it indexes a cache image)
     double v2Im[2];
@@ -203,8 +208,12 @@ bool System::AddPointEpipolar(int ksrc, int ktgt, int nLevel, int nCandidate) {
     const double len = v2Im[0] * along[0] + v2Im[1] * along[1];
     if (len < dMinLen) continue;
     if (len > dMaxLen) continue;
+    detail[0]++;
+    if (++nInBlock == 1) detail[2]++;
+    if (nInBlock > detail[1]) detail[1] = nInBlock;
     const int nZMSSD = finder_zmssd(f, kTarget.im[nLevel].data(), kTarget.w[nLevel], kTarget.h[nLevel], kTarget.w[nLevel], cx, cy);
-    if (nZMSSD < nBestZMSSD) { nBest = (int)i; nBestZMSSD = nZMSSD; }
+    if (nZMSSD < nBestZMSSD) { nBest = (int)i; nBestZMSSD = nZMSSD; detail[3] = 0; detail[5] = nInBlock - 1; }
+    else if (nBest != -1 && nZMSSD == nBestZMSSD) detail[3] = 1;
   }
   if (nBest == -1) { why = 5; return false; }
 
@@ -213,6 +222,9 @@ bool System::AddPointEpipolar(int ksrc, int ktgt, int nLevel, int nCandidate) {
   f.subpix[0] = level_zero_pos((double)(vIR[nBest] & 0xFFFF), nLevel);   // SetSubPixPos :661
   f.subpix[1] = level_zero_pos((double)(vIR[nBest] >> 16), nLevel);
   if (!finder_iterate_subpix_to_convergence(f, kTarget, 10)) { why = 6; return false; }
+  // Not PTAM: the reference's map has no capacity.  This mirrors the build's limit (vslam_params.max_points): a candidate that passes every
+  // stage while the map already holds max_points points is turned away as stage 7 and adds nothing; the caller goes on to the next candidate.
+  if (p.max_points > 0 && (int)pts.size() >= p.max_points) { why = 7; return false; }
 
   double uA[2], uB[2];
   camera.unproject(v2RootPos[0], v2RootPos[1], uA);
@@ -258,8 +270,13 @@ bool System::ReFind_Common(int kidx, int pi) {
   finder_calc_level_and_warp(f, pt, k.pose, d);                                                   // MakeTemplateCoarse, jni/PatchFinder.cc:72-76:
   finder_make_template(f, pt, *kfs[pt.src_kf]);              // a regenerated template's own verdict replaces the bad-scale flag (:112-117)
   refind_last_point = pi;
+  const int rec[8] = {refind_job, kidx, pi, f.kept ? 1 : 0, f.level, -1, 1, refind_run};
+  refind_log.insert(refind_log.end(), rec, rec + 8);
+  int* log = &refind_log[refind_log.size() - 8];
   if (f.bad) { pt.never_retry.insert(kidx); return false; }                                       // :1004-1007
-  if (!finder_find_coarse(f, pr.im, k, 4)) { pt.never_retry.insert(kidx); return false; }         // :1009-1013
+  const bool bFound = finder_find_coarse(f, pr.im, k, 4);
+  log[5] = f.span; log[6] = bFound ? 0 : (f.span < 0 ? 2 : 3);
+  if (!bFound) { pt.never_retry.insert(kidx); return false; }                                     // :1009-1013
   Measurement m;
   m.level = f.level; m.source = SRC_REFIND;
   if (f.level > 0) {
@@ -275,12 +292,14 @@ bool System::ReFind_Common(int kidx, int pi) {
 // MapMaker::ReFindInSingleKeyFrame, jni/MapMaker.cc:1040-1056.  Bad points stay in the arrays here (HandleBadPoints) and are skipped.
 int System::ReFindInSingleKeyFrame(int kidx) {
   int n = 0;
+  refind_job = 0; refind_run++;
   for (int i = 0; i < (int)pts.size(); i++) if (!pts[i]->bad && ReFind_Common(kidx, i)) n++;
   return n;
 }
 
 // MapMaker::ReFindNewlyMade, jni/MapMaker.cc:1061-1081: every point of the new queue against every keyframe
 void System::ReFindNewlyMade() {
+  refind_job = 1; refind_run++;
   for (int pi : new_queue) {
     if (pts[pi]->bad) continue;
     for (int k = 0; k < (int)kfs.size(); k++) if (ReFind_Common(k, pi)) n_refound_new++;
@@ -292,6 +311,7 @@ void System::ReFindNewlyMade() {
 // here by (keyframe index, point index), the build's stand-in for address order.
 void System::ReFindFromFailureQueue() {
   if (failure_queue.empty()) return;
+  refind_job = 2; refind_run++;
   std::sort(failure_queue.begin(), failure_queue.end());
   for (auto& e : failure_queue) if (ReFind_Common(e.first, e.second)) n_refound_failed++;
   failure_queue.clear();
@@ -331,6 +351,14 @@ extern "C" void orc_reproject_point(const double AfromB12[12], const double v2A[
   const orc::V3 r = orc::reproject_point(T, v2A, v2B);
   for (int i = 0; i < 3; i++) out3[i] = r[i];
 }
+
+static int copy_records(const std::vector<int>& v, int width, int* out, int cap) {
+  const int n = (int)v.size() / width;
+  for (int i = 0; i < n && i < cap; i++) for (int k = 0; k < width; k++) out[width * i + k] = v[(size_t)width * i + k];
+  return n;
+}
+extern "C" int orc_sys_get_grow_detail(void* sys, int* out6, int cap) { return copy_records(((orc::System*)sys)->grow_detail, 6, out6, cap); }
+extern "C" int orc_sys_get_refind_log(void* sys, int* out8, int cap) { return copy_records(((orc::System*)sys)->refind_log, 8, out8, cap); }
 
 extern "C" int orc_sys_get_grow_log(void* sys, int* out3, int cap) {
   orc::System* S = (orc::System*)sys;

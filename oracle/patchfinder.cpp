@@ -77,6 +77,7 @@ void finder_make_template(Finder& f, const MapPoint& p, const KeyFrame& src) {
     const double lim = 0.07;
     if (dx * dx + dy * dy > lim * lim) refresh = true;
   }
+  f.kept = !refresh;
   if (refresh) {
     const int l = p.src_level;
     const double inOrig[2] = {(double)p.irx, (double)p.iry}, outOrig[2] = {(double)(f.P / 2), (double)(f.P / 2)};
@@ -106,7 +107,7 @@ int finder_zmssd(const Finder& f, const uint8_t* img, int w, int h, int stride, 
 
 // PatchFinder::FindPatchCoarse, jni/PatchFinder.cc:170-235
 bool finder_find_coarse(Finder& f, const double irPosIn[2], const KeyFrame& kf, unsigned nRange) {
-  f.found = false;
+  f.found = false; f.span = -1;
   const int scale = level_scale(f.level);
   const double irPos[2] = {irPosIn[0] / scale, irPosIn[1] / scale};
   nRange = (nRange + scale - 1) / scale;
@@ -124,6 +125,7 @@ bool finder_find_coarse(Finder& f, const double irPosIn[2], const KeyFrame& kf, 
   const int i_end = nBottomPlusOne >= rows ? (int)kf.corners[l].size() : kf.lut[l][nBottomPlusOne];
   int best_x = -1, best_y = -1;
   int nBestSSD = f.max_ssd + 1;
+  f.span = i_end - i;
   for (; i < i_end; i++) {
     const int cx = kf.corners[l][i] & 0xFFFF, cy = kf.corners[l][i] >> 16;
     if (cx < nLeft || cx > nRight) continue;

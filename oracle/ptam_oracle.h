@@ -96,6 +96,8 @@ typedef struct orc_params {           /* mirrors the hot-path fields of vslam_pa
   int use_sbi;                        /* gvnUseSBI, jni/Tracker.cc:88 */
   int grow_map;                       /* AddSomeMapPoints on every new keyframe, jni/MapMaker.cc:498-501 */
   int idle_iterations;                /* iterations of MapMaker::run's idle jobs per frame (jni/MapMaker.cc:94-117) */
+  int max_points;                     /* the build's map capacity (vslam_params.max_points), no limit of PTAM: a candidate AddPointEpipolar would add to a
+                                       * map that holds this many points is logged with stage 7 and adds nothing; 0 = unlimited */
 } orc_params;
 
 typedef struct orc_track_state {      /* same fields as vslam_track_state */
@@ -157,6 +159,15 @@ int orc_sys_get_keyframe_meas(void* sys, int kf, int* pt, int* level, double* ro
 int orc_sys_get_template(void* sys, int pt, uint8_t* tmpl, int* sum, int* sumsq, int* bad);
 /* every AddPointEpipolar call so far: (level, packed candidate position, stage at which it gave up; 0 = point added) */
 int orc_sys_get_grow_log(void* sys, int* out3, int cap);
+/* beside it, one record of 6 per call: target corners that passed the line filter (jni/MapMaker.cc:622-628), the most of them inside one aligned block
+ * of 64 entries of the target's corner list, the blocks that hold at least one, 1 if the strict ZMSSD minimum had an equal rival later in the list,
+ * 1 if the start of the ray was clipped to the image plane (:565-568), the rank of the minimum among the survivors of its block (0 = the first).
+ * Zeros for what a call did not reach. */
+int orc_sys_get_grow_detail(void* sys, int* out6, int cap);
+/* every ReFind_Common call that reached the template (jni/MapMaker.cc:1000), 8 per record: job (0 ReFindInSingleKeyFrame, 1 ReFindNewlyMade,
+ * 2 ReFindFromFailureQueue), keyframe, point, 1 if MakeTemplateCoarseCont kept the previous template, search level, list span of the FindPatchCoarse
+ * window (-1: none), outcome (0 measured, 1 template bad, 2 window outside the level's rows, 3 no corner scored below the limit), run number of the job */
+int orc_sys_get_refind_log(void* sys, int* out8, int cap);
 int orc_sys_bundle_adjust_recent(void* sys);   /* MapMaker::BundleAdjustRecent, jni/MapMaker.cc:801-851 */
 int orc_sys_bundle_adjust_all(void* sys);      /* MapMaker::BundleAdjustAll,    jni/MapMaker.cc:776-798 */
 

@@ -48,6 +48,8 @@ struct Finder {
   double last_warp[4] = {9999.9, 0, 0, 9999.9};   // :23
   long n_zmssd = 0;           // statistics: ZMSSD evaluations (K of SURVEY 8(d))
   long n_win[3] = {0, 0, 0};  // statistics: FindPatchCoarse windows that reach the bottom row / hold no candidate / hold a candidate no patch fits around
+  bool kept = false;          // statistics: the last MakeTemplateCoarseCont kept the previous template (a cache hit)
+  int span = -1;              // statistics: list entries i_end - i of the last FindPatchCoarse window; -1: the window was outside the level's rows
 };
 
 struct MapPoint {     // jni/MapPoint.h:22-69 + TrackerData (jni/TrackerData.h:36-66)
@@ -79,6 +81,7 @@ struct Params {
   int use_sbi = 0;           // gvnUseSBI, jni/Tracker.cc:88 (reference: 1)
   int idle_iterations = 0;   // iterations of MapMaker::run's idle jobs (jni/MapMaker.cc:94-117) after every frame; 0: one BundleAdjustRecent per keyframe only
   int grow_map = 0;          // bit 0: AddSomeMapPoints (jni/MapMaker.cc:498-501), bit 1: ReFindInSingleKeyFrame (:497); 0: only the tracker's measurements
+  int max_points = 0;        // the build's map capacity (vslam_params.max_points), not a limit of PTAM: 0 = unlimited; see AddPointEpipolar
 };
 
 // SmallBlurryImage (jni/SmallBlurryImage.h): mimSmall, mimTemplate (zero-mean, blurred), mimImageJacs (x, y interleaved)
@@ -167,6 +170,15 @@ struct System {
   Finder refinder; int refind_last_point = -1;     // ReFind_Common's static PatchFinder and its mpLastTemplateMapPoint
   int n_points_added = 0, n_refound = 0;
   std::vector<int> grow_log;   // per AddPointEpipolar call: level, packed candidate position, stage at which it gave up (0 = point added)
+  // beside it, per call: target corners that passed the line filter (:622-628), the most of them inside one aligned block of 64 list
+  // entries, the blocks that hold one, the strict minimum had an equal-ZMSSD rival later in the list, the ray start was clipped (:565-568),
+  // the rank of the minimum among the survivors of its block
+  std::vector<int> grow_detail;
+  // per ReFind_Common call that reaches the template: job (0 ReFindInSingleKeyFrame, 1 ReFindNewlyMade, 2 ReFindFromFailureQueue), keyframe,
+  // point, MakeTemplateCoarseCont kept the previous template, search level, list span of the FindPatchCoarse window (-1: outside the rows),
+  // outcome (0 measured, 1 template bad :1004, 2 window outside the level :1009, 3 no corner scored below the limit :1009), the job's run number
+  std::vector<int> refind_log;
+  int refind_job = 0, refind_run = 0;
   int BundleAdjust(const std::vector<int>& adj, const std::vector<int>& fixed, const std::vector<int>& points, bool recent);
   // a finished Bundle whose results are still to be written to the map (asynchronous map-maker model, see mapmaker.cpp)
   struct PendingBA { Bundle b; std::vector<int> id_view, id_point; bool recent = true; int accepted = 0; int countdown = -1; };

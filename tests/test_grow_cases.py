@@ -1,0 +1,157 @@
+"""CPU check of tests/grow_cases.py: the oracle alone, run on every case of tests/test_gpu_grow_counts.py (one tracked frame that becomes a
+keyframe, the four idle jobs, a second tracked frame), reaches the counts at which csrc/mapgrow.hip forks.  A case that misses a condition
+is a broken case: the sub-map has to change, not the condition.  Run with -s to see the counts per stream.
+
+Reached: per-level candidate counts 0, 1, 2, 3, multiples of 4 and every residue modulo the four wavefronts of a chunk; level 3 (the first
+level grow_on_keyframe processes) with candidates and a new point; the reject stages 0, 1, 2, 5, 6, 7; ballots with more survivors than
+one step of k_epipolar scores, up to four steps (the winner in the second step at 8x8, in every step at 11x11); survivors in several blocks of 64; chunks accepted whole and in part; re-finds of the new
+keyframe measured at every level; search windows longer than 64 and 128 list entries; hundreds of kept templates in ReFindNewlyMade, some
+with a bad verdict.
+
+Not reached: at 8x8 a winner scored in the third or fourth step of its ballot (test_group_a prints the steps).  Not reached, and asserted to be
+absent so that a change that reaches one is noticed: stage 3, stage 4, an equal-ZMSSD tie at the
+minimum, the start-depth clip (module docstring of grow_cases.py); of ReFind_Common's early returns, a search window outside the rows of
+its level (the projection has been tested against the image before, jni/MapMaker.cc:996); a kept template in ReFindFromFailureQueue (the
+queue is sorted by keyframe first, neighbours are different points) and one kept across two jobs."""
+import numpy as np
+import pytest
+
+import grow_cases as gc
+import oracle.binding as orc
+
+OUTCOME = {name: i for i, name in enumerate(orc.OracleSystem.REFIND_OUTCOMES)}
+JOB = {name: i for i, name in enumerate(orc.OracleSystem.REFIND_JOBS)}
+
+
+def describe(case, r, patch):
+    d, rf = r.detail, r.refind
+    npw = gc.PATCHES_PER_STEP[patch]
+    line = "  %s: points %d -> %d, candidates per level %s, stages %s" % (case.name, r.n0, r.n_points, r.per_level(), r.stages())
+    if len(r.log):
+        line += "; survivors in one block: > %d in %d calls, most %d; in >= 2 blocks %d calls; chunks whole / mixed %s" % (
+            npw, int((d["block_max"] > npw).sum()), int(d["block_max"].max()), int((d["blocks"] >= 2).sum()), r.chunks())
+    for job, name in enumerate(orc.OracleSystem.REFIND_JOBS):
+        jm = rf["job"] == job
+        if jm.any():
+            line += "\n      %s: %d template calls, measured per level %s, outcomes %s, kept templates %d (bad %d), longest window %d" % (
+                name, int(jm.sum()), [int((jm & (rf["outcome"] == 0) & (rf["level"] == l)).sum()) for l in range(4)],
+                {k: int((jm & (rf["outcome"] == v)).sum()) for k, v in OUTCOME.items()}, int((jm & (rf["hit"] == 1)).sum()),
+                int((jm & (rf["hit"] == 1) & (rf["outcome"] == OUTCOME["template bad"])).sum()), int(rf["span"][jm].max()))
+    return line + "\n      idle: %s; second frame: quality %d, found %s" % (r.idle, r.quality1, r.found1)
+
+
+def records(group, patch, verbose=True):
+    cases = gc.groups(patch)[group]
+    assert 1 <= len(cases) <= 11
+    out = [(c, gc.record(c, patch)) for c in cases if c.has_map]
+    if verbose:
+        print("\n[%s, %dx%d patches] %d streams" % (group, patch, patch, len(cases)))
+        for c, r in out:
+            print(describe(c, r, patch))
+    for c, r in out:                                             # every stream with a map tracks both frames; the growing ones add one keyframe
+        assert (r.kf_added, r.kf_added1, r.n_keyframes - r.kf0) == (int(c.grows), 0, int(c.grows)), c.name
+        assert r.quality0 == r.quality1 == 2 and r.n_points1 == r.n_points, c.name
+        assert r.idle["new_queue"] == 0 and r.idle["failure_queue"] <= 8192, (c.name, r.idle)
+        for k in (3, 4):                                         # the unreached stages stay unreached
+            assert r.stages().get(k, 0) == 0, (c.name, r.stages())
+        assert r.detail["tie"].sum() == 0 and r.detail["clipped"].sum() == 0, c.name
+        assert (r.refind["outcome"] != OUTCOME["window outside"]).all(), c.name
+    return out
+
+
+@pytest.mark.parametrize("patch", [8, 11])
+def test_group_a_reaches_the_epipolar_counts(patch):
+    recs = records("a: epipolar counts", patch)
+    assert [c.name for c in gc.group_a() if not c.grows] == ["no keyframe request", "no map"]
+    for c, r in recs:
+        if not c.grows:
+            assert len(r.log) == 0 and r.n_points == r.n0 and len(r.refind["job"]) == 0 and not any(r.idle.values()), c.name
+    counts = [n for _c, r in recs if _c.grows for n in r.per_level()]
+    assert {0, 1, 2, 3} <= set(counts), counts
+    assert any(n >= 4 and n % gc.GROW_WAVES == 0 for n in counts), counts
+    assert {n % gc.GROW_WAVES for n in counts if n > 4} == set(range(gc.GROW_WAVES)), counts
+    assert max(r.per_level()[3] for _c, r in recs) >= 4
+    assert any(((r.log[:, 0] == 3) & (r.log[:, 2] == 0)).any() for _c, r in recs if len(r.log))                  # a level-3 point is added
+    stages = set().union(*[set(r.stages()) for _c, r in recs])
+    assert stages == {0, 5, 6}, stages
+    npw = gc.PATCHES_PER_STEP[patch]
+    block_max = np.concatenate([r.detail["block_max"] for _c, r in recs])
+    blocks = np.concatenate([r.detail["blocks"] for _c, r in recs])
+    assert (block_max > npw).sum() >= 10 and (block_max > 2 * npw).sum() >= 1 and (blocks >= 2).sum() >= 10
+    # the step of its ballot in which the winning corner is scored: at 11x11 the third and fourth steps hold winners; at 8x8 no sub-map, stride
+    # or texture tried puts one beyond the second step (the winner is among the first 16 survivors of its block), so there the later steps
+    # only ever score losers -- the count is printed, and asserted where it is reached
+    won = np.concatenate([r.detail["best_rank"][np.isin(r.log[:, 2], (0, 6, 7))] for _c, r in recs]) // npw
+    print("  step of the ballot that scores the winner: %s" % {int(k): int((won == k).sum()) for k in np.unique(won)})
+    assert (won >= 1).sum() >= 10 and (patch == 8 or (won >= 2).sum() >= 10)
+    whole, mixed = (sum(x) for x in zip(*[r.chunks() for _c, r in recs]))
+    assert whole >= 1 and mixed >= 1
+    print("  over the group: %d calls; calls with > %d survivors in a block %d, needing >= 3 steps %d, with survivors in >= 2 blocks %d; chunks whole %d, mixed %d"
+          % (len(block_max), npw, int((block_max > npw).sum()), int((block_max > 2 * npw).sum()), int((blocks >= 2).sum()), whole, mixed))
+
+
+def _cat(recs, key):
+    return np.concatenate([r.refind[key] for _c, r in recs])
+
+
+def cross_job_hits(rf):
+    """kept templates whose previous template call belonged to another run of a job"""
+    h = np.flatnonzero(rf["hit"] == 1)
+    assert (h > 0).all() and (rf["pt"][h] == rf["pt"][h - 1]).all()              # a kept template follows a call for the same point
+    return int((rf["run"][h] != rf["run"][h - 1]).sum())
+
+
+@pytest.mark.parametrize("patch", [8, 11])
+def test_group_b_reaches_the_refind_counts(patch):
+    recs = records("b: re-find", patch)
+    job, level, outcome, span, hit = (_cat(recs, k) for k in ("job", "level", "outcome", "span", "hit"))
+    new_kf = job == JOB["single keyframe"]
+    for l in range(4):                                                             # re-finds of the new keyframe measured at every level
+        assert (new_kf & (outcome == OUTCOME["measured"]) & (level == l)).sum() >= 1, l
+    assert (span > 64).sum() >= 1 and (span > 128).sum() >= 1
+    assert (new_kf & (span > 128)).sum() >= 1 and ((job == JOB["newly made"]) & (span > 128)).sum() >= 1     # by the row table and by the binary search
+    for name in ("measured", "template bad", "not found"):                         # every early return the scene reaches ("window outside": none)
+        assert (outcome == OUTCOME[name]).sum() >= 1, name
+    both = recs + records("a: epipolar counts", patch, verbose=False)
+    job, outcome, hit = (_cat(both, k) for k in ("job", "outcome", "hit"))
+    newly = job == JOB["newly made"]
+    n_hits, n_bad = int((newly & (hit == 1)).sum()), int((newly & (hit == 1) & (outcome == OUTCOME["template bad"])).sum())
+    fq_hits = int(((job == JOB["failure queue"]) & (hit == 1)).sum())
+    cross = sum(cross_job_hits(r.refind) for _c, r in both)
+    print("  groups a and b: kept templates in ReFindNewlyMade %d (bad verdict %d), in ReFindFromFailureQueue %d, kept across two jobs %d" % (n_hits, n_bad, fq_hits, cross))
+    assert n_hits >= 100 and n_bad >= 1
+    assert (new_kf_hits := int(((job == JOB["single keyframe"]) & (hit == 1)).sum())) == 0, new_kf_hits      # k_refind's comment: never the same point twice in a row
+    assert fq_hits == 0 and cross == 0           # RefindCache starts empty per point and per queue entry: a hit here would be one the device cannot have
+
+
+@pytest.mark.parametrize("patch", [8, 11])
+@pytest.mark.parametrize("which", ["c: stage 1", "c: stage 2"])
+def test_group_c_rejects_every_call_at_one_stage(which, patch):
+    (c, r), = records(which, patch)
+    assert len(r.log) >= 100 and (r.log[:, 2] == c.target["stage"]).all(), r.stages()
+    assert r.n_points == r.n0 and sum(n > 0 for n in r.per_level()) == 4
+
+
+@pytest.mark.parametrize("patch", [8, 11])
+def test_group_d_fills_the_map(patch):
+    recs = records("d: map capacity", patch)
+    assert [c.target["full_level"] for c, _r in recs] == [0, 1, 0, None, 0]
+    for c, r in recs:
+        assert r.n0 < gc.MAX_POINTS == r.n_points == r.n_points1, (c.name, r.n0, r.n_points)
+        assert sum(r.attempted1) > 0 and r.quality1 == 2, c.name                   # the second frame tracks the full map
+        ff, st = gc.first_full(r), r.log[:, 2]
+        if c.target["full_level"] is None:                                         # the last accepted candidate takes the last slot
+            assert ff is None and (st == 0).sum() == gc.MAX_POINTS - r.n0, c.name
+            continue
+        last, fill = int(np.flatnonzero(st == 0)[-1]), gc.fill_level(r)            # the call that takes the last slot
+        assert ff is not None and fill == c.target["full_level"], (c.name, fill, ff)
+        assert (st[:last + 1] != 7).all() and (st[:last + 1] == 0).sum() == gc.MAX_POINTS - r.n0 and (st[last + 1:] != 0).all(), c.name
+        # up to the end of the level that fills the map the candidates are those of the run without a limit (the later levels are thinned by
+        # fewer new points): there stage 7 is exactly what that run accepts
+        u = gc.record(c, patch, max_points=0).log
+        end = last + 1 + int((r.log[last + 1:, 0] == fill).sum())
+        assert np.array_equal(u[:end, :2], r.log[:end, :2]) and np.array_equal(np.where(st[:end] == 7, 0, st[:end]), u[:end, 2]), c.name
+        assert (st == 7).sum() >= 1 and (r.log[st == 7, 0] == ff[0]).any(), c.name
+        if c.target.get("mid_chunk"):
+            assert ff[1] % gc.GROW_WAVES != 0, (c.name, ff)
+        print("      the map fills during level %d; first call on a full map: level %d, candidate %d of the level (wavefront %d of its chunk); levels with stage 7: %s" % (fill, ff[0], ff[1], ff[1] % gc.GROW_WAVES, sorted(set(r.log[st == 7, 0].tolist()))))
