@@ -103,7 +103,8 @@ def reproject_point(AfromB12, v2A, v2B):
 
 
 def sbi_make(level3, blur=0.75):
-    """SmallBlurryImage::MakeFromKF on a level-3 image -> (small u8 image, zero-mean blurred fp32 template)."""
+    """SmallBlurryImage::MakeFromKF on a level-3 image -> (small u8 image, zero-mean blurred fp32 template).  blur <= 2 takes the
+    reference's 9 x 9 Gaussian, a larger one the 17 x 17 (the relocaliser's 2.5)."""
     l3 = np.ascontiguousarray(level3, np.uint8)
     h3, w3 = l3.shape
     small = np.empty((h3 // 2, w3 // 2), np.uint8); tmpl = np.empty((h3 // 2, w3 // 2), np.float32)
@@ -112,7 +113,8 @@ def sbi_make(level3, blur=0.75):
 
 
 def sbi_rotation(cur_l3, last_l3, cam5, quirks=0, blur=0.75):
-    """Tracker::CalcSBIRotation between two level-3 images -> (6-vector ln of the SE3 adjustment, final ESM score)."""
+    """Tracker::CalcSBIRotation between two level-3 images -> (6-vector ln of the SE3 adjustment, final ESM score); both
+    SmallBlurryImages are made at `blur`, with sbi_make's branch for it."""
     a = np.ascontiguousarray(cur_l3, np.uint8); b = np.ascontiguousarray(last_l3, np.uint8)
     cam = (C.c_double * 5)(*cam5); out = (C.c_double * 6)(); score = C.c_double(0)
     lib().orc_sbi_rotation(_p(a), _p(b), a.shape[1], a.shape[0], C.c_double(blur), cam, int(quirks), out, C.byref(score))

@@ -3,9 +3,9 @@
 //   Tracker::CalcSBIRotation                                                       jni/Tracker.cc:885-893
 // Third-party arithmetic restated here (parity unpinned, OpenCV 2.4.x is not in the tree):
 //   * cv::resize(level 3 -> half size) (:30): the exact 2:1 area filter (a+b+c+d+2)>>2, as for the pyramid;
-//   * cv::GaussianBlur(9x9, sigma 0.75, BORDER_REPLICATE) on CV_32F (:52): separable, fp32 kernel from
+//   * cv::GaussianBlur(9x9 for sigma <= 2, else 17x17, BORDER_REPLICATE) on CV_32F (:51-54): separable, fp32 kernel from
 //     cv::getGaussianKernel (exp(-x^2/(2 sigma^2)) in double, stored and normalised in float), each pass evaluated in
-//     float as k[4]*x[0] + sum_j k[4+j]*(x[+j] + x[-j]) (the symmetric row/column filter form);
+//     float as k[c]*x[0] + sum_j k[c+j]*(x[+j] + x[-j]) (the symmetric row/column filter form);
 //   * Eigen's fixed 4x4 inverse (:207): pivoted Gaussian elimination.
 #include "ptam_system.hpp"
 #include "ptam_oracle.h"
@@ -29,15 +29,18 @@ static SE2 se2_inverse(const SE2& a) {                                          
   return r;
 }
 
-void sbi_gauss_kernel9(double sigma, float k[9]) {   // cv::getGaussianKernel(9, sigma, CV_32F)
+// cv::getGaussianKernel(2 * half + 1, sigma, CV_32F)
+static void sbi_gauss_kernel(double sigma, int half, float* k) {
+  const int n = 2 * half + 1;
   const double scale2X = -0.5 / (sigma * sigma);
   double sum = 0;
-  for (int i = 0; i < 9; i++) { const double x = i - 4.0; k[i] = (float)std::exp(scale2X * x * x); sum += k[i]; }
+  for (int i = 0; i < n; i++) { const double x = i - (double)half; k[i] = (float)std::exp(scale2X * x * x); sum += k[i]; }
   sum = 1.0 / sum;
-  for (int i = 0; i < 9; i++) k[i] = (float)(k[i] * sum);
+  for (int i = 0; i < n; i++) k[i] = (float)(k[i] * sum);
 }
 
-// MakeFromKF (:20-55), blur <= 2 branch only (the tracker uses 0.75, jni/Tracker.cc:87)
+// MakeFromKF (:20-55), both branches of :51-54: 9 x 9 for blur <= 2 (the tracker uses 0.75, jni/Tracker.cc:87), 17 x 17 above
+// (the relocaliser's 2.5)
 void sbi_make(SBI& s, const uint8_t* l3, int w3, int h3, double blur) {
   s.w = w3 / 2; s.h = h3 / 2;                        // mirSize, :22-25
   s.small.assign((size_t)s.w * s.h, 0);
@@ -47,21 +50,22 @@ void sbi_make(SBI& s, const uint8_t* l3, int w3, int h3, double blur) {
   const float fMean = ((float)nSum) / (s.h * s.w);
   std::vector<float> t((size_t)s.w * s.h), row((size_t)s.w * s.h);
   for (size_t i = 0; i < t.size(); i++) t[i] = s.small[i] - fMean;
-  float k[9];
-  sbi_gauss_kernel9(blur, k);
+  const int half = blur <= 2.0 ? 4 : 8;
+  float k[17];
+  sbi_gauss_kernel(blur, half, k);
   auto clampi = [](int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); };
   for (int y = 0; y < s.h; y++)
     for (int x = 0; x < s.w; x++) {
       const float* r = &t[(size_t)y * s.w];
-      float acc = k[4] * r[x];
-      for (int j = 1; j <= 4; j++) acc += k[4 + j] * (r[clampi(x + j, s.w - 1)] + r[clampi(x - j, s.w - 1)]);
+      float acc = k[half] * r[x];
+      for (int j = 1; j <= half; j++) acc += k[half + j] * (r[clampi(x + j, s.w - 1)] + r[clampi(x - j, s.w - 1)]);
       row[(size_t)y * s.w + x] = acc;
     }
   s.tmpl.assign(t.size(), 0.f);
   for (int y = 0; y < s.h; y++)
     for (int x = 0; x < s.w; x++) {
-      float acc = k[4] * row[(size_t)y * s.w + x];
-      for (int j = 1; j <= 4; j++) acc += k[4 + j] * (row[(size_t)clampi(y + j, s.h - 1) * s.w + x] + row[(size_t)clampi(y - j, s.h - 1) * s.w + x]);
+      float acc = k[half] * row[(size_t)y * s.w + x];
+      for (int j = 1; j <= half; j++) acc += k[half + j] * (row[(size_t)clampi(y + j, s.h - 1) * s.w + x] + row[(size_t)clampi(y - j, s.h - 1) * s.w + x]);
       s.tmpl[(size_t)y * s.w + x] = acc;
     }
   s.made_jacs = false;

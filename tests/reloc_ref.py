@@ -1,14 +1,14 @@
-"""numpy restatement of the relocaliser's image arithmetic, used only by the tests (the oracle has no relocaliser and its
-SmallBlurryImage has only the 9-tap branch):
+"""numpy restatement of the relocaliser's image arithmetic, used only by the tests (the oracle has no relocaliser; its
+SmallBlurryImage, oracle/sbi.cpp, is a second statement of the same blur in C++):
 
   * SmallBlurryImage::MakeFromKF (jni/SmallBlurryImage.cc:20-55) with either branch of :51-54, cv::GaussianBlur(9x9) for
-    dBlur <= 2 and (17x17) above, restated as oracle/sbi.cpp restates the 9-tap one: cv::getGaussianKernel's weights (exp in
+    dBlur <= 2 and (17x17) above, restated as oracle/sbi.cpp restates it: cv::getGaussianKernel's weights (exp in
     double, stored and normalised in float) and a row pass then a column pass with a replicated border, every pixel
     k[c]*x0 + sum_j k[c+j]*(x[+j] + x[-j]) accumulated tap by tap in float32;
   * MakeJacs (:58-79);
   * SmallBlurryImage::ZMSSD (:82-94): the difference in float32, squared and summed in float64, columns outer, rows inner.
 
-test_reloc_ref.py pins the 9-tap form to orc.sbi_make bit for bit; the 17-tap form is the same code with more taps."""
+test_reloc_ref.py pins both forms to orc.sbi_make bit for bit."""
 import math
 
 import numpy as np

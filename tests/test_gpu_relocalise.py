@@ -2,8 +2,8 @@
 
 The oracle has no relocaliser, but it has the pieces, and the tests compose them:
 * orc.sbi_make / orc.sbi_rotation are SmallBlurryImage::MakeFromKF and ln(SE3fromSE2(IteratePosRelToTarget(target, 6))) + the final
-  score on the 9-tap branch (dBlur <= 2); tests/reloc_ref.py restates MakeFromKF with 17 taps and the ZMSSD (pinned to the oracle on
-  the shared branch by tests/test_reloc_ref.py);
+  score on both branches (9 taps for dBlur <= 2, 17 above); tests/reloc_ref.py restates MakeFromKF and the ZMSSD in numpy (pinned to
+  the oracle on both branches by tests/test_reloc_ref.py);
 * the staged oracle tracker (frame_begin, search_stage, pose_stage, set_pose, set_velocity) runs TrackMap from the relocaliser's pose.
 
 Scene: 320x240 feeder scene, two streams.  Stream 0 gets two real frames, then blank frames until lost_frames == 3, then real frames
@@ -164,7 +164,7 @@ class Lost:
 
 
 def test_recovery_at_blur_2_matches_the_oracle_composition():
-    """a + c.  reloc_blur = 2.0 is the 9-tap branch the oracle has: keyframe and current templates == orc.sbi_make, every ZMSSD and the
+    """a + c.  reloc_blur = 2.0 is the 9-tap branch: keyframe and current templates == orc.sbi_make, every ZMSSD and the
     best index == reloc_ref, ln(adj) and the ESM score == orc.sbi_rotation, mse3Best = exp(ln adj) * keyframe pose (1e-12 covers the
     test's own exp), then the recovered TrackMap bit for bit (module docstring; checked on the CPU beforehand to end GOOD)."""
     L = Lost(2.0)
@@ -197,8 +197,7 @@ def test_recovery_at_blur_2_matches_the_oracle_composition():
 def test_recovery_at_the_reference_blur():
     """b + c.  reloc_blur = 2.5, the reference's dBlur and the 17 x 17 branch: keyframe and current templates == reloc_ref's 17-tap
     result, ZMSSDs and best index == reloc_ref, the stream ends "Tracking Map, quality good." and is within POSE_TOL of stream 1 a
-    few frames later.  The ESM at 2.5 has no oracle (orc.sbi_rotation has only the 9-tap branch): it is the device function of the
-    blur-2.0 test on another template; its result is held to the recovered frame's composition instead."""
+    few frames later.  ln(adj) and the ESM score == orc.sbi_rotation at blur 2.5, mse3Best = exp(ln adj) * keyframe pose."""
     L = Lost(2.5)
     g, t = L.g, L.t
     gray = L.frames[t]
@@ -207,7 +206,10 @@ def test_recovery_at_the_reference_blur():
     ri = g.reloc_info(0)
     assert (ri["attempts"], ri["successes"]) == (1, 1) and ri["score"] < 9e6
     assert reloc_ref.taps_for(2.5) == 17
-    best, _ = L.expect_images(level3(gray), lambda l3: reloc_ref.make_from_l3(l3, 2.5)[1])
+    cur_l3 = level3(gray)
+    best, _ = L.expect_images(cur_l3, lambda l3: reloc_ref.make_from_l3(l3, 2.5)[1])
+    ln, score = orc.sbi_rotation(cur_l3, L.kf_l3[best], L.vp.cam[:], L.vp.quirks, 2.5)
+    assert np.array_equal(ri["ln_adj"], ln) and ri["score"] == score, (ri["ln_adj"], ln, ri["score"], score)
     assert np.abs(ri["best_pose"] - pose_mul(orc.se3_exp(ri["ln_adj"]), g.keyframe_pose(0, best))).max() < 1e-12
     L.assert_recovered_frame_exact(gray, "recovered frame, blur 2.5")
     for t in range(L.t, L.t + 4):

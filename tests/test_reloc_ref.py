@@ -1,5 +1,6 @@
-"""CPU: the numpy restatement the relocaliser's GPU tests compare against (tests/reloc_ref.py) is pinned to the oracle on the
-branch they share -- the 9-tap SmallBlurryImage -- and has the properties its other half, the ZMSSD, must have."""
+"""CPU: the numpy restatement the relocaliser's GPU tests compare against (tests/reloc_ref.py) is pinned to the oracle on both
+branches of the SmallBlurryImage -- 9 taps and 17, two independent restatements that agree bit for bit -- and has the properties its
+other half, the ZMSSD, must have."""
 import numpy as np
 import pytest
 
@@ -21,6 +22,27 @@ def test_nine_tap_restatement_is_the_oracles(w, h, seed, sigma):
         wsmall, wtmpl = orc.sbi_make(l3, sigma)
         assert np.array_equal(small, wsmall)
         assert tmpl.dtype == np.float32 and np.array_equal(tmpl, wtmpl), float(np.abs(tmpl - wtmpl).max())
+
+
+def smooth_level3(w3, h3, seed):
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:h3, 0:w3]
+    img = 120 + 50 * np.sin(x / 7.0 + 0.3) * np.cos(y / 5.0) + 30 * np.sin((x + 2 * y) / 11.0)
+    return np.clip(img + rng.normal(0, 4.0, img.shape), 0, 255).astype(np.uint8)
+
+
+@pytest.mark.parametrize("w3,h3", [(6, 6), (7, 9), (17, 15), (33, 17), (62, 62), (128, 66), (160, 90)])
+@pytest.mark.parametrize("blur", [0.75, 2.0, 2.5, 4.0])
+def test_both_branches_are_the_oracles_at_small_and_odd_sizes(w3, h3, blur):
+    """numpy and C++ state the blur independently; they agree at both tap counts, at level-3 sizes whose last row and column are
+    dropped, and at small images narrower than the 17 taps, which then reach past both borders at once"""
+    l3 = smooth_level3(w3, h3, 100 * w3 + h3)
+    small, tmpl = reloc_ref.make_from_l3(l3, blur)
+    wsmall, wtmpl = orc.sbi_make(l3, blur)
+    assert small.shape == (h3 // 2, w3 // 2) and np.array_equal(small, wsmall)
+    assert tmpl.dtype == np.float32 and np.array_equal(tmpl, wtmpl), float(np.abs(tmpl - wtmpl).max())
+    if blur > 2.0:                                                        # ... and the 17 taps are not the 9 with another sigma
+        assert not np.array_equal(tmpl, reloc_ref.make_from_l3(l3, blur, taps=9)[1])
 
 
 def test_branch_follows_the_blur():
