@@ -332,8 +332,11 @@ struct SearchArgs {
 // ---------------------------------------------------------------------------------------------------------------
 // SearchForPoints body (jni/Tracker.cc:629-674).  Several patches per wavefront: G lanes per patch (8 for the 8x8 BASELINE patches -> 8 patches per wave, 16 for the
 // reference's 11x11 default -> 4 per wave), lane r < PS owns template row r as packed dwords (unused bytes zero).  Same
-// arithmetic per pixel / per candidate as the reference; no LDS, and the dependent global loads of the patches of a wave
-// overlap (a one-patch-per-wavefront version of this kernel was 2.4x slower at 8x8 and 2.7x slower at 11x11).  ZMSSD sums use v_dot4_u32_u8.
+// arithmetic per pixel / per candidate as the reference; the dependent global loads of the patches of a wave overlap (a
+// one-patch-per-wavefront version of this kernel was 2.4x slower at 8x8 and 2.7x slower at 11x11).  ZMSSD sums use v_dot4_u32_u8.
+// A wavefront's time is the round trips of its chain of dependent loads (list entry -> point -> row LUT -> window corners -> image
+// rows): every link requests all it can know at once, and LDS (4.6 KB) holds the trip's corners and the window while rows are in
+// flight, which keeps the 8x8 form at 64 registers.
 
 // Workgroups go to the eight XCDs of the device round-robin by their linear index, and every XCD has its own L2.  The search kernels
 // gather from one stream's frame pyramid and keyframes: with (patch block, stream) as (x, y) of the grid the ~140 workgroups of a stream
@@ -347,6 +350,55 @@ DEVFN void xcd_stream_block(int nblk, int S, int& s, int& blk) {
   if (s >= S) s = -1;
 }
 static int xcd_grid(int nblk, int S) { return nblk * ((S + TRK_XCDS - 1) / TRK_XCDS) * TRK_XCDS; }
+
+#ifndef SEARCH_N
+#define SEARCH_N 128  // window corners a lane group filters per trip (at least four per lane): the survivors of a trip are the bits of 64-bit masks
+#endif
+#ifndef SEARCH_K
+#define SEARCH_K 4    // survivors whose image rows are in flight together
+#endif
+// Diagnostic build only (-DVSLAM_BA_PROF, tools/build_baprof.sh; read by tools/search_phase_profile.py): clock64() stamps per phase of
+// k_searchN and the counts its trip sizes rest on, of every seventh workgroup per XCD, summed per stage.  The stamps stay in scalar
+// registers and leave in atomics behind the last of them.  Slots: 0-5 cycles per phase, 6 wavefronts, 7 wavefronts that refresh a
+// template, 8 / 9 filter / ZMSSD trips, 10 the ZMSSD trips the patches need one by one, 11 patches, 12 survivors, 13 window corners,
+// 16-23 / 24-32 / 34-39 / 40-49 histograms of corners per window, survivors per patch, filter and ZMSSD trips per wavefront.
+#ifdef VSLAM_BA_PROF
+#define SEARCH_PROF_SLOTS 64
+__device__ unsigned long long g_search_prof[2][SEARCH_PROF_SLOTS];
+enum { SP_ENTRY, SP_TEMPLATE, SP_LUT, SP_FILTER, SP_ZMSSD, SP_WRITE, SP_PHASES };
+#define SEARCH_PROF(...) __VA_ARGS__
+#define SEARCH_PROF_BEGIN() const bool sp_on = (blockIdx.x / TRK_XCDS) % 7 == 0; unsigned long long sp_ph[SP_PHASES] = {0, 0, 0, 0, 0, 0}, sp_t0 = clock64(); \
+  int sp_ftrips = 0, sp_ztrips = 0, sp_ncorners = 0; bool sp_refresh = false
+#define SEARCH_STAMP(id) do { if (sp_on) { const unsigned long long t_ = clock64(); sp_ph[id] += t_ - sp_t0; sp_t0 = t_; } } while (0)
+#define SEARCH_PROF_END() do { if (sp_on) search_prof_flush(g_search_prof[stage], sp_ph, sp_ftrips, sp_ztrips, sp_refresh, e < nsearch && lead, sp_ncorners, (int)nEval); } while (0)
+DEVFN void search_prof_flush(unsigned long long* g, const unsigned long long* ph, int ftrips, int ztrips, bool refresh, bool patch, int ncorners, int nsurv) {
+  if (threadIdx.x == 0) {
+    for (int i = 0; i < SP_PHASES; i++) atomicAdd(&g[i], ph[i]);
+    atomicAdd(&g[6], 1ull); atomicAdd(&g[7], refresh ? 1ull : 0ull); atomicAdd(&g[8], (unsigned long long)ftrips); atomicAdd(&g[9], (unsigned long long)ztrips);
+    atomicAdd(&g[34 + (ftrips < 5 ? ftrips : 5)], 1ull); atomicAdd(&g[40 + (ztrips < 9 ? ztrips : 9)], 1ull);
+  }
+  if (patch) {
+    atomicAdd(&g[10], (unsigned long long)((nsurv + SEARCH_K - 1) / SEARCH_K)); atomicAdd(&g[11], 1ull);
+    atomicAdd(&g[12], (unsigned long long)nsurv); atomicAdd(&g[13], (unsigned long long)ncorners);
+    const int cb = ncorners == 0 ? 0 : ncorners <= 64 ? 1 + (ncorners - 1) / 16 : ncorners <= 128 ? 5 + (ncorners - 65) / 32 : 7;
+    const int sb = nsurv <= 4 ? nsurv : nsurv <= 16 ? 5 + (nsurv - 5) / 4 : 8;
+    atomicAdd(&g[16 + cb], 1ull); atomicAdd(&g[24 + sb], 1ull);
+  }
+}
+#else
+#define SEARCH_PROF(...)
+#define SEARCH_PROF_BEGIN() do { } while (0)
+#define SEARCH_STAMP(id) do { } while (0)
+#define SEARCH_PROF_END() do { } while (0)
+#endif
+
+// k_searchN's workgroup is one wavefront, whose LDS accesses are made in program order: what one lane wrote is there for the others once the
+// compiler keeps that order.  No wait and no s_barrier, which would also wait for every global load, store and atomic in flight.
+DEVFN void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 template <int PS, int G>
 __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, SearchArgs a, int stage) {
@@ -363,6 +415,7 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
   const int e = bx * PPW + grp;
   bool act = e < nsearch;                                            // this lane group has a patch
   const bool lead = sub == 0;
+  SEARCH_PROF_BEGIN();
   const int2 ent = act ? m.search_list[(size_t)s * tp.max_points + e] : make_int2(0, 0);
   const int idx = ent.x, nSubPixIts = ent.y;
   const int nRangeL0 = stage == 0 ? st->coarse_range : st->fine_range;
@@ -371,17 +424,29 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
   int& tdflags = m.pt_flags[(size_t)s * tp.max_points + idx];
   const MapPointDev& p = m.pts[(size_t)s * tp.max_points + idx];
   uint8_t* gtmpl = m.tmpl + ((size_t)s * tp.max_points + idx) * TMPL_PITCH;
+  // Everything the search reads of the point, requested in one batch behind the list entry: nothing below loads from td, and the
+  // stores to td, the flags and the cached template come after the loads they could otherwise hold back.
   const int level = act ? tdlevel : 0, scale = 1 << level;
   int flags = tdflags;
+  const double td_image[2] = {td.image[0], td.image[1]};
+  const double td_warp_inv[4] = {td.warp_inv[0], td.warp_inv[1], td.warp_inv[2], td.warp_inv[3]};
+  const double td_last_warp[4] = {td.last_warp[0], td.last_warp[1], td.last_warp[2], td.last_warp[3]};
+  const int tsum_cached = td.tsum, tsumsq_cached = td.tsumsq;
+  PRow<PS> trow = zero_row<PS>();                                    // template row `sub`
+  if (rowact) trow = load_row<PS>(gtmpl + sub * PS);                 // the cached row, fetched along with the tracker data; a refresh overwrites it
+  // What the template and the trips do not read waits in LDS while they run: the predicted position (the window and the filter read
+  // it) and, below, the window's columns and what the write-out needs of the patch.  This keeps the 8x8 form at 64 registers.
+    struct PatchRec { double irx, iry; int left, right; unsigned range; int flags, level, subpix_its, idx, pad; };
+  __shared__ PatchRec wrec[PPW];
+  if (lead) { wrec[grp].irx = td_image[0] / scale; wrec[grp].iry = td_image[1] / scale; }
+  SEARCH_STAMP(SP_ENTRY);
 
   // ---- MakeTemplateCoarseCont, jni/PatchFinder.cc:79-125 ----
   double m2[4];
-  template_warp_matrix(td.warp_inv, scale, m2);
-  const bool refresh = (!(flags & TDF_HAVE_LAST) || warp_moved(m2, td.last_warp)) && act;
-  PRow<PS> trow = zero_row<PS>();                                    // template row `sub`
-  if (rowact) trow = load_row<PS>(gtmpl + sub * PS);                 // the cached row, fetched along with the tracker data; a refresh overwrites it
-  const int tsum_cached = td.tsum, tsumsq_cached = td.tsumsq;
+  template_warp_matrix(td_warp_inv, scale, m2);
+  const bool refresh = (!(flags & TDF_HAVE_LAST) || warp_moved(m2, td_last_warp)) && act;
   int tsum, tsumsq;
+  SEARCH_PROF(sp_refresh = __any(refresh) != 0;)
   if (__any(refresh)) {
     // transform_image (jni/vision/ImageHandler.cpp:21-113): same accumulated stepping of the sample position
     const int sl = p.src_level;
@@ -420,71 +485,100 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
     if (lead) tdflags = flags & ~(TDF_IN_IMAGE | TDF_FOUND);
     act = false;
   }
-  for (int l = 0; l < NLEV; l++) {                                   // manMeasAttempted[level]++ (:641), one atomic per wave
-    const int c = __popcll(__ballot(act && lead && level == l));
-    if (lane == 0 && c) atomicAdd(&st->attempted[l], c);
-  }
+  const bool attempted = act;                                        // counted with the found patches, behind the last load: the wait for a
+  SEARCH_STAMP(SP_TEMPLATE);                                         // load ends only when the atomics and stores issued before it have ended
 
-  // ---- FindPatchCoarse, jni/PatchFinder.cc:170-235 ----
-  const double irx = td.image[0] / scale, iry = td.image[1] / scale;
+  // ---- FindPatchCoarse, jni/PatchFinder.cc:170-235: the window and its rows of the corner list, all three entries requested together ----
+  wave_lds_sync();
+  const double irx = wrec[grp].irx, iry = wrec[grp].iry;
   const int rows = a.h[level], cols = a.w[level];
   const CoarseWindow cw = coarse_window(irx, iry, nRangeL0, scale, rows);
+  int i0 = 0, i1 = 0;
+  if (act && !cw.empty) {
+    const int* lut = a.rowlut[level] + (size_t)s * (rows + 1);
+    const int below = cw.bottom_plus_one >= rows ? rows : cw.bottom_plus_one;
+    const int n_all = a.ncorners[s * NLEV + level], lut_top = lut[cw.top], lut_below = lut[below];
+    i0 = lut_top;
+    i1 = cw.bottom_plus_one >= rows ? n_all : lut_below;
+  }
   int nBestSSD = tp.max_ssd + 1;
   uint32_t bestCorner = 0;                                           // packed position of the best candidate so far
   unsigned nEval = 0;
   const uint32_t* corners = a.corners[level] + (size_t)s * a.cap[level];
   const uint8_t* img = a.img[level] + (size_t)s * a.img_sstride[level];
   const int ip = a.img_pitch[level];
-  int i0 = 0, i1 = 0;
-  if (act && !cw.empty) {
-    const int* lut = a.rowlut[level] + (size_t)s * (rows + 1);
-    i0 = lut[cw.top];
-    i1 = cw.bottom_plus_one >= rows ? a.ncorners[s * NLEV + level] : lut[cw.bottom_plus_one];
+  SEARCH_PROF(sp_ncorners = i1 - i0;)
+  // Filter SEARCH_N corners of the row-LUT window per trip (:216-219: x window, then the circular range test): lane `sub` takes
+  // corners base + j G + sub, j < CPL, all requested before the first is tested, so the group's survivors form a bit mask in
+  // raster order.  Survivors are scored SEARCH_K at a time (the image rows of all of them are in flight before one is used) and
+  // compared in raster order (:223).
+  constexpr int CPL = SEARCH_N / G < 4 ? 4 : SEARCH_N / G, K = SEARCH_K, NM = (CPL * G + 63) / 64;
+  static_assert(64 % G == 0, "a lane group's bits of one ballot lie in one mask word");
+  constexpr int CSTRIDE = CPL * G + G;                               // a group's corners of the trip, padded so that the groups' writes meet no common bank
+  __shared__ uint32_t ctrip[PPW * CSTRIDE];
+  uint32_t* const gtrip = ctrip + grp * CSTRIDE;
+  if (lead) {
+    wrec[grp].left = cw.left; wrec[grp].right = cw.right; wrec[grp].range = cw.range;
+    wrec[grp].flags = flags; wrec[grp].level = level; wrec[grp].subpix_its = nSubPixIts; wrec[grp].idx = idx;
   }
-  const double r2max = (double)(cw.range * cw.range);
-  // Filter 4 G corners of the row-LUT window per step (:216-219: x window, then the circular range test): lane `sub` takes
-  // corners base + j G + sub, j < 4, so the group's survivors form one bit mask in raster order.  Survivors are scored two
-  // at a time (both image rows are in flight before either is used) and compared in raster order (:223).
-  constexpr int CPL = 4;
+  wave_lds_sync();
   for (int base = i0; __any(base < i1); base += CPL * G) {
     uint32_t cval[CPL];
-    unsigned long long gm = 0;
+    unsigned long long gm[NM];                                       // bit k of the masks, read as one: corner base + k survives
+#pragma unroll
+    for (int w = 0; w < NM; w++) gm[w] = 0;
+    const double wx = wrec[grp].irx, wy = wrec[grp].iry, r2max = (double)(wrec[grp].range * wrec[grp].range);
+    const int wleft = wrec[grp].left, wright = wrec[grp].right;
 #pragma unroll
     for (int j = 0; j < CPL; j++) {
       const int ci = base + j * G + sub;
       cval[j] = ci < i1 ? corners[ci] : 0u;
     }
+    SEARCH_STAMP(SP_LUT);                                            // the wait for the row-LUT entries ends where the first address is formed
 #pragma unroll
     for (int j = 0; j < CPL; j++) {
       const int ci = base + j * G + sub;
       bool ok = false;
       if (ci < i1) {
         const int cx = cval[j] & 0xFFFF, cy = cval[j] >> 16;
-        if (!(cx < cw.left || cx > cw.right)) {
-          const double dx = irx - cx, dy = iry - cy;
+        if (!(cx < wleft || cx > wright)) {
+          const double dx = wx - cx, dy = wy - cy;
           ok = !(dx * dx + dy * dy > r2max);
         }
       }
-      gm |= (unsigned long long)((unsigned)(__ballot(ok) >> (grp * G)) & ((1u << G) - 1u)) << (j * G);
+      gm[j * G / 64] |= (unsigned long long)((unsigned)(__ballot(ok) >> (grp * G)) & ((1u << G) - 1u)) << (j * G % 64);
+      gtrip[j * G + sub] = cval[j];                                  // bit k of the masks is gtrip[k]: the survivors are read back from here
     }
-    nEval += __popcll(gm);
-    while (__any(gm != 0)) {
-      int kk[2]; bool has[2], inside[2]; uint32_t c[2]; PRow<PS> n[2];
+    wave_lds_sync();                                                 // the writes before the reads of other lanes
+    unsigned long long left = 0;                                     // any survivor not yet scored
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
-        has[u] = gm != 0;
-        kk[u] = has[u] ? __ffsll((long long)gm) - 1 : 0;
-        gm &= gm - 1;
-        const int j = kk[u] / G;
-        const uint32_t csel = j == 0 ? cval[0] : (j == 1 ? cval[1] : (j == 2 ? cval[2] : cval[3]));
-        c[u] = __shfl(csel, grp * G + (kk[u] % G));
+    for (int w = 0; w < NM; w++) { nEval += __popcll(gm[w]); left |= gm[w]; }
+    SEARCH_PROF(sp_ftrips++;)
+    SEARCH_STAMP(SP_FILTER);
+    while (__any(left != 0)) {
+      bool has[K], inside[K]; uint32_t c[K]; PRow<PS> n[K];
+#pragma unroll
+      for (int u = 0; u < K; u++) {
+        has[u] = left != 0;
+        int kk = 0;                                                  // the lowest set bit of the masks, which is then cleared
+        bool taken = false;
+        left = 0;
+#pragma unroll
+        for (int w = 0; w < NM; w++) {
+          const bool here = !taken && gm[w] != 0;
+          if (here) { kk = 64 * w + __ffsll((long long)gm[w]) - 1; gm[w] &= gm[w] - 1; }
+          taken = taken || here;
+          left |= gm[w];
+        }
+        c[u] = gtrip[kk];
         const int cx = c[u] & 0xFFFF, cy = c[u] >> 16;
         inside[u] = has[u] && cx >= HALF && cy >= HALF && cx < cols - HALF && cy < rows - HALF;   // in_image_with_border
         n[u] = zero_row<PS>();
         if (inside[u] && rowact) n[u] = load_row<PS>(img + (size_t)(cy - HALF + sub) * ip + (cx - HALF));
       }
 #pragma unroll
-      for (int u = 0; u < 2; u++) {
+      for (int u = 0; u < K; u++) {
+        if (u >= 2 && !__any(has[u])) break;                         // no group of the wavefront has a candidate left in this trip
         // ZMSSDAtPoint (:352-380): one image row per lane; the pad bytes of both rows are zero
         int sA, sQ, sX;
         grp_zmssd_sums<PS, G>(n[u], trow, sA, sQ, sX);
@@ -493,27 +587,37 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
           if (ssd < nBestSSD) { nBestSSD = ssd; bestCorner = c[u]; }   // first strict minimum in raster order (:223)
         }
       }
+      SEARCH_PROF(sp_ztrips++;)
+      SEARCH_STAMP(SP_ZMSSD);
     }
+    wave_lds_sync();                                                 // the next trip overwrites what this one read
   }
-  flags |= TDF_SEARCHED;                                             // :645
+  SEARCH_STAMP(SP_LUT);                                              // a wavefront without a window
   {
     const int tot = wave_sum(act && lead ? (int)nEval : 0);
     if (lane == 0 && tot) atomicAdd(&st->n_zmssd, (unsigned long long)tot);
   }
-  bool found = act && nBestSSD < tp.max_ssd;
-  if (act && !found && lead) tdflags = flags & ~TDF_FOUND;          // :646-649
+  const int wlevel = wrec[grp].level, wits = wrec[grp].subpix_its;
+  int wflags = wrec[grp].flags | TDF_SEARCHED;                       // :645
+  const size_t gi = (size_t)s * tp.max_points + wrec[grp].idx;
+  const bool found = act && nBestSSD < tp.max_ssd;
+  if (act && !found && lead) m.pt_flags[gi] = wflags & ~TDF_FOUND;   // :646-649
   const uint32_t bc = found ? bestCorner : 0u;
-  const double coarse[2] = {level_zero_pos((double)(bc & 0xFFFF), level), level_zero_pos((double)(bc >> 16), level)};
-  if (found) flags |= TDF_FOUND;
-  const bool dosub = found && nSubPixIts > 0;                        // refined by k_subpixN, which also counts it as found
+  const double coarse[2] = {level_zero_pos((double)(bc & 0xFFFF), wlevel), level_zero_pos((double)(bc >> 16), wlevel)};
+  if (found) wflags |= TDF_FOUND;
+  const bool dosub = found && wits > 0;                              // refined by k_subpixN, which also counts it as found
   if (found) {                                                       // :668-671
-    flags = dosub ? (flags | TDF_SUBPIX) : (flags & ~TDF_SUBPIX);
-    if (lead) { tdflags = flags; td.sqrt_inv_noise = 1.0 / scale; td.vfound[0] = coarse[0]; td.vfound[1] = coarse[1]; }
+    wflags = dosub ? (wflags | TDF_SUBPIX) : (wflags & ~TDF_SUBPIX);
+    if (lead) { TrackData& tdw = m.td[gi]; m.pt_flags[gi] = wflags; tdw.sqrt_inv_noise = 1.0 / (1 << wlevel); tdw.vfound[0] = coarse[0]; tdw.vfound[1] = coarse[1]; }
   }
-  for (int l = 0; l < NLEV; l++) {                                   // manMeasFound[level]++ (:652)
-    const int c = __popcll(__ballot(found && !dosub && lead && level == l));
+  for (int l = 0; l < NLEV; l++) {                                   // manMeasAttempted[level]++ (:641) and manMeasFound[level]++ (:652), one atomic per wave
+    const int ca = __popcll(__ballot(attempted && lead && wlevel == l));
+    if (lane == 0 && ca) atomicAdd(&st->attempted[l], ca);
+    const int c = __popcll(__ballot(found && !dosub && lead && wlevel == l));
     if (lane == 0 && c) atomicAdd(&st->found[l], c);
   }
+  SEARCH_STAMP(SP_WRITE);
+  SEARCH_PROF_END();
 }
 
 // MakeSubPixTemplate (jni/PatchFinder.cc:242-271) + IterateSubPixToConvergence (:273-350) for the patches k_searchN found
@@ -1125,6 +1229,13 @@ __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VS
 }
 
 #ifdef VSLAM_BA_PROF
+extern "C" int vslam_debug_search_prof(unsigned long long* out, int reset) {   // [2 stages][SEARCH_PROF_SLOTS]
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_search_prof), sizeof(unsigned long long) * 2 * SEARCH_PROF_SLOTS));
+  if (reset) { unsigned long long z[2 * SEARCH_PROF_SLOTS] = {0}; HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_search_prof), z, sizeof(z))); }
+  out[15] = SEARCH_N; out[SEARCH_PROF_SLOTS + 15] = SEARCH_K;                  // the trip sizes this library was built with
+  return VSLAM_OK;
+}
 extern "C" int vslam_debug_pose_prof(unsigned long long* out16, int reset) {
   HIPCHK(hipDeviceSynchronize());
   HIPCHK(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_pose_prof), sizeof(unsigned long long) * 16));
