@@ -122,7 +122,7 @@ template <class T> static void arena_take(PoolArena& a, T** out, size_t count) {
 }
 #define PALLOC(field, count) arena_take(a, &b.field, (count))
 
-static int pool_create(BaPool& b, std::vector<void*>& allocs, hipStream_t st, int N, int max_cams, int max_pts, int max_meas, int work_slots = 1, bool ordered = false, size_t lstat_records = 0) {
+static int pool_create(BaPool& b, DevOwner& own, hipStream_t st, int N, int max_cams, int max_pts, int max_meas, int work_slots = 1, bool ordered = false, size_t lstat_records = 0) {
   b.N = N; b.max_cams = max_cams; b.max_pts = max_pts; b.max_meas = max_meas; b.max_free = max_cams;
   b.work_slots = work_slots > 0 ? work_slots : 1;
   const size_t n = N, C = max_cams, P = max_pts, M = max_meas, F = (size_t)max_cams * 6;
@@ -149,12 +149,8 @@ static int pool_create(BaPool& b, std::vector<void*>& allocs, hipStream_t st, in
   };
   PoolArena a = {nullptr, 0};
   carve(a);                                                           // sizes only
-  const size_t bytes = a.off + 256;
-  void* ptr = nullptr;
-  HIPCHK(hipMalloc(&ptr, bytes));
-  allocs.push_back(ptr);
-  HIPCHK(hipMemsetAsync(ptr, 0, bytes, st));
-  a.base = (char*)ptr; a.off = 0;
+  VCHK(own.alloc(&a.base, a.off + 256, st));
+  a.off = 0;
   carve(a);
   return VSLAM_OK;
 }
@@ -176,7 +172,7 @@ struct HostProblem {
 static inline unsigned long long meas_key(int cam, int point) { return ((unsigned long long)(unsigned)cam << 32) | (unsigned)point; }
 
 struct vslam_bundle {
-  BaPool pool; std::vector<void*> allocs; hipStream_t stream; BaConfig cfg; TrackParams tp;
+  BaPool pool; DevOwner own; hipStream_t stream = nullptr; BaConfig cfg; TrackParams tp;
   std::vector<HostProblem> host; bool uploaded;
   hipEvent_t ev[2] = {nullptr, nullptr};      // around the last Bundle::Compute launch (vslam_bundle_get_timing)
   // Compute() overwrites cameras, points and results; a second Compute() of the same problems restores them from these device-side
@@ -185,6 +181,18 @@ struct vslam_bundle {
 };
 
 
+// everything a new bundle acquires, through its owner; vslam_bundle_create gives a handle that failed here to vslam_bundle_destroy
+static int bundle_acquire(vslam_bundle* b, int n_problems, int max_cameras, int max_points, int max_meas) {
+  VCHK(b->own.stream(&b->stream));
+  VCHK(pool_create(b->pool, b->own, b->stream, n_problems, max_cameras, max_points, max_meas, 1, b->cfg.sum_order != 0, 1));   // one launch record (vslam_bundle_get_timing)
+  for (int k = 0; k < 2; k++) VCHK(b->own.event(&b->ev[k], true));
+  VCHK(b->own.alloc(&b->res0, (size_t)n_problems, b->stream));
+  VCHK(b->own.alloc(&b->cam0, (size_t)n_problems * max_cameras, b->stream));
+  VCHK(b->own.alloc(&b->pt0, 3 * (size_t)n_problems * max_points, b->stream));
+  b->host.resize(n_problems);
+  HIPCHK(hipStreamSynchronize(b->stream));              // the zeroing contract (DevOwner::alloc)
+  return VSLAM_OK;
+}
 
 extern "C" int vslam_bundle_create(const vslam_params* p, int n_problems, int max_cameras, int max_points, int max_meas, vslam_bundle** out) {
   if (!p || !out || n_problems < 1 || max_cameras < 1 || max_cameras > BA_MAX_KF || max_points < 1 || max_points > 4096 || max_meas < 1 || max_meas > 65536) {
@@ -195,31 +203,17 @@ extern "C" int vslam_bundle_create(const vslam_params* p, int n_problems, int ma
   HIPCHK(hipSetDevice(p->device));
   vslam_bundle* b = new vslam_bundle();
   b->uploaded = false;
-  HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   trk_fill_params(*p, b->tp);
   b->cfg = make_cfg(b->tp);
-  int r = pool_create(b->pool, b->allocs, b->stream, n_problems, max_cameras, max_points, max_meas, 1, b->cfg.sum_order != 0, 1);   // one launch record (vslam_bundle_get_timing)
-  if (!r && (hipEventCreate(&b->ev[0]) != hipSuccess || hipEventCreate(&b->ev[1]) != hipSuccess)) { vslam_set_error("bundle_create: hipEventCreate failed"); r = VSLAM_E_HIP; }
-  if (!r) {
-    void* q = nullptr;
-    if (hipMalloc(&q, sizeof(BaResult) * n_problems + 64) == hipSuccess) { b->res0 = (BaResult*)q; b->allocs.push_back(q); } else r = VSLAM_E_HIP;
-    if (!r && hipMalloc(&q, sizeof(Pose) * (size_t)n_problems * max_cameras + 64) == hipSuccess) { b->cam0 = (Pose*)q; b->allocs.push_back(q); } else if (!r) r = VSLAM_E_HIP;
-    if (!r && hipMalloc(&q, sizeof(double) * 3 * (size_t)n_problems * max_points + 64) == hipSuccess) { b->pt0 = (double*)q; b->allocs.push_back(q); } else if (!r) r = VSLAM_E_HIP;
-    if (r) vslam_set_error("bundle_create: hipMalloc failed");
-  }
+  const int r = bundle_acquire(b, n_problems, max_cameras, max_points, max_meas);
   if (r) { vslam_bundle_destroy(b); return r; }
-  b->host.resize(n_problems);
-  HIPCHK(hipStreamSynchronize(b->stream));
   *out = b;
   return VSLAM_OK;
 }
 
 extern "C" int vslam_bundle_destroy(vslam_bundle* b) {
   if (!b) return VSLAM_OK;
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  for (void* p : b->allocs) (void)hipFree(p);
-  for (int k = 0; k < 2; k++) if (b->ev[k]) (void)hipEventDestroy(b->ev[k]);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
+  b->own.release();
   delete b;
   return VSLAM_OK;
 }
@@ -734,22 +728,25 @@ __global__ __launch_bounds__(BA_THREADS) void k_handle_bad_points(MapDev m, Trac
 // ---- host ---------------------------------------------------------------------------------------------------------
 struct BaSystemWs { BaPool pool; };
 
+void ba_free(vslam_system* sys) { delete sys->ba_ws; sys->ba_ws = nullptr; }
+
 int ba_alloc(vslam_system* sys) {
-  BaSystemWs* ws = new BaSystemWs();
-  sys->ba_ws = ws;
+  BaSystemWs* ws = sys->ba_ws = new BaSystemWs();
   const int K = sys->p.max_keyframes, P = sys->p.max_points;
   if (K > BA_MAX_KF) { vslam_set_error("max_keyframes %d exceeds %d", K, BA_MAX_KF); return VSLAM_E_INVALID; }
   // worst case of BundleAdjust: every keyframe a camera, every point, every (kf, point) slot a measurement
   size_t M = (size_t)K * P;
   if (M > 65536) M = 65536;
-  int r = pool_create(ws->pool, sys->allocs, sys->stream, sys->S, K, P, (int)M, sys->p.ba_delay_frames > 0 ? sys->p.ba_delay_frames + 2 : 1, sys->p.ba_sum_order != 0, BA_LSTAT_RING);
-  if (r) return r;
+  VCHK(pool_create(ws->pool, sys->own, sys->stream, sys->S, K, P, (int)M, sys->p.ba_delay_frames > 0 ? sys->p.ba_delay_frames + 2 : 1, sys->p.ba_sum_order != 0, BA_LSTAT_RING));
   // One launch of the full synchronous grid over the still empty pool (every problem inactive: the workgroups return at once).
   // k_ba_compute needs scratch memory, and the runtime sizes that lazily, at the first launch of a grid this large: paid here,
   // at creation, not by the first BundleAdjustRecent / BundleAdjustAll a caller times.
   ba_launch_compute(ws->pool, make_cfg(sys->tp), sys->S, sys->stream, -1, -1);
   // ... and on every stream of the asynchronous map-maker's ring: scratch belongs to the hardware queue a stream maps to, and the
   // first batch on a queue that has not seen the kernel stalled the host for ~5 ms in the middle of the timed frames.
+  // Those streams are not ordered behind the system's, and the kernels read the pool's `active` flags: the zeroing contract of
+  // DevOwner::alloc is kept by waiting for the pool's memset first.
+  HIPCHK(hipStreamSynchronize(sys->stream));
   for (hipStream_t st : sys->ba_streams) ba_launch_compute(ws->pool, make_cfg(sys->tp), sys->S, st, -1, -1);
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
@@ -758,7 +755,7 @@ int ba_alloc(vslam_system* sys) {
 
 // the next record of the ring, zeroed on the stream that launches k_ba_compute
 static int ba_next_launch_record(vslam_system* sys, hipStream_t st, int* rec, int* ordinal) {
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   *ordinal = (int)(sys->ba_launch_no & 0x3fffffff);
   *rec = (int)(sys->ba_launch_no++ % BA_LSTAT_RING);
   HIPCHK(hipMemsetAsync(ws->pool.lstat + (size_t)*rec * BA_LSTAT_N, 0, sizeof(unsigned long long) * BA_LSTAT_N, st));
@@ -777,7 +774,7 @@ static void fill_kfcopy(vslam_system* sys, KfCopyArgs& a) {
 // the next map-maker stream of the ring, behind the main stream's last k_ba_assemble.
 static int ba_launch_batch(vslam_system* sys) {
   if (sys->ba_batch_fill == 0) return VSLAM_OK;
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   const BaConfig cfg = make_cfg(sys->tp);
   const int R = (int)sys->ev_ba.size(), slot = (int)(sys->ba_batch_id % R);
   sys->ba_stream = sys->ba_streams[(size_t)(sys->ba_batch_id % (long)sys->ba_streams.size())];
@@ -802,7 +799,7 @@ static int ba_launch_batch(vslam_system* sys) {
 int ba_frame_start(vslam_system* sys) {
   const int D = sys->tp.ba_delay;
   if (D <= 0) return VSLAM_OK;
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   const int R = (int)sys->ev_ba.size(), FB = (int)sys->frame_batch.size();
   prof_mark(sys, PROF_BA_WRITEBACK);
   if (sys->frame_no >= D) {
@@ -843,7 +840,7 @@ __global__ void k_ba_reset(BaPool pool, const unsigned char* flags, int open_slo
 // k_ba_compute reads a pool record or a map while the reset kernels rewrite them.  The caller orders the map-maker streams behind
 // the reset in turn (sys->ev_reset).
 int ba_reset_streams(vslam_system* sys, const unsigned char* d_flags) {
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   for (size_t i = 0; i < sys->ba_streams.size(); i++) {
     HIPCHK(hipEventRecord(sys->ev_reset_ba[i], sys->ba_streams[i]));
     HIPCHK(hipStreamWaitEvent(sys->stream, sys->ev_reset_ba[i], 0));
@@ -857,7 +854,7 @@ int ba_reset_streams(vslam_system* sys, const unsigned char* d_flags) {
 // explicit (host-driven) map-maker calls first collect a bundle adjustment that is still in flight
 static int ba_drain(vslam_system* sys) {
   if (sys->tp.ba_delay <= 0) return VSLAM_OK;
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   { int rs = ba_sync_streams(sys); if (rs) return rs; }
   hipLaunchKernelGGL(k_ba_writeback, dim3(sys->S), dim3(BA_THREADS), 0, sys->stream, sys->map, sys->tp, ws->pool, BaWriteback::Drain);
   HIPCHK(hipGetLastError());
@@ -883,7 +880,7 @@ int ba_launch_add_keyframe(vslam_system* sys) { return ba_add_keyframe_prologue(
 // collected in one work list and launched together; successive launches go to a ring of streams and may overlap.
 // A launch walks exactly its batch's list -- never a problem a later frame's k_ba_assemble is writing beside it.
 static int ba_adjust_keyframe_async(vslam_system* sys, int token) {
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   const int R = (int)sys->ev_ba.size(), slot = (int)(sys->ba_batch_id % R);
   hipStream_t bs = sys->ba_streams[(size_t)(sys->ba_batch_id % (long)sys->ba_streams.size())];
   hipLaunchKernelGGL(k_ba_select, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->tp, ws->pool, BaJob::Keyframe, token);
@@ -909,7 +906,7 @@ static int ba_adjust_keyframe_async(vslam_system* sys, int token) {
 // adjusted here and now even when the tracker-driven ones run on the map-maker streams (the pending ones were collected by the
 // caller): the kernels see ba_delay = 0.
 static int ba_adjust_now(vslam_system* sys, BaJob job, bool host_driven_keyframe, int token) {
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   const bool keyframe = job == BaJob::Keyframe;          // part of a frame: its stages are profiled
   const bool timed = (ba_job_on_request(job) || host_driven_keyframe) && sys->ev_mm[0];
   TrackParams tps = sys->tp;
@@ -966,7 +963,7 @@ int mm_idle(vslam_system* sys) {
 
 extern "C" int vslam_get_bundle_stats(vslam_system* sys, int s, int out[6]) {
   if (!sys || !out || s < 0 || s >= sys->S || !sys->ba_ws) { vslam_set_error("get_bundle_stats: bad argument"); return VSLAM_E_INVALID; }
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   HIPCHK(hipStreamSynchronize(sys->stream));
   { int rs = ba_sync_streams(sys); if (rs) return rs; }
   BaResult r;
@@ -977,7 +974,7 @@ extern "C" int vslam_get_bundle_stats(vslam_system* sys, int s, int out[6]) {
 
 // ---- measurement ----------------------------------------------------------------------------------------------------
 static int ba_read_launch_record(vslam_system* sys, int rec, unsigned long long out[BA_LSTAT_N]) {
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   HIPCHK(hipMemcpy(out, ws->pool.lstat + (size_t)rec * BA_LSTAT_N, sizeof(unsigned long long) * BA_LSTAT_N, hipMemcpyDeviceToHost));
   return VSLAM_OK;
 }
@@ -1006,7 +1003,7 @@ extern "C" int vslam_get_ba_launch_totals(vslam_system* sys, unsigned long long 
   if (!sys || !stats || !sys->ba_ws) { vslam_set_error("get_ba_launch_totals: bad argument"); return VSLAM_E_INVALID; }
   HIPCHK(hipStreamSynchronize(sys->stream));
   { int rs = ba_sync_streams(sys); if (rs) return rs; }
-  BaSystemWs* ws = (BaSystemWs*)sys->ba_ws;
+  BaSystemWs* ws = sys->ba_ws;
   const long n = sys->ba_launch_no < BA_LSTAT_RING ? sys->ba_launch_no : BA_LSTAT_RING;
   std::vector<unsigned long long> all((size_t)BA_LSTAT_RING * BA_LSTAT_N);
   HIPCHK(hipMemcpy(all.data(), ws->pool.lstat, sizeof(unsigned long long) * all.size(), hipMemcpyDeviceToHost));

@@ -556,13 +556,12 @@ int boot_alloc(vslam_system* sys) {
   sys->map.trail_patch = nullptr; sys->map.trail_pos = nullptr; sys->map.boot_match = nullptr; sys->map.boot_inl = nullptr; sys->map.boot_ws = nullptr;
   if (!sys->p.bootstrap) return VSLAM_OK;
   const size_t S = sys->S, P = sys->p.max_points;
-  auto get = [&](size_t bytes, void** out) -> int { void* q = nullptr; HIPCHK(hipMalloc(&q, bytes + 64)); HIPCHK(hipMemsetAsync(q, 0, bytes + 64, sys->stream)); sys->allocs.push_back(q); *out = q; return VSLAM_OK; };
-  int r;
-  if ((r = get(S * 2 * BOOT_MAX_TRAILS * MPP, (void**)&sys->map.trail_patch))) return r;
-  if ((r = get(S * 2 * BOOT_MAX_TRAILS * 4 * sizeof(int), (void**)&sys->map.trail_pos))) return r;
-  if ((r = get(S * BOOT_MAX_TRAILS * 8 * sizeof(double), (void**)&sys->map.boot_match))) return r;
-  if ((r = get(S * BOOT_MAX_TRAILS * sizeof(int), (void**)&sys->map.boot_inl))) return r;
-  if ((r = get(S * boot_ws_stride(P) * sizeof(double), (void**)&sys->map.boot_ws))) return r;
+  DevOwner& own = sys->own; hipStream_t q = sys->stream;
+  VCHK(own.alloc(&sys->map.trail_patch, S * 2 * BOOT_MAX_TRAILS * MPP, q));
+  VCHK(own.alloc(&sys->map.trail_pos, S * 2 * BOOT_MAX_TRAILS * 4, q));
+  VCHK(own.alloc(&sys->map.boot_match, S * BOOT_MAX_TRAILS * 8, q));
+  VCHK(own.alloc(&sys->map.boot_inl, S * BOOT_MAX_TRAILS, q));
+  VCHK(own.alloc(&sys->map.boot_ws, S * boot_ws_stride(P), q));
   return VSLAM_OK;
 }
 
@@ -692,10 +691,6 @@ extern "C" int vslam_get_trails(vslam_system* sys, int stream, int* out4, int ca
 
 // ---- the two stages on their own (vslam_probe_homography_init, vslam_probe_plane_aligner) ------------------------------------
 namespace {
-struct ProbeBuf {            // device memory of one probe call
-  void* p = nullptr;
-  ~ProbeBuf() { if (p) (void)hipFree(p); }
-};
 // a probe works in the stream's InitFromStereo slices: not inside a frame, not while the stream's trails are running
 int probe_admissible(vslam_system* sys, int stream, const char* who) {
   if (!sys->p.bootstrap) { vslam_set_error("%s: created with bootstrap = 0", who); return VSLAM_E_STATE; }
@@ -714,8 +709,8 @@ extern "C" int vslam_probe_homography_init(vslam_system* sys, int stream, int n,
   int r = probe_admissible(sys, stream, "probe_homography_init"); if (r) return r;
   static_assert(VSLAM_PROBE_MAX_MATCHES == BOOT_MAX_TRAILS && sizeof(bm::Match) == 8 * sizeof(double), "vslam_homography_probe holds a stream's match slice");
   const size_t off_scores = sizeof(bm::HomographyStages), off_pos = off_scores + 300 * sizeof(double);
-  ProbeBuf buf;
-  HIPCHK(hipMalloc(&buf.p, off_pos + sizeof(int) * 4 * (size_t)(n > 0 ? n : 1)));
+  DevTemp<char> buf;
+  HIPCHK(buf.get(off_pos + sizeof(int) * 4 * (size_t)(n > 0 ? n : 1)));
   hipStream_t q = sys->stream;
   HIPCHK(hipMemsetAsync(buf.p, 0, off_pos, q));
   int* d_pos = nullptr;
@@ -746,8 +741,8 @@ extern "C" int vslam_probe_plane_aligner(vslam_system* sys, int stream, int n, c
   if (n > sys->p.max_points) { vslam_set_error("probe_plane_aligner: at most max_points = %d points", sys->p.max_points); return VSLAM_E_CAPACITY; }
   int r = probe_admissible(sys, stream, "probe_plane_aligner"); if (r) return r;
   const size_t off_sums = sizeof(bm::PlaneStages);
-  ProbeBuf buf;
-  HIPCHK(hipMalloc(&buf.p, off_sums + 100 * sizeof(double)));
+  DevTemp<char> buf;
+  HIPCHK(buf.get(off_sums + 100 * sizeof(double)));
   hipStream_t q = sys->stream;
   HIPCHK(hipMemsetAsync(buf.p, 0, off_sums + 100 * sizeof(double), q));
   if (n > 0) HIPCHK(hipMemcpyAsync(sys->map.boot_ws + (size_t)stream * boot_ws_stride((size_t)sys->p.max_points), pos3, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, q));

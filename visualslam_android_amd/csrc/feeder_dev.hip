@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/vslam_feeder.h"
 #include "feeder_internal.h"
+#include "vslam_internal.h"   // DevTemp
 
 using namespace feeder_detail;
 
@@ -104,29 +105,23 @@ extern "C" int vslam_feeder_render_device(const vslam_feeder* const* feeders, in
       k[(size_t)i * count + j] = (keys ? keys[(size_t)i * count + j] : (uint64_t)(first + j + 100000)) ^ (feeders[i]->seed << 20);
   }
   if (hipSetDevice(device) != hipSuccess) return -2;
-  float *d_lat = nullptr, *d_rays = nullptr;
-  int* d_rects = nullptr;
-  double* d_poses = nullptr;
-  uint64_t* d_keys = nullptr;
-  uint8_t* d_tex = nullptr;
+  DevTemp<float> d_lat, d_rays; DevTemp<int> d_rects; DevTemp<double> d_poses; DevTemp<uint64_t> d_keys; DevTemp<uint8_t> d_tex;
   int rc = 0;
-  if (hipMalloc(&d_lat, lat.size() * sizeof(float)) != hipSuccess || hipMalloc(&d_rects, rects.size() * sizeof(int)) != hipSuccess ||
-      hipMalloc(&d_rays, f0->rays.size() * sizeof(float)) != hipSuccess || hipMalloc(&d_poses, (size_t)n * count * 12 * sizeof(double)) != hipSuccess ||
-      hipMalloc(&d_keys, k.size() * sizeof(uint64_t)) != hipSuccess || hipMalloc(&d_tex, (size_t)n * TEX * TEX) != hipSuccess) {
+  if (d_lat.get(lat.size()) != hipSuccess || d_rects.get(rects.size()) != hipSuccess || d_rays.get(f0->rays.size()) != hipSuccess ||
+      d_poses.get((size_t)n * count * 12) != hipSuccess || d_keys.get(k.size()) != hipSuccess || d_tex.get((size_t)n * TEX * TEX) != hipSuccess) {
     rc = -3;
-  } else if (hipMemcpy(d_lat, lat.data(), lat.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-             hipMemcpy(d_rects, rects.data(), rects.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
-             hipMemcpy(d_rays, f0->rays.data(), f0->rays.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-             hipMemcpy(d_poses, poses, (size_t)n * count * 12 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-             hipMemcpy(d_keys, k.data(), k.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
+  } else if (hipMemcpy(d_lat.p, lat.data(), lat.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(d_rects.p, rects.data(), rects.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(d_rays.p, f0->rays.data(), f0->rays.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(d_poses.p, poses, (size_t)n * count * 12 * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(d_keys.p, k.data(), k.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
     rc = -4;
   } else {
-    hipLaunchKernelGGL(k_feeder_noise, dim3((unsigned)(((size_t)TEX * TEX + 255) / 256), n), dim3(256), 0, 0, d_lat, d_tex);
-    hipLaunchKernelGGL(k_feeder_rects, dim3(n), dim3(1024), 0, 0, d_rects, nrect, d_tex);
-    hipLaunchKernelGGL(k_feeder_render, dim3((unsigned)((w * h + 255) / 256), count, n), dim3(256), 0, 0, d_tex, d_rays, d_poses, d_keys,
+    hipLaunchKernelGGL(k_feeder_noise, dim3((unsigned)(((size_t)TEX * TEX + 255) / 256), n), dim3(256), 0, 0, d_lat.p, d_tex.p);
+    hipLaunchKernelGGL(k_feeder_rects, dim3(n), dim3(1024), 0, 0, d_rects.p, nrect, d_tex.p);
+    hipLaunchKernelGGL(k_feeder_render, dim3((unsigned)((w * h + 255) / 256), count, n), dim3(256), 0, 0, d_tex.p, d_rays.p, d_poses.p, d_keys.p,
                        w, h, f0->noise, count, out, feeder_stride, frame_stride);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = -4;
   }
-  (void)hipFree(d_lat); (void)hipFree(d_rects); (void)hipFree(d_rays); (void)hipFree(d_poses); (void)hipFree(d_keys); (void)hipFree(d_tex);
   return rc;
 }

@@ -318,7 +318,7 @@ extern "C" const char* vslam_stage_name(int stage) { return stage >= 0 && stage 
 extern "C" int vslam_profile_begin(vslam_system* sys, int max_frames) {
   if (!sys || max_frames < 1) return VSLAM_E_INVALID;
   HIPCHK(hipStreamSynchronize(sys->stream));
-  while ((int)sys->prof_ev.size() < max_frames * PROF_MARKS) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); sys->prof_ev.push_back(e); }
+  while ((int)sys->prof_ev.size() < max_frames * PROF_MARKS) { hipEvent_t e; VCHK(sys->own.event(&e, true)); sys->prof_ev.push_back(e); }
   sys->prof_cap = max_frames; sys->prof_frame = 0; sys->prof_on = true;
   sys->prof_ba_launched.assign((size_t)max_frames, 0);
   return VSLAM_OK;

@@ -492,31 +492,15 @@ static bool keeps_kf_corners(const vslam_system* sys) { return sys->p.grow_map !
 int grow_alloc(vslam_system* sys) {
   sys->map.never_retry = nullptr; sys->map.fq = nullptr;
   if (!keeps_kf_corners(sys)) return VSLAM_OK;
-  if (sys->p.idle_iterations != 0) {
-    void* q = nullptr;
-    HIPCHK(hipMalloc(&q, (size_t)sys->S * sys->p.max_points * 2 * sizeof(unsigned long long) + 64));
-    HIPCHK(hipMemsetAsync(q, 0, (size_t)sys->S * sys->p.max_points * 2 * sizeof(unsigned long long) + 64, sys->stream));
-    sys->allocs.push_back(q); sys->map.never_retry = (unsigned long long*)q;
-    q = nullptr;
-    HIPCHK(hipMalloc(&q, (size_t)sys->S * sys->tp.fq_cap * sizeof(int2) + 64));
-    sys->allocs.push_back(q); sys->map.fq = (int2*)q;
-  }
+  DevOwner& own = sys->own; hipStream_t q = sys->stream;
   const size_t S = sys->S, K = sys->p.max_keyframes;
-  for (int l = 0; l < NLEV; l++) {
-    void* ptr = nullptr;
-    HIPCHK(hipMalloc(&ptr, S * K * (size_t)sys->tp.kcap[l] * sizeof(uint32_t) + 64));
-    sys->allocs.push_back(ptr);
-    sys->map.kf_corners[l] = (uint32_t*)ptr;
+  if (sys->p.idle_iterations != 0) {
+    VCHK(own.alloc(&sys->map.never_retry, S * sys->p.max_points * 2, q));
+    VCHK(own.alloc(&sys->map.fq, S * sys->tp.fq_cap, q));
   }
-  void* ptr = nullptr;
-  HIPCHK(hipMalloc(&ptr, S * K * NLEV * sizeof(int) + 64));
-  HIPCHK(hipMemsetAsync(ptr, 0, S * K * NLEV * sizeof(int) + 64, sys->stream));
-  sys->allocs.push_back(ptr);
-  sys->map.kf_ncorners = (int*)ptr;
-  ptr = nullptr;
-  HIPCHK(hipMalloc(&ptr, S * (size_t)sys->tp.kcap[0] * 2 * sizeof(double) + 64));
-  sys->allocs.push_back(ptr);
-  sys->grow_implane = (double*)ptr;
+  for (int l = 0; l < NLEV; l++) VCHK(own.alloc(&sys->map.kf_corners[l], S * K * (size_t)sys->tp.kcap[l], q));
+  VCHK(own.alloc(&sys->map.kf_ncorners, S * K * NLEV, q));
+  VCHK(own.alloc(&sys->grow_implane, S * (size_t)sys->tp.kcap[0] * 2, q));
   return VSLAM_OK;
 }
 

@@ -77,28 +77,19 @@ __global__ __launch_bounds__(64) void k_minipatch_find(const uint8_t* img, int p
   }
 }
 
-static int mp_buffers(vslam_system* sys, int n, int** d_pos, uint8_t** d_patch, int** d_flag) {
-  void *a = nullptr, *b = nullptr, *c = nullptr;
-  HIPCHK(hipMalloc(&a, sizeof(int) * 2 * (size_t)n + 64));
-  HIPCHK(hipMalloc(&b, (size_t)MP_PIX * n + 64));
-  HIPCHK(hipMalloc(&c, sizeof(int) * (size_t)n + 64));
-  *d_pos = (int*)a; *d_patch = (uint8_t*)b; *d_flag = (int*)c;
-  return VSLAM_OK;
-}
-
 extern "C" int vslam_minipatch_sample(vslam_system* sys, int stream, int n, const int* pos_xy, uint8_t* patches, int* ok) {
   if (!sys || stream < 0 || stream >= sys->S || n < 0 || (n && (!pos_xy || !patches || !ok))) { vslam_set_error("minipatch_sample: bad argument"); return VSLAM_E_INVALID; }
   if (!sys->have_frame) { vslam_set_error("minipatch_sample: no current frame"); return VSLAM_E_STATE; }
   if (n == 0) return VSLAM_OK;
-  int* d_pos; uint8_t* d_patch; int* d_ok;
-  int r = mp_buffers(sys, n, &d_pos, &d_patch, &d_ok); if (r) return r;
+  DevTemp<int> pos, flag; DevTemp<uint8_t> patch;      // of this call, each with 64 bytes of slack
+  HIPCHK(pos.get(2 * (size_t)n + 16)); HIPCHK(patch.get((size_t)MP_PIX * n + 64)); HIPCHK(flag.get((size_t)n + 16));
+  int* d_pos = pos.p; uint8_t* d_patch = patch.p; int* d_ok = flag.p;
   HIPCHK(hipMemcpyAsync(d_pos, pos_xy, sizeof(int) * 2 * n, hipMemcpyHostToDevice, sys->stream));
   hipLaunchKernelGGL(k_minipatch_sample, dim3(n), dim3(128), 0, sys->stream, sys->fr.img[0] + (size_t)stream * sys->fr.img_sstride[0],
                      sys->fr.img_pitch[0], sys->geom[0].w, sys->geom[0].h, d_pos, n, d_patch, d_ok);
   HIPCHK(hipMemcpyAsync(patches, d_patch, (size_t)MP_PIX * n, hipMemcpyDeviceToHost, sys->stream));
   HIPCHK(hipMemcpyAsync(ok, d_ok, sizeof(int) * n, hipMemcpyDeviceToHost, sys->stream));
   HIPCHK(hipStreamSynchronize(sys->stream));
-  (void)hipFree(d_pos); (void)hipFree(d_patch); (void)hipFree(d_ok);
   return VSLAM_OK;
 }
 
@@ -107,8 +98,9 @@ extern "C" int vslam_minipatch_find(vslam_system* sys, int stream, int n, const 
   if (!sys || stream < 0 || stream >= sys->S || n < 0 || range < 0 || (n && (!pos_xy || !patches || !found))) { vslam_set_error("minipatch_find: bad argument"); return VSLAM_E_INVALID; }
   if (!sys->have_frame) { vslam_set_error("minipatch_find: no current frame"); return VSLAM_E_STATE; }
   if (n == 0) return VSLAM_OK;
-  int* d_pos; uint8_t* d_patch; int* d_found;
-  int r = mp_buffers(sys, n, &d_pos, &d_patch, &d_found); if (r) return r;
+  DevTemp<int> pos, flag; DevTemp<uint8_t> patch;      // of this call, each with 64 bytes of slack
+  HIPCHK(pos.get(2 * (size_t)n + 16)); HIPCHK(patch.get((size_t)MP_PIX * n + 64)); HIPCHK(flag.get((size_t)n + 16));
+  int* d_pos = pos.p; uint8_t* d_patch = patch.p; int* d_found = flag.p;
   int nc = 0;
   HIPCHK(hipMemcpyAsync(&nc, sys->fr.ncorners + stream * NLEV, sizeof(int), hipMemcpyDeviceToHost, sys->stream));
   HIPCHK(hipMemcpyAsync(d_pos, pos_xy, sizeof(int) * 2 * n, hipMemcpyHostToDevice, sys->stream));
@@ -121,6 +113,5 @@ extern "C" int vslam_minipatch_find(vslam_system* sys, int stream, int n, const 
   HIPCHK(hipMemcpyAsync(pos_xy, d_pos, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, sys->stream));
   HIPCHK(hipMemcpyAsync(found, d_found, sizeof(int) * n, hipMemcpyDeviceToHost, sys->stream));
   HIPCHK(hipStreamSynchronize(sys->stream));
-  (void)hipFree(d_pos); (void)hipFree(d_patch); (void)hipFree(d_found);
   return VSLAM_OK;
 }

@@ -125,14 +125,9 @@ int reloc_alloc(vslam_system* sys) {
   if (!sys->p.relocalise) return VSLAM_OK;
   const size_t S = sys->S, K = sys->p.max_keyframes, N = small_pixels(sys);
   if (N > SBI_MAX_PIX) { vslam_set_error("relocalise: small image of %d pixels exceeds %d", (int)N, SBI_MAX_PIX); return VSLAM_E_INVALID; }
-  struct { void** p; size_t bytes; } v[] = {
-    {(void**)&sys->reloc.kf_tmpl, S * K * N * sizeof(float)}, {(void**)&sys->reloc.kf_jacs, S * K * N * 2 * sizeof(float)},
-    {(void**)&sys->reloc.cur_tmpl, S * N * sizeof(float)}, {(void**)&sys->reloc.scores, S * K * sizeof(double)}, {(void**)&sys->reloc.info, S * sizeof(RelocInfo)}};
-  for (auto& e : v) {
-    HIPCHK(hipMalloc(e.p, e.bytes));
-    sys->allocs.push_back(*e.p);
-    HIPCHK(hipMemsetAsync(*e.p, 0, e.bytes, sys->stream));
-  }
+  DevOwner& own = sys->own; hipStream_t q = sys->stream;
+  VCHK(own.alloc(&sys->reloc.kf_tmpl, S * K * N, q)); VCHK(own.alloc(&sys->reloc.kf_jacs, S * K * N * 2, q));
+  VCHK(own.alloc(&sys->reloc.cur_tmpl, S * N, q)); VCHK(own.alloc(&sys->reloc.scores, S * K, q)); VCHK(own.alloc(&sys->reloc.info, S, q));
   return VSLAM_OK;
 }
 

@@ -72,27 +72,19 @@ __global__ void k_reset_state(MapDev m, int S, const unsigned char* flags, int* 
 #define RESET_RING 4
 
 int reset_alloc(vslam_system* sys) {
-  int r = dev_alloc(sys, &sys->reset_flags, (size_t)sys->S); if (r) return r;
-  r = dev_alloc(sys, &sys->reset_info, (size_t)sys->S * 4); if (r) return r;
-  if (sys->p.use_sbi) { r = dev_alloc(sys, &sys->sbi_restart, (size_t)sys->S); if (r) return r; }
+  DevOwner& own = sys->own;
+  VCHK(own.alloc(&sys->reset_flags, (size_t)sys->S, sys->stream));
+  VCHK(own.alloc(&sys->reset_info, (size_t)sys->S * 4, sys->stream));
+  if (sys->p.use_sbi) VCHK(own.alloc(&sys->sbi_restart, (size_t)sys->S, sys->stream));
   for (int q = 0; q < RESET_RING; q++) {
-    HIPCHK(hipHostMalloc((void**)&sys->reset_stage[q], (size_t)sys->S, hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&sys->ev_reset_stage[q], hipEventDisableTiming));
+    VCHK(own.pinned((void**)&sys->reset_stage[q], (size_t)sys->S));
+    VCHK(own.event(&sys->ev_reset_stage[q], false));
   }
-  HIPCHK(hipEventCreateWithFlags(&sys->ev_reset, hipEventDisableTiming));
-  for (int k = 0; k < 2; k++) HIPCHK(hipEventCreate(&sys->ev_reset_t[k]));
-  for (size_t i = 0; i < sys->ba_streams.size(); i++) { hipEvent_t e = nullptr; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); sys->ev_reset_ba.push_back(e); }
+  VCHK(own.event(&sys->ev_reset, false));
+  for (int k = 0; k < 2; k++) VCHK(own.event(&sys->ev_reset_t[k], true));
+  sys->ev_reset_ba.assign(sys->ba_streams.size(), nullptr);
+  for (hipEvent_t& e : sys->ev_reset_ba) VCHK(own.event(&e, false));
   return VSLAM_OK;
-}
-
-void reset_free(vslam_system* sys) {
-  for (int q = 0; q < RESET_RING; q++) {
-    if (sys->reset_stage[q]) (void)hipHostFree(sys->reset_stage[q]);
-    if (sys->ev_reset_stage[q]) (void)hipEventDestroy(sys->ev_reset_stage[q]);
-  }
-  if (sys->ev_reset) (void)hipEventDestroy(sys->ev_reset);
-  for (int k = 0; k < 2; k++) if (sys->ev_reset_t[k]) (void)hipEventDestroy(sys->ev_reset_t[k]);
-  for (hipEvent_t e : sys->ev_reset_ba) (void)hipEventDestroy(e);
 }
 
 extern "C" int vslam_reset_streams(vslam_system* sys, const int* streams, int n) {

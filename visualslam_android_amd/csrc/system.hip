@@ -57,7 +57,82 @@ extern "C" int vslam_default_params(vslam_params* p, int width, int height, int 
   return VSLAM_OK;
 }
 
-#define ALLOC(ptr, count) do { int _r = dev_alloc(sys, &(ptr), (count)); if (_r) { vslam_destroy(sys); return _r; } } while (0)
+// Everything a new handle acquires, through its owner; vslam_create gives a handle that failed here to vslam_destroy.
+static int sys_acquire(vslam_system* sys) {
+  const vslam_params* p = &sys->p;
+  DevOwner& own = sys->own;
+  // (default priorities: the tracker's stream at the highest priority, with or without the front end's at the lowest, was measured at
+  // 3072 streams: 376 k against 398-400 k frames/s -- the front end of frame t+1 then finishes late and the tracker waits for it)
+  VCHK(own.stream(&sys->stream));
+  hipStream_t q = sys->stream;
+  const int S = sys->S;
+  {
+    int ncu = 0;
+    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess && ncu > 0) sys->n_cu = ncu;
+  }
+  VCHK(own.stream(&sys->fe_stream));
+  for (int b = 0; b < 2; b++) { VCHK(own.event(&sys->ev_fe_done[b], false)); VCHK(own.event(&sys->ev_track_done[b], false)); }
+  for (int k = 0; k < 4; k++) VCHK(own.event(&sys->ev_mm[k], true));
+  for (int l = 0; l < NLEV; l++) {
+    LevelGeom& g = sys->geom[l];
+    g.w = p->width >> l; g.h = p->height >> l;
+    g.pitch = (g.w + 63) & ~63;
+    g.nchunk = (g.w + 63) >> 6;
+    g.cap = p->max_corners[l];
+    g.thr = p->fast_threshold[l];
+  }
+  for (int b = 0; b < 2; b++) {
+    FrameDev& fr = sys->frbuf[b];
+    for (int l = 0; l < NLEV; l++) {
+      const LevelGeom& g = sys->geom[l];
+      VCHK(own.alloc(&sys->d_lvl_buf[b][l], (size_t)S * g.pitch * g.h, q));
+      VCHK(own.alloc(&fr.cmask[l], (size_t)S * g.h * g.nchunk, q));
+      VCHK(own.alloc(&fr.rowcnt[l], (size_t)S * g.h, q));
+      VCHK(own.alloc(&fr.rowlut[l], (size_t)S * (g.h + 1), q));
+      VCHK(own.alloc(&fr.corners[l], (size_t)S * g.cap, q));
+      VCHK(own.alloc(&fr.scores[l], (size_t)S * g.cap, q));
+      VCHK(own.alloc(&fr.maxcorners[l], (size_t)S * g.cap, q));
+      fr.img[l] = sys->d_lvl_buf[b][l];
+      fr.img_sstride[l] = (size_t)g.pitch * g.h;
+      fr.img_pitch[l] = g.pitch;
+    }
+    {
+      const size_t ns = (size_t)(sys->geom[3].w / 2) * (sys->geom[3].h / 2);
+      VCHK(own.alloc(&fr.sbi_small, (size_t)S * ns, q)); VCHK(own.alloc(&fr.sbi_tmpl, (size_t)S * ns, q));
+      VCHK(own.alloc(&fr.sbi_jacs, (size_t)S * ns * 2, q)); VCHK(own.alloc(&fr.sbi_rot, (size_t)S * 8, q));
+    }
+    VCHK(own.alloc(&fr.ncorners, (size_t)S * NLEV, q));
+    VCHK(own.alloc(&fr.nmax, (size_t)S * NLEV, q));
+    VCHK(own.alloc(&fr.overflow, 1, q));
+  }
+  for (int l = 0; l < NLEV; l++) { VCHK(own.alloc(&sys->cand[l], (size_t)S * sys->geom[l].cap, q)); VCHK(own.alloc(&sys->cand_score[l], (size_t)S * sys->geom[l].cap, q)); }
+  VCHK(own.alloc(&sys->ncand, (size_t)S * NLEV, q));
+  sys->have_candidates = false;
+  sys->have_sbi = false;
+  if (p->ba_delay_frames > 0) {
+    // (default priority: giving the map-maker's streams the lowest one was measured -- the adjustments then finish late and the
+    // frames that apply them wait: 215 k against 243 k frames/s; the highest one changes nothing: 340 k either way at 2048 streams)
+    sys->ba_streams.assign(p->ba_delay_frames < 8 ? p->ba_delay_frames : 8, nullptr);
+    for (hipStream_t& st : sys->ba_streams) VCHK(own.stream(&st));
+    sys->ba_stream = sys->ba_streams[0];
+    sys->frame_batch.assign((size_t)p->ba_delay_frames + 2, -1L);
+    sys->ev_asm.assign((size_t)p->ba_delay_frames + 2, nullptr); sys->ev_ba = sys->ev_asm;
+    for (size_t i = 0; i < sys->ev_asm.size(); i++) { VCHK(own.event(&sys->ev_asm[i], false)); VCHK(own.event(&sys->ev_ba[i], false)); }
+  }
+  sys->fr_idx = 0;
+  sys->fr = sys->frbuf[0];
+  for (int l = 0; l < NLEV; l++) sys->d_lvl[l] = sys->d_lvl_buf[0][l];
+  VCHK(trk_alloc(sys));
+  VCHK(ba_alloc(sys));
+  VCHK(grow_alloc(sys));
+  VCHK(boot_alloc(sys));
+  VCHK(reloc_alloc(sys));
+  VCHK(reset_alloc(sys));
+  HIPCHK(hipStreamSynchronize(q));
+  VCHK(map_init_states(sys));
+  HIPCHK(hipStreamSynchronize(q));       // the zeroing contract (DevOwner::alloc): from here on the memory is zero for every stream
+  return VSLAM_OK;
+}
 
 extern "C" int vslam_create(const vslam_params* p, vslam_system** out) {
   if (!p || !out) { vslam_set_error("create: null argument"); return VSLAM_E_INVALID; }
@@ -85,111 +160,16 @@ extern "C" int vslam_create(const vslam_params* p, vslam_system** out) {
   sys->p = *p;
   sys->S = p->n_streams;
   sys->have_frame = false;
-  sys->stream = nullptr;
-  // (default priorities: the tracker's stream at the highest priority, with or without the front end's at the lowest, was measured at
-  // 3072 streams: 376 k against 398-400 k frames/s -- the front end of frame t+1 then finishes late and the tracker waits for it)
-  if (hipStreamCreateWithFlags(&sys->stream, hipStreamNonBlocking) != hipSuccess) {
-    vslam_set_error("create: hipStreamCreate failed"); delete sys; return VSLAM_E_HIP;
-  }
-  const int S = sys->S;
-  {
-    int ncu = 0;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess && ncu > 0) sys->n_cu = ncu;
-  }
-  if (hipStreamCreateWithFlags(&sys->fe_stream, hipStreamNonBlocking) != hipSuccess) { vslam_set_error("create: hipStreamCreate failed"); vslam_destroy(sys); return VSLAM_E_HIP; }
-  for (int b = 0; b < 2; b++) {
-    if (hipEventCreateWithFlags(&sys->ev_fe_done[b], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sys->ev_track_done[b], hipEventDisableTiming) != hipSuccess) { vslam_set_error("create: hipEventCreate failed"); vslam_destroy(sys); return VSLAM_E_HIP; }
-  }
-  for (int k = 0; k < 4; k++)
-    if (hipEventCreate(&sys->ev_mm[k]) != hipSuccess) { vslam_set_error("create: hipEventCreate failed"); vslam_destroy(sys); return VSLAM_E_HIP; }
-  for (int l = 0; l < NLEV; l++) {
-    LevelGeom& g = sys->geom[l];
-    g.w = p->width >> l; g.h = p->height >> l;
-    g.pitch = (g.w + 63) & ~63;
-    g.nchunk = (g.w + 63) >> 6;
-    g.cap = p->max_corners[l];
-    g.thr = p->fast_threshold[l];
-  }
-  for (int b = 0; b < 2; b++) {
-    FrameDev& fr = sys->frbuf[b];
-    for (int l = 0; l < NLEV; l++) {
-      const LevelGeom& g = sys->geom[l];
-      ALLOC(sys->d_lvl_buf[b][l], (size_t)S * g.pitch * g.h);
-      ALLOC(fr.cmask[l], (size_t)S * g.h * g.nchunk);
-      ALLOC(fr.rowcnt[l], (size_t)S * g.h);
-      ALLOC(fr.rowlut[l], (size_t)S * (g.h + 1));
-      ALLOC(fr.corners[l], (size_t)S * g.cap);
-      ALLOC(fr.scores[l], (size_t)S * g.cap);
-      ALLOC(fr.maxcorners[l], (size_t)S * g.cap);
-      fr.img[l] = sys->d_lvl_buf[b][l];
-      fr.img_sstride[l] = (size_t)g.pitch * g.h;
-      fr.img_pitch[l] = g.pitch;
-    }
-    {
-      const size_t ns = (size_t)(sys->geom[3].w / 2) * (sys->geom[3].h / 2);
-      ALLOC(fr.sbi_small, (size_t)S * ns); ALLOC(fr.sbi_tmpl, (size_t)S * ns); ALLOC(fr.sbi_jacs, (size_t)S * ns * 2); ALLOC(fr.sbi_rot, (size_t)S * 8);
-    }
-    ALLOC(fr.ncorners, (size_t)S * NLEV);
-    ALLOC(fr.nmax, (size_t)S * NLEV);
-    ALLOC(fr.overflow, 1);
-  }
-  for (int l = 0; l < NLEV; l++) { ALLOC(sys->cand[l], (size_t)S * sys->geom[l].cap); ALLOC(sys->cand_score[l], (size_t)S * sys->geom[l].cap); }
-  ALLOC(sys->ncand, (size_t)S * NLEV);
-  sys->have_candidates = false;
-  sys->have_sbi = false;
-  if (p->ba_delay_frames > 0) {
-    const int nb = p->ba_delay_frames < 8 ? p->ba_delay_frames : 8;
-    for (int i = 0; i < nb; i++) {
-      hipStream_t st = nullptr;
-      // (default priority: giving the map-maker's streams the lowest one was measured -- the adjustments then finish late and the
-      // frames that apply them wait: 215 k against 243 k frames/s; the highest one changes nothing: 340 k either way at 2048 streams)
-      if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { vslam_set_error("create: hipStreamCreate failed"); vslam_destroy(sys); return VSLAM_E_HIP; }
-      sys->ba_streams.push_back(st);
-    }
-    sys->ba_stream = sys->ba_streams[0];
-    sys->frame_batch.assign((size_t)p->ba_delay_frames + 2, -1L);
-    for (int i = 0; i < p->ba_delay_frames + 2; i++) {
-      hipEvent_t a = nullptr, b = nullptr;
-      if (hipEventCreateWithFlags(&a, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&b, hipEventDisableTiming) != hipSuccess) { vslam_set_error("create: hipEventCreate failed"); vslam_destroy(sys); return VSLAM_E_HIP; }
-      sys->ev_asm.push_back(a); sys->ev_ba.push_back(b);
-    }
-  }
-  sys->fr_idx = 0;
-  sys->fr = sys->frbuf[0];
-  for (int l = 0; l < NLEV; l++) sys->d_lvl[l] = sys->d_lvl_buf[0][l];
-  sys->ba_ws = nullptr;
-  {
-    int r = trk_alloc(sys);
-    if (!r) r = ba_alloc(sys);
-    if (!r) r = grow_alloc(sys);
-    if (!r) r = boot_alloc(sys);
-    if (!r) r = reloc_alloc(sys);
-    if (!r) r = reset_alloc(sys);
-    if (!r && hipStreamSynchronize(sys->stream) != hipSuccess) r = VSLAM_E_HIP;
-    if (!r) r = map_init_states(sys);
-    if (r) { vslam_destroy(sys); return r; }
-  }
-  if (hipStreamSynchronize(sys->stream) != hipSuccess) { vslam_set_error("create: sync failed"); vslam_destroy(sys); return VSLAM_E_HIP; }
+  const int r = sys_acquire(sys);
+  if (r) { vslam_destroy(sys); return r; }
   *out = sys;
   return VSLAM_OK;
 }
 
 extern "C" int vslam_destroy(vslam_system* sys) {
   if (!sys) return VSLAM_OK;
-  if (sys->fe_stream) (void)hipStreamSynchronize(sys->fe_stream);
-  for (hipStream_t st : sys->ba_streams) (void)hipStreamSynchronize(st);
-  if (sys->stream) (void)hipStreamSynchronize(sys->stream);
-  for (hipEvent_t e : sys->ev_asm) (void)hipEventDestroy(e);
-  for (hipEvent_t e : sys->ev_ba) (void)hipEventDestroy(e);
-  for (hipStream_t st : sys->ba_streams) (void)hipStreamDestroy(st);
-  for (void* p : sys->allocs) (void)hipFree(p);
-  reset_free(sys);
-  for (hipEvent_t e : sys->prof_ev) (void)hipEventDestroy(e);
-  for (int k = 0; k < 4; k++) if (sys->ev_mm[k]) (void)hipEventDestroy(sys->ev_mm[k]);
-  for (int b = 0; b < 2; b++) { if (sys->ev_fe_done[b]) (void)hipEventDestroy(sys->ev_fe_done[b]); if (sys->ev_track_done[b]) (void)hipEventDestroy(sys->ev_track_done[b]); }
-  if (sys->fe_stream) (void)hipStreamDestroy(sys->fe_stream);
-  if (sys->stream) (void)hipStreamDestroy(sys->stream);
+  sys->own.release();
+  ba_free(sys);
   delete sys;
   return VSLAM_OK;
 }
@@ -343,18 +323,12 @@ extern "C" int vslam_eval_transcendental(int fn, int n, const double* x, double*
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { vslam_set_error("eval_transcendental: no HIP device visible"); return VSLAM_E_HIP; }
   if (n == 0) return VSLAM_OK;
-  double *dx = nullptr, *dy = nullptr;
-  auto run = [&]() -> int {
-    HIPCHK(hipMalloc((void**)&dx, sizeof(double) * n));
-    HIPCHK(hipMalloc((void**)&dy, sizeof(double) * n));
-    HIPCHK(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_eval_transcendental, dim3((n + 255) / 256), dim3(256), 0, 0, fn, n, dx, dy);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(y, dy, sizeof(double) * n, hipMemcpyDeviceToHost));
-    return VSLAM_OK;
-  };
-  const int rc = run();
-  if (dx) (void)hipFree(dx);
-  if (dy) (void)hipFree(dy);
-  return rc;
+  DevTemp<double> dx, dy;
+  HIPCHK(dx.get(n));
+  HIPCHK(dy.get(n));
+  HIPCHK(hipMemcpy(dx.p, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_eval_transcendental, dim3((n + 255) / 256), dim3(256), 0, 0, fn, n, (const double*)dx.p, dy.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(y, dy.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return VSLAM_OK;
 }

@@ -1245,19 +1245,17 @@ extern "C" int vslam_debug_pose_prof(unsigned long long* out16, int reset) {
 #endif
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-#define TALLOC(ptr, count) do { int _r = dev_alloc(sys, &(ptr), (count)); if (_r) return _r; } while (0)
-
 int trk_alloc(vslam_system* sys) {
   const vslam_params& p = sys->p;
   const size_t S = sys->S, P = p.max_points, K = p.max_keyframes;
   if (P > SORT_CAP) { vslam_set_error("max_points %d exceeds %d", (int)P, SORT_CAP); return VSLAM_E_INVALID; }
-  MapDev& m = sys->map;
-  TALLOC(m.pts, S * P); TALLOC(m.td, S * P); TALLOC(m.tmpl, S * P * TMPL_PITCH);
-  TALLOC(m.kf_meas, S * K * P); TALLOC(m.cur_meas, S * P);
-  TALLOC(m.kf_pose, S * K); TALLOC(m.kf_fixed, S * K); TALLOC(m.kf_depth, S * K * 2);
-  for (int l = 0; l < NLEV; l++) TALLOC(m.kf_img[l], S * K * (size_t)sys->geom[l].pitch * sys->geom[l].h);
-  TALLOC(m.st, S); TALLOC(m.pvs_list, S * NLEV * P); TALLOC(m.search_list, S * P); TALLOC(m.iter_list, S * P); TALLOC(m.pt_level, S * P); TALLOC(m.pt_flags, S * P);
-  TALLOC(m.pose_ws, S * POSE_WS_COMPS * P); TALLOC(m.pose_wsi, S * 2 * P);
+  MapDev& m = sys->map; DevOwner& own = sys->own; hipStream_t q = sys->stream;
+  VCHK(own.alloc(&m.pts, S * P, q)); VCHK(own.alloc(&m.td, S * P, q)); VCHK(own.alloc(&m.tmpl, S * P * TMPL_PITCH, q));
+  VCHK(own.alloc(&m.kf_meas, S * K * P, q)); VCHK(own.alloc(&m.cur_meas, S * P, q));
+  VCHK(own.alloc(&m.kf_pose, S * K, q)); VCHK(own.alloc(&m.kf_fixed, S * K, q)); VCHK(own.alloc(&m.kf_depth, S * K * 2, q));
+  for (int l = 0; l < NLEV; l++) VCHK(own.alloc(&m.kf_img[l], S * K * (size_t)sys->geom[l].pitch * sys->geom[l].h, q));
+  VCHK(own.alloc(&m.st, S, q)); VCHK(own.alloc(&m.pvs_list, S * NLEV * P, q)); VCHK(own.alloc(&m.search_list, S * P, q)); VCHK(own.alloc(&m.iter_list, S * P, q)); VCHK(own.alloc(&m.pt_level, S * P, q)); VCHK(own.alloc(&m.pt_flags, S * P, q));
+  VCHK(own.alloc(&m.pose_ws, S * POSE_WS_COMPS * P, q)); VCHK(own.alloc(&m.pose_wsi, S * 2 * P, q));
   trk_fill_params(p, sys->tp);
   return VSLAM_OK;
 }
@@ -1432,20 +1430,14 @@ extern "C" int vslam_pvs_permutation(unsigned seed, int frame, int list, int n, 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { vslam_set_error("pvs_permutation: no HIP device visible"); return VSLAM_E_HIP; }
   if (n == 0) return VSLAM_OK;
-  unsigned* dk = nullptr; int* dout = nullptr;
-  auto run = [&]() -> int {
-    HIPCHK(hipMalloc((void**)&dout, sizeof(int) * n));
-    if (keys_or_null) {
-      HIPCHK(hipMalloc((void**)&dk, sizeof(unsigned) * n));
-      HIPCHK(hipMemcpy(dk, keys_or_null, sizeof(unsigned) * n, hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_pvs_permutation, dim3(1), dim3(TRK_THREADS), 0, 0, seed, frame, list, n, (const unsigned*)dk, dout);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(out, dout, sizeof(int) * n, hipMemcpyDeviceToHost));
-    return VSLAM_OK;
-  };
-  const int rc = run();
-  if (dk) (void)hipFree(dk);
-  if (dout) (void)hipFree(dout);
-  return rc;
+  DevTemp<unsigned> dk; DevTemp<int> dout;
+  HIPCHK(dout.get(n));
+  if (keys_or_null) {
+    HIPCHK(dk.get(n));
+    HIPCHK(hipMemcpy(dk.p, keys_or_null, sizeof(unsigned) * n, hipMemcpyHostToDevice));
+  }
+  hipLaunchKernelGGL(k_pvs_permutation, dim3(1), dim3(TRK_THREADS), 0, 0, seed, frame, list, n, (const unsigned*)dk.p, dout.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dout.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+  return VSLAM_OK;
 }

@@ -21,6 +21,9 @@ void vslam_set_error(const char* fmt, ...);
     }                                                                                        \
   } while (0)
 
+// a failed call inside csrc/ has set the error string: pass its status up
+#define VCHK(expr) do { int _r = (expr); if (_r) return _r; } while (0)
+
 // the C ABI's pose12 (R row-major, then t) <-> Pose
 static inline Pose pose_from12(const double* q) { Pose p; for (int i = 0; i < 9; i++) p.R[i] = q[i]; for (int i = 0; i < 3; i++) p.t[i] = q[9 + i]; return p; }
 static inline void pose_to12(const Pose& p, double* q) { for (int i = 0; i < 9; i++) q[i] = p.R[i]; for (int i = 0; i < 3; i++) q[9 + i] = p.t[i]; }
@@ -202,10 +205,69 @@ struct RelocDev {             // all null with relocalise = 0
   RelocInfo* info;          // [S]
 };
 
+// What a handle holds on the device: device memory, pinned host memory, streams and events.  Every acquisition of a handle goes through
+// its owner and nothing else in csrc/ creates, frees or destroys one of these, so one release() gives everything back -- after a
+// destroy and after a create that failed half way alike.  Each acquiring method sets the error string and returns VSLAM_E_HIP on failure.
+struct DevOwner {
+  enum Kind : int { MEM, PINNED, STREAM, EVENT };
+  struct Held { Kind kind; void* h; };
+  std::vector<Held> held;      // in order of acquisition
+  // count zeroed elements of T (and 64 bytes of slack) in HBM.  The zeroing contract, stated once: the memory is zero for every stream
+  // once vslam_create / vslam_bundle_create has returned (both end with a wait for zero_on); inside create it is zero only for work
+  // queued behind it on zero_on.
+  template <class T> int alloc(T** out, size_t count, hipStream_t zero_on) {
+    void* ptr = nullptr;
+    HIPCHK(hipMalloc(&ptr, count * sizeof(T) + 64));
+    held.push_back({MEM, ptr});
+    HIPCHK(hipMemsetAsync(ptr, 0, count * sizeof(T) + 64, zero_on));
+    *out = (T*)ptr;
+    return VSLAM_OK;
+  }
+  int pinned(void** out, size_t bytes) {
+    HIPCHK(hipHostMalloc(out, bytes, hipHostMallocDefault));
+    held.push_back({PINNED, *out});
+    return VSLAM_OK;
+  }
+  int stream(hipStream_t* out) {
+    HIPCHK(hipStreamCreateWithFlags(out, hipStreamNonBlocking));
+    held.push_back({STREAM, *out});
+    return VSLAM_OK;
+  }
+  int event(hipEvent_t* out, bool timing) {
+    HIPCHK(hipEventCreateWithFlags(out, timing ? hipEventDefault : hipEventDisableTiming));
+    held.push_back({EVENT, *out});
+    return VSLAM_OK;
+  }
+  // waits for its streams, then gives everything back in reverse order of acquisition (the streams, acquired first, go last); idempotent
+  void release() {
+    for (const Held& x : held) if (x.kind == STREAM) (void)hipStreamSynchronize((hipStream_t)x.h);
+    for (size_t i = held.size(); i-- > 0;) {
+      const Held& x = held[i];
+      if (x.kind == MEM) (void)hipFree(x.h);
+      else if (x.kind == PINNED) (void)hipHostFree(x.h);
+      else if (x.kind == EVENT) (void)hipEventDestroy((hipEvent_t)x.h);
+      else (void)hipStreamDestroy((hipStream_t)x.h);
+    }
+    held.clear();
+  }
+};
+
+// A device buffer that lives for one call: freed when it goes out of scope, on every return path.  Not zeroed.
+template <class T> struct DevTemp {
+  T* p = nullptr;
+  DevTemp() = default;
+  DevTemp(const DevTemp&) = delete;
+  DevTemp& operator=(const DevTemp&) = delete;
+  ~DevTemp() { if (p) (void)hipFree(p); }
+  hipError_t get(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)); }
+};
+
+struct BaSystemWs;             // bundle-adjustment workspace (ba.hip)
+
 struct vslam_system {
   vslam_params p;
   int S;
-  hipStream_t stream;
+  hipStream_t stream = nullptr;
   LevelGeom geom[NLEV];
   FrameDev fr;                 // view of the CURRENT frame's front-end products (= frbuf[fr_idx])
   uint8_t* d_lvl[NLEV];        // owned level images of the current buffer (level 0 = staging copy for host input)
@@ -232,7 +294,7 @@ struct vslam_system {
   long ba_launch_no = 0;       // k_ba_compute launches of this system so far (ring index of the launch records)
   hipEvent_t ev_mm[4] = {nullptr, nullptr, nullptr, nullptr};   // host-driven BundleAdjustRecent / All: before select+assemble, compute, write-back, after
   int mm_lrec = -1;            // launch record of the last host-driven call
-  std::vector<void*> allocs;   // everything to hipFree
+  DevOwner own;               // everything the handle holds on the device; vslam_destroy releases it
   bool have_frame;
   bool frame_open = false;  // stage-wise TrackFrame (vslam_patch_search ... vslam_finish_frame) in progress
   bool have_sbi;            // a SmallBlurryImage of a previous frame exists (mpSBILastFrame)
@@ -252,24 +314,13 @@ struct vslam_system {
   bool boot_key_pressed = false;   // vslam_press_spacebar since the last frame: that frame launches the start / InitFromStereo pipelines
   TrackParams tp;
   MapDev map;
-  void* ba_ws;                 // bundle-adjustment workspace (ba.hip)
+  BaSystemWs* ba_ws = nullptr; // bundle-adjustment workspace (ba.hip): ba_alloc makes it, ba_free deletes it
   RelocDev reloc = {nullptr, nullptr, nullptr, nullptr, nullptr};
   // per-stage HIP-event timing of vslam_track_frame (vslam_profile_begin/end)
   std::vector<hipEvent_t> prof_ev;
   int prof_cap = 0, prof_frame = 0;
   bool prof_on = false;
 };
-
-// count zeroed elements of T (and 64 bytes of slack) in HBM, owned by the handle
-template <class T>
-static inline int dev_alloc(vslam_system* sys, T** out, size_t count) {
-  void* ptr = nullptr;
-  HIPCHK(hipMalloc(&ptr, count * sizeof(T) + 64));
-  HIPCHK(hipMemsetAsync(ptr, 0, count * sizeof(T) + 64, sys->stream));
-  sys->allocs.push_back(ptr);
-  *out = (T*)ptr;
-  return VSLAM_OK;
-}
 
 // The profile's stages, in the order of vslam_stage_name (kStageNames, map.hip); a stage's mark is the event at its start, and
 // PROF_FRAME_END, the mark after the last stage, closes the frame.
@@ -359,6 +410,7 @@ DEVFN int* ba_job_idle_counter(BaJob j, TrackerState* st) {   // the counter of 
   return j == BaJob::IdleRecent ? &st->n_ba_recent_idle : j == BaJob::IdleAll ? &st->n_ba_all : nullptr;
 }
 int ba_alloc(vslam_system* sys);
+void ba_free(vslam_system* sys);          // the host-side workspace (its device memory is the owner's)
 int ba_add_keyframe_and_adjust(vslam_system* sys);
 int ba_run(vslam_system* sys, BaJob job, bool host_driven_keyframe = false);
 int ba_frame_start(vslam_system* sys);    // asynchronous map-maker: apply the results that are due at this frame
@@ -373,5 +425,4 @@ int ba_reset_streams(vslam_system* sys, const unsigned char* d_flags);   // the 
 int map_init_states(vslam_system* sys);
 // reset.hip
 int reset_alloc(vslam_system* sys);
-void reset_free(vslam_system* sys);
 
