@@ -138,6 +138,10 @@ class MapMaker {
   // :1254-1286 "SaveMap": map.dump and keyframes/<i>.info below `dir` (the reference writes to the working directory)
   void GUICommandHandler(const std::string& sCommand, const std::string& dir = ".") {
     if (sCommand == "SaveMap") vslam_detail::check(vslam_save_map(mMap.sys, 0, dir.c_str()));
+    // beside it, not in the reference: the whole stream (Map, jni/Map.h:21-34, with the Tracker's and MapMaker's members) as
+    // <dir>/stream.snap, bit for bit (vslam_save_stream / vslam_load_stream)
+    else if (sCommand == "SaveState") vslam_detail::check(vslam_save_stream(mMap.sys, 0, (dir + "/stream.snap").c_str()));
+    else if (sCommand == "LoadState") vslam_detail::check(vslam_load_stream(mMap.sys, 0, (dir + "/stream.snap").c_str()));
     else throw std::runtime_error("MapMaker::GUICommandHandler: unhandled command " + sCommand);
   }
  protected:

@@ -250,6 +250,60 @@ int vslam_get_reset_info(vslam_system* sys, int stream, int out[4]);
  * (asynchronous map-maker) and the reset kernels.  Synchronises.  VSLAM_E_STATE before the first call. */
 int vslam_get_reset_timing(vslam_system* sys, double* ms);
 
+/* ---- stream snapshots ------------------------------------------------------------------------
+ * One stream taken out of a live batch whole, and put back bit for bit into any slot of any compatible system.  The reference's only
+ * persistence is MapMaker::GUICommandHandler("SaveMap") (jni/MapMaker.cc:1254-1286, vslam_save_map below: positions and poses at six
+ * digits); what a snapshot carries is the Map itself (jni/Map.h:21-34: vpPoints, vpKeyFrames, bGood) with everything of the Tracker and
+ * the MapMaker that a later frame or a per-stream read-back depends on: the tracker state, the map points with their PatchFinder state
+ * and cached templates, the measurement tables, keyframe poses, depths and pyramids, the last frame's iteration set, and where the source
+ * keeps them the never-retry sets and the failure queue (idle jobs), the last frame's SmallBlurryImage (use_sbi) and the relocaliser's
+ * record (relocalise).  Keyframe corner lists and keyframe SmallBlurryImages are not carried: the restore remakes them from the stored
+ * pyramids exactly as the map upload does, so a blob of a system without grow_map / relocalise restores into one with it.  Not carried: the
+ * frame's own front-end products, vslam_get_reset_info, profiles and timings, and the bundle-adjustment pool record (vslam_get_bundle_stats
+ * is a new stream's until the next adjustment).  From its next frame on the restored stream produces the bits the source stream produces
+ * had it gone on.  The blob is compact (the counts in use, dense image rows), independent of the source's capacities, stream count and
+ * slot, and has no checksum; csrc/snapshot_format.h states its layout.
+ *
+ * Refused with VSLAM_E_STATE: while a stage-wise frame is open; while the stream's trails are running (mnInitialStage
+ * TRAIL_TRACKING_STARTED: the trail tracker reads the previous frame in place); while an adjustment of the asynchronous map-maker is
+ * pending for the stream (the call succeeds once it has landed). */
+/* (the struct cannot share the function's name: typedef names and functions live in one C name space) */
+typedef struct vslam_snapshot_desc {
+  int version, width, height, patch_size;
+  double cam[5];
+  int quirks;
+  int n_keyframes, n_points, frame, map_good;
+  int has_idle_state, has_sbi, has_reloc_state;          /* the optional parts */
+  unsigned long long total_bytes;
+  /* keyframe k's level-l image starts at image_offset[l] + k * image_stride[l]; its rows are image_row_stride[l] (= width >> l) bytes apart */
+  unsigned long long image_offset[VSLAM_LEVELS], image_row_stride[VSLAM_LEVELS], image_stride[VSLAM_LEVELS];
+  unsigned long long point_pos_offset;                   /* n_points x 3 doubles, MapPoint::v3WorldPos */
+  unsigned long long keyframe_pose_offset;               /* n_keyframes x 12 doubles, pose12 layout */
+} vslam_snapshot_desc;
+/* *bytes = the size of the blob the stream's present state packs to.  Synchronises. */
+int vslam_snapshot_size(vslam_system* sys, int stream, size_t* bytes);
+/* Packs the stream on the device, then makes one copy to dst (host memory, or device memory with dst_on_device != 0).  Synchronises.
+ * *bytes (may be NULL) is set to the blob's size whenever the stream can be packed, that is on success and on VSLAM_E_CAPACITY (cap too
+ * small; dst is not written); a call refused with VSLAM_E_STATE or VSLAM_E_INVALID leaves it alone.  The failure queue travels sorted by
+ * (keyframe, point) -- its order in memory is no part of the state -- and at most its capacity's entries of it. */
+int vslam_snapshot_stream(vslam_system* sys, int stream, void* dst, size_t cap, int dst_on_device, size_t* bytes);
+/* The slot first becomes what vslam_reset_streams makes it (a pending adjustment of the asynchronous map-maker is abandoned, and
+ * vslam_get_reset_info counts the call), then receives the blob.  Ordered on the system's stream; a host blob is consumed before the call
+ * returns.  Not asynchronous: the blob's header is read on the host first, and with keyframe corner lists (grow_map, idle jobs) the host
+ * waits once per keyframe while they are remade, as in the map upload.  The blob's width, height, patch size, cam[5] and quirks must equal the system's, and the bytes must be a well-formed snapshot:
+ * otherwise VSLAM_E_INVALID.  More keyframes or points (or failure-queue entries) than the system's capacities: VSLAM_E_CAPACITY.  A
+ * refused call changes nothing.  The other streams are not touched. */
+int vslam_restore_stream(vslam_system* sys, int stream, const void* blob, size_t bytes, int on_device);
+/* Pure host code, no GPU and no system: validates magic, version, total size and every section of a blob in host memory against `bytes`
+ * (VSLAM_E_INVALID otherwise) and describes it. */
+int vslam_snapshot_info(const void* blob, size_t bytes, vslam_snapshot_desc* out);
+/* The blob to and from a file. */
+int vslam_save_stream(vslam_system* sys, int stream, const char* path);
+int vslam_load_stream(vslam_system* sys, int stream, const char* path);
+/* ms[0], ms[1] = HIP-event milliseconds of the last pack (the kernel) and of the last unpack (the reset, the kernel and the remaking of
+ * the derived keyframe data) on the system's stream; 0 for one that has not run.  Synchronises. */
+int vslam_get_snapshot_timing(vslam_system* sys, double ms[2]);
+
 /* ---- tracking ------------------------------------------------------------------------------ */
 
 typedef struct vslam_track_state {

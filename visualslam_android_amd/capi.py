@@ -46,6 +46,15 @@ class TrackState(C.Structure):
                 ("n_zmssd", C.c_longlong), ("n_ba_trials", C.c_longlong)]
 
 
+class SnapshotInfo(C.Structure):
+    """Mirror of struct vslam_snapshot_desc (what vslam_snapshot_info fills)."""
+    _fields_ = [("version", C.c_int), ("width", C.c_int), ("height", C.c_int), ("patch_size", C.c_int), ("cam", C.c_double * 5),
+                ("quirks", C.c_int), ("n_keyframes", C.c_int), ("n_points", C.c_int), ("frame", C.c_int), ("map_good", C.c_int),
+                ("has_idle_state", C.c_int), ("has_sbi", C.c_int), ("has_reloc_state", C.c_int), ("total_bytes", C.c_ulonglong),
+                ("image_offset", C.c_ulonglong * LEVELS), ("image_row_stride", C.c_ulonglong * LEVELS), ("image_stride", C.c_ulonglong * LEVELS),
+                ("point_pos_offset", C.c_ulonglong), ("keyframe_pose_offset", C.c_ulonglong)]
+
+
 PROBE_MAX_MATCHES = 1000
 
 
@@ -108,6 +117,13 @@ SYMBOLS = {
     "vslam_reset_streams": (_i, [_sys, _vp, _i]),
     "vslam_get_reset_info": (_i, [_sys, _i, _vp]),
     "vslam_get_reset_timing": (_i, [_sys, C.POINTER(_d)]),
+    "vslam_snapshot_size": (_i, [_sys, _i, C.POINTER(_sz)]),
+    "vslam_snapshot_stream": (_i, [_sys, _i, _vp, _sz, _i, C.POINTER(_sz)]),
+    "vslam_restore_stream": (_i, [_sys, _i, _vp, _sz, _i]),
+    "vslam_snapshot_info": (_i, [_vp, _sz, C.POINTER(SnapshotInfo)]),
+    "vslam_save_stream": (_i, [_sys, _i, C.c_char_p]),
+    "vslam_load_stream": (_i, [_sys, _i, C.c_char_p]),
+    "vslam_get_snapshot_timing": (_i, [_sys, _vp]),
     "vslam_track_frame": (_i, [_sys, _vp, _sz, _sz, _i]),
     "vslam_update": (_i, [_sys, _vp, _sz, _sz]),
     "vslam_patch_search": (_i, [_sys, _i]),
@@ -216,6 +232,14 @@ def read_map_dump(directory):
         poses.append(np.concatenate([m[:, :3].reshape(-1), m[:, 3]]))
         k += 1
     return a[:, :3], a[:, 3].astype(np.int32), np.array(poses).reshape(-1, 12)
+
+
+def snapshot_info(blob):
+    """vslam_snapshot_info: validates a snapshot held in host memory (bytes or a uint8 array) and describes it -> SnapshotInfo.  Host code only."""
+    a = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8)
+    out = SnapshotInfo()
+    _check(load_library().vslam_snapshot_info(a.ctypes.data if a.size else None, a.size, C.byref(out)))
+    return out
 
 
 def default_params(width, height, n_streams=1, **overrides):
@@ -420,6 +444,45 @@ class System:
         ms = C.c_double(0.0)
         _check(self.lib.vslam_get_reset_timing(self.h, C.byref(ms)))
         return ms.value
+
+    # ---- stream snapshots --------------------------------------------------------------------
+    def snapshot_size(self, stream):
+        n = _sz(0)
+        _check(self.lib.vslam_snapshot_size(self.h, stream, C.byref(n)))
+        return n.value
+
+    def snapshot(self, stream, out=None):
+        """The stream whole, as a blob (vslam_snapshot_stream) -> uint8 array.  out: a device pointer (int) with its capacity, as
+        (ptr, cap): the blob is written there and its size returned."""
+        n = _sz(0)
+        if out is not None:
+            _check(self.lib.vslam_snapshot_stream(self.h, stream, int(out[0]), int(out[1]), 1, C.byref(n)))
+            return n.value
+        buf = np.empty(self.snapshot_size(stream), np.uint8)
+        _check(self.lib.vslam_snapshot_stream(self.h, stream, buf.ctypes.data, buf.size, 0, C.byref(n)))
+        return buf[:n.value]
+
+    def restore(self, stream, blob, nbytes=None):
+        """vslam_restore_stream: blob is a uint8 array / bytes in host memory, or a device pointer (int) with nbytes"""
+        if isinstance(blob, int):
+            _check(self.lib.vslam_restore_stream(self.h, stream, blob, int(nbytes), 1))
+            return
+        a = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8)
+        _check(self.lib.vslam_restore_stream(self.h, stream, a.ctypes.data if a.size else None, a.size, 0))
+
+    snapshot_info = staticmethod(snapshot_info)
+
+    def save_stream(self, stream, path):
+        _check(self.lib.vslam_save_stream(self.h, stream, os.fsencode(path)))
+
+    def load_stream(self, stream, path):
+        _check(self.lib.vslam_load_stream(self.h, stream, os.fsencode(path)))
+
+    def snapshot_timing(self):
+        """-> HIP-event ms of the last pack and of the last unpack on the system's stream (vslam_get_snapshot_timing)"""
+        ms = np.zeros(2)
+        _check(self.lib.vslam_get_snapshot_timing(self.h, ms.ctypes.data))
+        return float(ms[0]), float(ms[1])
 
     # ---- tracking ----------------------------------------------------------------------------
     def track_frame(self, gray):

@@ -128,6 +128,7 @@ static int sys_acquire(vslam_system* sys) {
   VCHK(boot_alloc(sys));
   VCHK(reloc_alloc(sys));
   VCHK(reset_alloc(sys));
+  VCHK(snapshot_alloc(sys));
   HIPCHK(hipStreamSynchronize(q));
   VCHK(map_init_states(sys));
   HIPCHK(hipStreamSynchronize(q));       // the zeroing contract (DevOwner::alloc): from here on the memory is zero for every stream

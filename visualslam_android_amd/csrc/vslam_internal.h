@@ -311,6 +311,9 @@ struct vslam_system {
   hipEvent_t ev_reset_t[2] = {nullptr, nullptr};   // around the last call's work on the system's stream (vslam_get_reset_timing)
   hipEvent_t ev_reset = nullptr;             // the reset kernels are done (the front-end and map-maker streams wait for it)
   std::vector<hipEvent_t> ev_reset_ba;       // one per map-maker stream: what it held when the reset was called
+  // vslam_snapshot_stream / vslam_restore_stream (snapshot.hip)
+  hipEvent_t ev_snap_t[4] = {nullptr, nullptr, nullptr, nullptr};   // around the last pack [0, 1] and the last unpack [2, 3] on the system's stream
+  bool snap_timed[2] = {false, false};       // a pack / an unpack has run
   bool boot_key_pressed = false;   // vslam_press_spacebar since the last frame: that frame launches the start / InitFromStereo pipelines
   TrackParams tp;
   MapDev map;
@@ -425,4 +428,6 @@ int ba_reset_streams(vslam_system* sys, const unsigned char* d_flags);   // the 
 int map_init_states(vslam_system* sys);
 // reset.hip
 int reset_alloc(vslam_system* sys);
+// snapshot.hip
+int snapshot_alloc(vslam_system* sys);
 
