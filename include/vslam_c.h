@@ -347,6 +347,33 @@ int vslam_finish_frame(vslam_system* sys);
  * TrackMap and AssessTrackingQuality only (no motion model, no keyframe).  The other streams are not touched.  Does nothing with
  * vslam_params.relocalise = 0.  vslam_track_frame calls it.  Asynchronous. */
 int vslam_attempt_recovery(vslam_system* sys);
+/* ---- subset steps: only the streams that have a new frame ----
+ * One step for the n streams listed (distinct indices, any order); image i, at gray + i*stream_stride, belongs to streams[i].
+ * The other streams of the batch are HELD: this step does not exist for them.  Every read-back of a held stream's tracker and map
+ * returns the bytes it returned before the step (vslam_get_state with frame, kf_added, attempted / found and n_zmssd,
+ * vslam_get_point_tracks, vslam_get_points, keyframe poses and measurements, templates, vslam_get_search_plan, vslam_get_idle_stats,
+ * vslam_get_reloc_info, vslam_read_sbi, vslam_get_init_info); it makes no keyframe, runs no bundle adjustment and no idle pass, makes
+ * no recovery attempt and no trail step; a pending spacebar stays pending, its shuffle seed and boot seed stay.  With the asynchronous
+ * map-maker ba_delay_frames counts the stream's own frames: a pending result lands at the start of its D-th own frame after the
+ * keyframe.  With use_sbi the rotation prior of its next frame aligns to its own last frame.
+ * vslam_track_frame_subset is exactly vslam_make_keyframe_lite_subset, vslam_attempt_recovery, vslam_patch_search(0), vslam_pose_update(0),
+ * vslam_patch_search(1), vslam_pose_update(1), vslam_finish_frame: after vslam_make_keyframe_lite_subset the stage-wise calls act on the
+ * subset until the frame is finished.  n == 0 is a valid step in which nothing moves (streams and gray may then be NULL).
+ * Every image is copied into the system's own level-0 storage, from the host (on_device = 0) or from device memory.
+ * The step's front-end products of a held stream do not exist: vslam_read_level_image, vslam_read_corners, vslam_read_row_lut,
+ * vslam_read_max_corners, vslam_read_candidates, vslam_minipatch_sample, vslam_minipatch_find and vslam_add_keyframe(stream) return
+ * VSLAM_E_STATE for it; vslam_fast_nonmax, vslam_make_keyframe_rest, vslam_thin_candidates(keyframe < 0) and vslam_add_keyframe(-1) act
+ * on the streams of the step.  Between steps nothing is special about a held stream.
+ * VSLAM_E_INVALID: n < 0, n > n_streams, an index outside the batch, a duplicate index, NULL gray with n > 0.  VSLAM_E_STATE: a
+ * stage-wise frame is open; or the step would hold a stream whose bootstrap trails are running (init_stage 1: it reads the previous
+ * frame's level 0 in place, so its frames must be consecutive steps).  On systems created with bootstrap = 1 the call synchronises
+ * once to read the stages; other systems do not synchronise.  A refused call changes nothing.  Asynchronous otherwise. */
+int vslam_make_keyframe_lite_subset(vslam_system* sys, const int* streams, int n, const uint8_t* gray, size_t row_stride,
+                                    size_t stream_stride, int on_device);
+int vslam_track_frame_subset(vslam_system* sys, const int* streams, int n, const uint8_t* gray, size_t row_stride,
+                             size_t stream_stride, int on_device);
+/* in_step[n_streams] = 1 for the streams of the current / last step (all ones after a full step) */
+int vslam_get_step_streams(vslam_system* sys, unsigned char* in_step);
 /* the JNI-equivalent per-frame entry: native_update (jni/jni_part.cpp:132-145): host gray image of stream 0..n-1,
  * synchronous; native_touchScreen (:120-124) = the spacebar of every stream: with vslam_params.bootstrap it starts the trails / runs
  * InitFromStereo on the next frame of the streams that have no map, otherwise (and once a map exists) it has no effect. */

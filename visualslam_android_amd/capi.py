@@ -129,6 +129,9 @@ SYMBOLS = {
     "vslam_patch_search": (_i, [_sys, _i]),
     "vslam_pose_update": (_i, [_sys, _i]),
     "vslam_finish_frame": (_i, [_sys]),
+    "vslam_make_keyframe_lite_subset": (_i, [_sys, _vp, _i, _vp, _sz, _sz, _i]),
+    "vslam_track_frame_subset": (_i, [_sys, _vp, _i, _vp, _sz, _sz, _i]),
+    "vslam_get_step_streams": (_i, [_sys, _vp]),
     "vslam_map_set_point_positions": (_i, [_sys, _i, _i, _i, _vp]),
     "vslam_map_set_keyframe_pose": (_i, [_sys, _i, _i, _vp]),
     "vslam_touch": (_i, [_sys]),
@@ -323,6 +326,43 @@ class System:
 
     def make_keyframe_lite_device(self, dev_ptr, row_stride, stream_stride):
         _check(self.lib.vslam_make_keyframe_lite(self.h, dev_ptr, row_stride, stream_stride, 1))
+
+    # ---- subset steps: only the listed streams move, the others are held --------------------------
+    def _subset(self, streams, gray):
+        idx = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        g = np.ascontiguousarray(gray, dtype=np.uint8)
+        if g.ndim == 2:
+            g = g[None]
+        assert g.shape == (len(idx), self.params.height, self.params.width), g.shape
+        return idx, g
+
+    def make_keyframe_lite_subset(self, streams, gray):
+        """streams: n distinct stream indices, gray: uint8 [n, H, W] (host), image i for streams[i]; the other streams are held."""
+        idx, g = self._subset(streams, gray)
+        _check(self.lib.vslam_make_keyframe_lite_subset(self.h, idx.ctypes.data if len(idx) else None, len(idx),
+                                                        g.ctypes.data if len(idx) else None, g.shape[2], g.shape[1] * g.shape[2], 0))
+        self.synchronize()  # the host buffers are only borrowed for the call
+
+    def make_keyframe_lite_subset_device(self, streams, dev_ptr, row_stride, stream_stride):
+        idx = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        _check(self.lib.vslam_make_keyframe_lite_subset(self.h, idx.ctypes.data if len(idx) else None, len(idx), dev_ptr, row_stride, stream_stride, 1))
+
+    def track_frame_subset(self, streams, gray):
+        """One step for the listed streams on host frames [n, H, W]; synchronous."""
+        idx, g = self._subset(streams, gray)
+        _check(self.lib.vslam_track_frame_subset(self.h, idx.ctypes.data if len(idx) else None, len(idx),
+                                                 g.ctypes.data if len(idx) else None, g.shape[2], g.shape[1] * g.shape[2], 0))
+        self.synchronize()
+
+    def track_frame_subset_device(self, streams, dev_ptr, row_stride, stream_stride):
+        idx = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        _check(self.lib.vslam_track_frame_subset(self.h, idx.ctypes.data if len(idx) else None, len(idx), dev_ptr, row_stride, stream_stride, 1))
+
+    def step_streams(self):
+        """-> uint8 [S]: 1 for the streams of the current / last step"""
+        out = np.zeros(self.S, dtype=np.uint8)
+        _check(self.lib.vslam_get_step_streams(self.h, out.ctypes.data))
+        return out
 
     def fast_nonmax(self):
         _check(self.lib.vslam_fast_nonmax(self.h))

@@ -403,7 +403,7 @@ struct KfCopyArgs {
 __global__ __launch_bounds__(256) void k_add_keyframe(MapDev m, TrackParams tp, KfCopyArgs a) {
   const int s = blockIdx.y;
   TrackerState* st = &m.st[s];
-  if (!st->kf_pending) return;
+  if (!trk_kf_pending(m.held, s, st)) return;
   const int slot = st->n_kf;                         // n_kf is advanced by k_ba_assemble (next launch)
   const int nth = gridDim.x * blockDim.x, tid = blockIdx.x * blockDim.x + threadIdx.x;
   for (int l = 0; l < NLEV; l++) {                   // Level::operator= copies pixels (jni/KeyFrame.cc:104-112)
@@ -451,7 +451,7 @@ DEVFN double kfdist(const Pose& a, const Pose& b) {   // KeyFrameLinearDist :705
 // on the map-maker's stream beside the following frames: nothing it reads changes while the stream's adjustment is pending.
 __global__ __launch_bounds__(64) void k_ba_select(MapDev m, TrackParams tp, BaPool pool, BaJob job, int token) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s >= pool.N) return;
+  if (s >= pool.N || !trk_in_step(m.held, s)) return;   // a held stream takes part in no job of the step; its pool record stays as it is
   TrackerState* st = &m.st[s];
   const BaView v = ba_view(pool, s);
   BaResult* R = v.res;
@@ -642,6 +642,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_writeback(MapDev m, TrackPara
   MapPointDev* pts = m.pts + (size_t)s * P;
   MeasDev* kfm = m.kf_meas + (size_t)s * K * P;
   __shared__ int sh_due;
+  if (!trk_in_step(m.held, s)) return;                    // a held stream: no countdown tick (the delay counts its own frames), no write-back
   if (wb == BaWriteback::Boot && !st->boot_run) return;   // InitFromStereo's adjustments: only the streams it runs for
   const bool all = wb == BaWriteback::All || wb == BaWriteback::Boot;
   if (wb == BaWriteback::IfDue || wb == BaWriteback::Drain) {   // asynchronous map-maker: is this stream's pending result due?
@@ -720,7 +721,7 @@ __global__ __launch_bounds__(BA_THREADS) void k_ba_writeback(MapDev m, TrackPara
 __global__ __launch_bounds__(BA_THREADS) void k_handle_bad_points(MapDev m, TrackParams tp) {
   const int s = blockIdx.x;
   const TrackerState* st = &m.st[s];
-  if (!st->map_good) return;
+  if (!trk_in_step(m.held, s) || !st->map_good) return;
   const int P = tp.max_points, K = tp.max_keyframes;
   handle_bad_points(st, m.pts + (size_t)s * P, m.kf_meas + (size_t)s * K * P, P);
 }
@@ -1036,6 +1037,7 @@ __global__ void k_request_keyframe(MapDev m, TrackParams tp, int S, int stream) 
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
   TrackerState* st = &m.st[s];
+  if (!trk_in_step(m.held, s)) return;
   const bool want = (stream < 0 || s == stream) && st->map_good && st->n_kf < tp.max_keyframes;
   st->kf_pending = want ? 1 : 0;                      // a request left over from the last frame has been served already
   if (want) st->last_kf_dropped = st->frame;          // Tracker::AddNewKeyFrame, jni/Tracker.cc:823-827
@@ -1044,6 +1046,7 @@ __global__ void k_request_keyframe(MapDev m, TrackParams tp, int S, int stream) 
 extern "C" int vslam_add_keyframe(vslam_system* sys, int stream) {
   if (!sys || stream >= sys->S) { vslam_set_error("add_keyframe: bad argument"); return VSLAM_E_INVALID; }
   if (!sys->have_frame) { vslam_set_error("add_keyframe: no current frame"); return VSLAM_E_STATE; }
+  if (stream >= 0) { int r = fe_stream_in_step(sys, stream, "add_keyframe"); if (r) return r; }
   { int r = ba_drain(sys); if (r) return r; }        // asynchronous map-maker: collect the adjustments in flight first
   hipLaunchKernelGGL(k_request_keyframe, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->tp, sys->S, stream);
   return ba_run(sys, BaJob::Keyframe, true);

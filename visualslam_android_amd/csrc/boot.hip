@@ -47,6 +47,7 @@ DEVFN int* trail_positions(const MapDev& m, int s, int buf) { return m.trail_pos
 __global__ void k_boot_gate(MapDev m, int S) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
+  if (!trk_in_step(m.held, s)) return;                               // a held stream: its spacebar stays pending, its flags stay
   TrackerState* st = &m.st[s];
   st->kf_pending = 0;
   st->boot_action = 0;
@@ -61,7 +62,7 @@ __global__ void k_boot_gate(MapDev m, int S) {
 __global__ __launch_bounds__(BOOT_THREADS) void k_trail_start(MapDev m, BootArgs a) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
-  if (st->boot_action != 1) return;
+  if (!trk_in_step(m.held, s) || st->boot_action != 1) return;
   __shared__ int sh_cnt;
   if (threadIdx.x == 0) sh_cnt = 0;
   __syncthreads();
@@ -95,7 +96,7 @@ __global__ void k_boot_started(MapDev m, int S) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
   TrackerState* st = &m.st[s];
-  if (st->boot_action != 1) return;
+  if (!trk_in_step(m.held, s) || st->boot_action != 1) return;
   st->kf_pending = 0; st->n_kf = 1; st->init_stage = 1;
 }
 
@@ -155,7 +156,7 @@ DEVFN bool mp_find(const BootFrame& f, int s, int w, int h, const uint8_t* tmpl 
 __global__ __launch_bounds__(BOOT_THREADS) void k_trail_advance(MapDev m, BootArgs a) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
-  if (st->boot_action != 2) return;
+  if (!trk_in_step(m.held, s) || st->boot_action != 2) return;      // (boot_action outlives its frame: a held stream's is stale)
   __shared__ int sh_host;
   if (threadIdx.x == 0) sh_host = st->boot_host_matches;
   __syncthreads();
@@ -439,7 +440,7 @@ __global__ void k_boot_phase(MapDev m, int S, int what) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
   TrackerState* st = &m.st[s];
-  if (!st->boot_run) return;
+  if (!trk_in_step(m.held, s) || !st->boot_run) return;
   if (what == 1) { st->kf_pending = 0; st->n_kf = 2; st->map_good = 1; st->kf_added = 0; }
   else if (what == 2) { st->kf_pending = 1; st->n_kf = 1; }
   else { st->kf_pending = 0; st->n_kf = 2; st->ba_converged_full = 0; st->ba_converged_recent = 0; }
@@ -583,8 +584,21 @@ int boot_frame(vslam_system* sys) {
   hipStream_t q = sys->stream;
   BootArgs a;
   boot_args(sys, a);
-  const bool key = sys->boot_key_pressed;
-  sys->boot_key_pressed = false;
+  // the presses since the last frame: a full step serves them all; a subset step serves those of its own streams, the press of a held
+  // stream waits (on the host as on the device, TrackerState::spacebar) for that stream's next frame
+  bool key = sys->boot_key_pressed;
+  if (key && sys->step_subset) {
+    bool left = false;
+    key = false;
+    for (int s = 0; s < S; s++) {
+      if (!sys->boot_key_stream[(size_t)s]) continue;
+      if (sys->step_in[(size_t)s]) { key = true; sys->boot_key_stream[(size_t)s] = 0; } else left = true;
+    }
+    sys->boot_key_pressed = left;
+  } else if (key) {
+    sys->boot_key_stream.assign((size_t)S, 0);
+    sys->boot_key_pressed = false;
+  }
   int r;
   hipLaunchKernelGGL(k_boot_gate, gs, bs, 0, q, sys->map, S);
   if (key) {                                                         // a first press may be consumed: TrailTracking_Start
@@ -622,6 +636,7 @@ extern "C" int vslam_press_spacebar(vslam_system* sys, int stream) {
   hipLaunchKernelGGL(k_boot_press, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->S, stream, 0u, 0);
   HIPCHK(hipGetLastError());
   sys->boot_key_pressed = true;
+  if (stream < 0) sys->boot_key_stream.assign((size_t)sys->S, 1); else sys->boot_key_stream[(size_t)stream] = 1;
   return VSLAM_OK;
 }
 

@@ -33,7 +33,10 @@ struct FeArgs {
   int* ncorners;
   int* overflow;
   int band_first[NLEV];   // k_fast_lvl: first blockIdx.x of each level
+  const int* list;        // subset step: launch ordinal -> stream whose slots (input and products) the ordinal works on; null: the identity
 };
+// the stream of launch ordinal i (uniform per workgroup in the band kernels and k_compact)
+DEVFN int fe_stream_of(const FeArgs& a, int i) { return a.list ? a.list[i] : i; }
 
 __device__ __forceinline__ bool ring_run10(unsigned m16) {
   unsigned m = m16 | (m16 << 16);
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(FE_THREADS) void k_pyr_fast0(FeArgs a, int lp0, int
   unsigned long long* mask_lds = (unsigned long long*)(((uintptr_t)(t2 + (BAND / 4) * lp2) + 15) & ~(uintptr_t)15);
   unsigned short* cand = (unsigned short*)(mask_lds + BAND * a.nchunk[0]);
   int* ncand = (int*)(cand + FB_ROWS * lp0);
-  const int b = blockIdx.x, s = blockIdx.y;
+  const int b = blockIdx.x, s = fe_stream_of(a, blockIdx.y);
   const uint8_t* in = a.in + (size_t)s * a.in_sstride;
   const int y0 = b * BAND;
   stage_rows(t0, lp0, in, a.in_pitch, a.w[0], a.h[0], y0 - HALO, BAND + 2 * HALO);
@@ -219,7 +222,7 @@ __global__ __launch_bounds__(FE_THREADS) void k_fast_lvl(FeArgs a) {
   int l = 1;
   if ((int)blockIdx.x >= a.band_first[2]) l = 2;
   if ((int)blockIdx.x >= a.band_first[3]) l = 3;
-  const int b = blockIdx.x - a.band_first[l], s = blockIdx.y;
+  const int b = blockIdx.x - a.band_first[l], s = fe_stream_of(a, blockIdx.y);
   const int lp = (a.w[l] + 15) & ~15;
   uint8_t* t = lds;
   unsigned long long* mask_lds = (unsigned long long*)(((uintptr_t)(t + (BAND + 2 * HALO) * lp) + 15) & ~(uintptr_t)15);
@@ -307,7 +310,8 @@ __global__ __launch_bounds__(SL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
   const int bl = tid / W16, cg = tid - bl * W16;
   const long gband = (long)wg * bpw + bl;
   const bool active = bl < bpw && gband < (long)q.S * nb;
-  const int s = active ? (int)(gband / nb) : 0, b = active ? (int)(gband - (long)s * nb) : 0;
+  const int ord = active ? (int)(gband / nb) : 0, b = active ? (int)(gband - (long)ord * nb) : 0;
+  const int s = active ? fe_stream_of(a, ord) : 0;
   const int yb = b * SL_R, x0 = cg * 16;
   tb[tid] = make_int4(s, yb, x0, active ? bl : -1);
   for (int i = tid; i < bpw * SL_R * nchunk; i += SL_THREADS) mask[i] = 0ull;
@@ -466,7 +470,7 @@ __global__ __launch_bounds__(SL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
 __global__ __launch_bounds__(COMPACT_THREADS) void k_compact(FeArgs a, int cband /* rows per workgroup */) {
   __shared__ int wsum[COMPACT_THREADS / 64];
   __shared__ int sh_above;
-  const int b = blockIdx.x, l = blockIdx.y, s = blockIdx.z;
+  const int b = blockIdx.x, l = blockIdx.y, s = fe_stream_of(a, blockIdx.z);
   const int h = a.h[l], nchunk = a.nchunk[l], cap = a.cap[l];
   const int y0 = b * cband;
   if (y0 >= h) return;
@@ -514,6 +518,32 @@ __global__ __launch_bounds__(COMPACT_THREADS) void k_compact(FeArgs a, int cband
   }
 }
 
+// Subset step from device memory: image i of the caller's buffer into the owned level-0 slot of stream list[i], all n images in one
+// launch (n two-dimensional copies would cost the host more than the front end costs the device).  One workgroup per band of
+// GATHER_ROWS rows of one image; 16 B per lane when the source allows it, bytes otherwise (any base address, pitch and stride).
+#define GATHER_ROWS 16
+__global__ __launch_bounds__(FE_THREADS) void k_gather_level0(const uint8_t* in, size_t in_sstride, int in_pitch, uint8_t* out, size_t out_sstride,
+                                                             int out_pitch /* multiple of 64, slots 16-B aligned */, int w, int h, const int* list) {
+  const int i = blockIdx.y, s = list[i];
+  const int y0 = blockIdx.x * GATHER_ROWS, nrows = min(GATHER_ROWS, h - y0);
+  const uint8_t* src = in + (size_t)i * in_sstride + (size_t)y0 * in_pitch;
+  uint8_t* dst = out + (size_t)s * out_sstride + (size_t)y0 * out_pitch;
+  int done = 0;
+  if ((((uintptr_t)src) & 15) == 0 && (in_pitch & 15) == 0) {
+    const int nvec = w >> 4;
+    for (int t = threadIdx.x; t < nrows * nvec; t += FE_THREADS) {
+      const int r = t / nvec, v = t - r * nvec;
+      ((uint4*)(dst + (size_t)r * out_pitch))[v] = ((const uint4*)(src + (size_t)r * in_pitch))[v];
+    }
+    done = nvec << 4;
+  }
+  const int rem = w - done;
+  for (int t = threadIdx.x; t < nrows * rem; t += FE_THREADS) {
+    const int r = t / rem, x = done + (t - r * rem);
+    dst[(size_t)r * out_pitch + x] = src[(size_t)r * in_pitch + x];
+  }
+}
+
 // ---- MakeKeyFrame_Rest: FAST score + non-max (jni/KeyFrame.cc:53-63) ---------------------------------------------
 struct NmArgs {
   const uint8_t* img[NLEV]; size_t img_sstride[NLEV]; int img_pitch[NLEV];
@@ -522,12 +552,13 @@ struct NmArgs {
   int* scores[NLEV]; uint32_t* maxcorners[NLEV]; int* nmax;
   int barrier, quirk;
   const TrackerState* gate;   // non-null: only the streams whose tracker asked for a keyframe (kf_pending)
+  const unsigned char* held;  // the frame's subset mask (null: a full step): a held stream has no front-end products
 };
 
 // compute_fast_score_old (cvfast.cpp:9337-9393): one lane per corner.
 __global__ __launch_bounds__(FE_THREADS) void k_score(NmArgs a) {
   const int l = blockIdx.y, s = blockIdx.z;
-  if (a.gate && !a.gate[s].kf_pending) return;
+  if (!trk_in_step(a.held, s) || (a.gate && !a.gate[s].kf_pending)) return;
   const int n = a.ncorners[s * NLEV + l];
   for (int i = blockIdx.x * FE_THREADS + threadIdx.x; i < n; i += gridDim.x * FE_THREADS) {
   const uint32_t cxy = a.corners[l][(size_t)s * a.cap[l] + i];
@@ -550,7 +581,7 @@ __global__ __launch_bounds__(FE_THREADS) void k_nonmax(NmArgs a) {
   __shared__ int wsum[8];
   __shared__ int carry;
   const int l = blockIdx.x, s = blockIdx.y;
-  if (a.gate && !a.gate[s].kf_pending) return;
+  if (!trk_in_step(a.held, s) || (a.gate && !a.gate[s].kf_pending)) return;
   const int n = a.ncorners[s * NLEV + l], cap = a.cap[l], h = a.h[l];
   const uint32_t* cs = a.corners[l] + (size_t)s * cap;
   const int* sc = a.scores[l] + (size_t)s * cap;
@@ -619,6 +650,7 @@ struct CandArgs {
   uint32_t* cand[NLEV]; double* cand_score[NLEV]; int* ncand;
   double min_score; int border;
   const TrackerState* gate;
+  const unsigned char* held;
 };
 
 __device__ __forceinline__ double shi_tomasi7(const uint8_t* img, int pitch, int px, int py) {
@@ -657,7 +689,7 @@ __global__ __launch_bounds__(FE_THREADS) void k_candidates(CandArgs a) {
   __shared__ int wsum[FE_THREADS / 64];
   __shared__ int carry;
   const int l = blockIdx.x, s = blockIdx.y;
-  if (a.gate && !a.gate[s].kf_pending) return;
+  if (!trk_in_step(a.held, s) || (a.gate && !a.gate[s].kf_pending)) return;
   const int n = a.nmax[s * NLEV + l], cap = a.cap[l];
   const uint32_t* mc = a.maxcorners[l] + (size_t)s * cap;
   const uint8_t* img = a.img[l] + (size_t)s * a.img_sstride[l];
@@ -694,6 +726,7 @@ struct ThinArgs {
   int new_kf;       // 1: gated on kf_pending and against the keyframe slot k_add_keyframe has just filled (slot n_kf)
   int only_level;   // >= 0: this level only
   size_t kf_row;    // max_points (elements per keyframe row) when new_kf
+  const unsigned char* held;   // the frame's subset mask (null: a full step)
 };
 
 __global__ __launch_bounds__(FE_THREADS) void k_thin_candidates(ThinArgs a, const TrackerState* st) {
@@ -702,7 +735,7 @@ __global__ __launch_bounds__(FE_THREADS) void k_thin_candidates(ThinArgs a, cons
   __shared__ int wsum[FE_THREADS / 64];
   __shared__ int carry;
   const int l = a.only_level >= 0 ? a.only_level : blockIdx.x, s = blockIdx.y;
-  if (a.new_kf && !st[s].kf_pending) return;
+  if (!trk_in_step(a.held, s) || (a.new_kf && !st[s].kf_pending)) return;
   const MeasDev* ms = a.meas + (size_t)s * a.meas_sstride + (a.new_kf ? (size_t)st[s].n_kf * a.kf_row : 0);
   const int np = st[s].n_points;
   if (threadIdx.x == 0) { nbusy = 0; carry = 0; }
@@ -753,6 +786,7 @@ static void fill_fe_args(vslam_system* sys, FeArgs& a) {
   }
   a.ncorners = sys->fr.ncorners;
   a.overflow = sys->fr.overflow;
+  a.list = nullptr;
 }
 
 // the strip form applies when every level is a multiple of 4 wide and at most 4096, and the level-0 input can be read 16 B at a time
@@ -833,12 +867,49 @@ static int fe_launch_bands(vslam_system* sys, FeArgs& a, hipStream_t stream, int
   return VSLAM_OK;
 }
 
+// A subset step's arguments (vslam_make_keyframe_lite_subset), checked before anything moves: the list, and on systems with the map
+// bootstrap the one stream state that cannot be held.  A stream whose trails are running reads the previous frame's level 0 and corner
+// list out of the other front-end buffer in place (k_trail_advance), so its frames must be consecutive steps: this is the one place
+// where a subset step waits for the device, to read the stages.
+static int fe_check_subset(vslam_system* sys, const uint8_t* gray, const int* streams, int n, std::vector<unsigned char>& in_step) {
+  if (n < 0 || n > sys->S || (n > 0 && (!streams || !gray))) { vslam_set_error("make_keyframe_lite_subset: bad arguments (n %d of %d streams)", n, sys->S); return VSLAM_E_INVALID; }
+  if (sys->frame_open) { vslam_set_error("make_keyframe_lite_subset: the previous frame was not finished (vslam_finish_frame)"); return VSLAM_E_STATE; }
+  in_step.assign((size_t)sys->S, 0);
+  for (int i = 0; i < n; i++) {
+    const int s = streams[i];
+    if (s < 0 || s >= sys->S) { vslam_set_error("make_keyframe_lite_subset: stream %d outside the batch of %d", s, sys->S); return VSLAM_E_INVALID; }
+    if (in_step[s]) { vslam_set_error("make_keyframe_lite_subset: stream %d listed twice", s); return VSLAM_E_INVALID; }
+    in_step[s] = 1;
+  }
+  if (sys->p.bootstrap && n < sys->S) {
+    std::vector<TrackerState> st((size_t)sys->S);
+    HIPCHK(hipStreamSynchronize(sys->stream));
+    HIPCHK(hipMemcpy(st.data(), sys->map.st, sizeof(TrackerState) * (size_t)sys->S, hipMemcpyDeviceToHost));
+    for (int s = 0; s < sys->S; s++)
+      if (!in_step[s] && st[s].init_stage == 1) { vslam_set_error("make_keyframe_lite_subset: stream %d has trails running and cannot be held", s); return VSLAM_E_STATE; }
+  }
+  return VSLAM_OK;
+}
+
+int fe_stream_in_step(vslam_system* sys, int stream, const char* who) {
+  if (sys->step_subset && !sys->step_in[(size_t)stream]) { vslam_set_error("%s: stream %d was held in this step, it has no front-end products", who, stream); return VSLAM_E_STATE; }
+  return VSLAM_OK;
+}
+
+// n < 0: the full step, image s for stream s.  n >= 0: a subset step, image i for streams[i]; every image is copied into its stream's
+// owned level-0 slot (from the host or from device memory alike), so the kernels find input and products of an ordinal in the same
+// stream's slots and the tracker finds level 0 where it finds it after a host-input full step.
 int fe_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_stride, size_t stream_stride,
-                          int on_device) {
+                          int on_device, const int* streams, int n) {
   const LevelGeom* g = sys->geom;
-  if (!gray || (int)row_stride < g[0].w) { vslam_set_error("make_keyframe_lite: bad image arguments"); return VSLAM_E_INVALID; }
+  const bool subset = n >= 0;
+  if ((!gray && !(subset && n == 0)) || (gray && (int)row_stride < g[0].w)) { vslam_set_error("make_keyframe_lite: bad image arguments"); return VSLAM_E_INVALID; }
+  std::vector<unsigned char> in_step;
+  if (subset) { const int r = fe_check_subset(sys, gray, streams, n, in_step); if (r) return r; }
+  const int nb = sys->fr_idx ^ 1;
+  if (subset && sys->step_stage_used[nb]) HIPCHK(hipEventSynchronize(sys->ev_step_stage[nb]));   // the upload of two steps ago has left the block
   // next front-end buffer; it may be rebuilt once the tracking that last read it (two frames ago) has finished
-  const int b = sys->fr_idx ^ 1;
+  const int b = nb;
   sys->fr_idx = b;
   sys->fr = sys->frbuf[b];
   for (int l = 0; l < NLEV; l++) sys->d_lvl[l] = sys->d_lvl_buf[b][l];
@@ -849,31 +920,69 @@ int fe_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_str
   if (sys->p.bootstrap) HIPCHK(hipStreamWaitEvent(fs, sys->ev_track_done[b ^ 1], 0));
   FeArgs a;
   fill_fe_args(sys, a);
-  if (on_device) {
+  const int S = subset ? n : sys->S;                                  // streams the front end works on
+  if (subset) {
+    const size_t Sz = (size_t)sys->S;
+    int* hl = (int*)sys->step_stage[b];
+    unsigned char* hm = sys->step_stage[b] + Sz * sizeof(int);
+    for (int i = 0; i < sys->S; i++) { hl[i] = i < n ? streams[i] : 0; hm[i] = in_step[(size_t)i] ? 0 : 1; }
+    HIPCHK(hipMemcpyAsync(sys->fr.step_list, sys->step_stage[b], Sz * sizeof(int) + Sz, hipMemcpyHostToDevice, fs));
+    HIPCHK(hipEventRecord(sys->ev_step_stage[b], fs));
+    sys->step_stage_used[b] = true;
+    sys->step_in.swap(in_step);
+    a.list = sys->fr.step_list;
+    sys->fe_held = sys->fr.held; sys->map.held = sys->fr.held;
+  } else {
+    if (sys->step_subset) sys->step_in.assign((size_t)sys->S, 1);
+    sys->fe_held = nullptr; sys->map.held = nullptr;
+  }
+  sys->step_subset = subset;
+  if (on_device && !subset) {
     a.in = gray; a.in_sstride = stream_stride; a.in_pitch = (int)row_stride;
   } else {
     // host input: copy into the owned level-0 image (TrackFrame copies its input too, jni/KeyFrame.cc:12)
-    for (int s = 0; s < sys->S; s++)
-      HIPCHK(hipMemcpy2DAsync(sys->d_lvl[0] + (size_t)s * a.lvl_sstride[0], g[0].pitch, gray + (size_t)s * stream_stride,
+    for (int i = 0; i < S && !on_device; i++) {
+      const int s = subset ? streams[i] : i;
+      HIPCHK(hipMemcpy2DAsync(sys->d_lvl[0] + (size_t)s * a.lvl_sstride[0], g[0].pitch, gray + (size_t)i * stream_stride,
                               row_stride, g[0].w, g[0].h, hipMemcpyHostToDevice, fs));
+    }
+    if (on_device && S > 0)                                          // a subset step from device memory: the same, in one launch
+      hipLaunchKernelGGL(k_gather_level0, dim3((g[0].h + GATHER_ROWS - 1) / GATHER_ROWS, S), dim3(FE_THREADS), 0, fs, gray, stream_stride, (int)row_stride,
+                         sys->d_lvl[0], a.lvl_sstride[0], g[0].pitch, g[0].w, g[0].h, (const int*)sys->fr.step_list);
     a.in = sys->d_lvl[0]; a.in_sstride = a.lvl_sstride[0]; a.in_pitch = g[0].pitch;
   }
   sys->fr.img[0] = a.in; sys->fr.img_sstride[0] = a.in_sstride; sys->fr.img_pitch[0] = a.in_pitch;
   for (int l = 1; l < NLEV; l++) { sys->fr.img[l] = a.lvl[l]; sys->fr.img_sstride[l] = a.lvl_sstride[l]; sys->fr.img_pitch[l] = a.lvl_pitch[l]; }
   sys->frbuf[b] = sys->fr;
 
-  if (fe_slide_ok(sys, a)) fe_launch_slide(sys, a, fs, sys->S);
-  else { const int r = fe_launch_bands(sys, a, fs, sys->S, true); if (r) return r; }
+  if (S > 0) {                                                        // (an empty subset step launches nothing here)
+    if (fe_slide_ok(sys, a)) fe_launch_slide(sys, a, fs, S);
+    else { const int r = fe_launch_bands(sys, a, fs, S, true); if (r) return r; }
+  }
   prof_mark(sys, PROF_COMPACT);
-  {
+  if (S > 0) {
     static const int cb = getenv("VSLAM_COMPACT_BAND") ? atoi(getenv("VSLAM_COMPACT_BAND")) : 32;   // rows of a level per workgroup of the compaction (measured alone, 1024 frames: 16 rows 96 us, 32: 62, 64: 96, 128: 78, 256: 156)
-    hipLaunchKernelGGL(k_compact, dim3((g[0].h + cb - 1) / cb, NLEV, sys->S), dim3(COMPACT_THREADS), 0, fs, a, cb);
+    hipLaunchKernelGGL(k_compact, dim3((g[0].h + cb - 1) / cb, NLEV, S), dim3(COMPACT_THREADS), 0, fs, a, cb);
   }
   if (sys->p.use_sbi) {                                           // jni/Tracker.cc:86-97, 104-105
-    int r = fe_sbi(sys, sys->have_sbi ? sys->frbuf[b ^ 1] : sys->fr);
+    const FrameDev& last = sys->have_sbi ? sys->frbuf[b ^ 1] : sys->fr;
+    int r = VSLAM_OK;
+    if (subset) {
+      // a stream whose first frame comes in a subset step, after other streams' frames: its "last frame" is the frame itself
+      for (int i = 0; i < n && sys->have_sbi; i++)
+        if (!sys->sbi_seen[(size_t)streams[i]]) { HIPCHK(hipMemsetAsync(sys->sbi_restart + streams[i], 1, 1, fs)); sys->sbi_restart_pending = true; }
+      for (int i = 0; i < n; i++) sys->sbi_seen[(size_t)streams[i]] = 1;
+      if (S > 0) r = fe_sbi(sys, last, a.list, S);
+      if (!r && sys->have_sbi && S < sys->S) r = fe_sbi_carry(sys, last);   // the held streams keep their last frame's products in the current buffer
+    } else {
+      if (!sys->sbi_all_seen) { sys->sbi_seen.assign((size_t)sys->S, 1); sys->sbi_all_seen = true; }
+      r = fe_sbi(sys, last, nullptr, S);
+    }
     if (r) return r;
-    if (sys->sbi_restart_pending) { r = fe_sbi_restart(sys); if (r) return r; sys->sbi_restart_pending = false; }   // streams reset since the last frame
-    sys->have_sbi = true;
+    // streams reset since their last frame: a full step serves every flag; a subset step only its own streams' (k_sbi_restart), so the
+    // flags of held streams may remain and the launch is repeated until a full step
+    if (sys->sbi_restart_pending && S > 0) { r = fe_sbi_restart(sys); if (r) return r; if (!subset) sys->sbi_restart_pending = false; }
+    if (S > 0) sys->have_sbi = true;
   }
   prof_mark(sys, PROF_FE_END);
   HIPCHK(hipGetLastError());
@@ -898,6 +1007,7 @@ static int fe_nonmax_impl(vslam_system* sys, bool gated) {
   a.barrier = sys->p.nonmax_barrier;
   a.quirk = (sys->p.quirks & VSLAM_Q_NONMAX_RIGHT_NEIGHBOUR) ? 1 : 0;
   a.gate = gated ? sys->map.st : nullptr;
+  a.held = sys->fe_held;
   (void)maxcap;
   hipLaunchKernelGGL(k_score, dim3(16, NLEV, sys->S), dim3(FE_THREADS), 0, sys->stream, a);
   hipLaunchKernelGGL(k_nonmax, dim3(NLEV, sys->S), dim3(FE_THREADS), 0, sys->stream, a);
@@ -921,6 +1031,7 @@ static int fe_rest_impl(vslam_system* sys, double min_score, bool gated) {
   a.nmax = sys->fr.nmax; a.ncand = sys->ncand;
   a.min_score = min_score; a.border = 10;                            // gvdCandidateMinSTScore / border, jni/KeyFrame.cc:57,65
   a.gate = gated ? sys->map.st : nullptr;
+  a.held = sys->fe_held;
   hipLaunchKernelGGL(k_candidates, dim3(NLEV, sys->S), dim3(FE_THREADS), 0, sys->stream, a);
   HIPCHK(hipGetLastError());
   sys->have_candidates = true;
@@ -936,7 +1047,7 @@ int fe_thin_candidates(vslam_system* sys, int keyframe) {
   for (int l = 0; l < NLEV; l++) { a.cand[l] = sys->cand[l]; a.cand_score[l] = sys->cand_score[l]; a.cap[l] = sys->geom[l].cap; }
   a.ncand = sys->ncand;
   const size_t P = sys->p.max_points, K = sys->p.max_keyframes;
-  a.new_kf = 0; a.only_level = -1; a.kf_row = 0;
+  a.new_kf = 0; a.only_level = -1; a.kf_row = 0; a.held = sys->fe_held;
   if (keyframe < 0) { a.meas = sys->map.cur_meas; a.meas_sstride = P; }           // the tracker's measurements of this frame
   else { a.meas = sys->map.kf_meas + (size_t)keyframe * P; a.meas_sstride = K * P; }
   hipLaunchKernelGGL(k_thin_candidates, dim3(NLEV, sys->S), dim3(FE_THREADS), 0, sys->stream, a, sys->map.st);
@@ -951,7 +1062,7 @@ int fe_thin_new_keyframe(vslam_system* sys, int level) {
   for (int l = 0; l < NLEV; l++) { a.cand[l] = sys->cand[l]; a.cand_score[l] = sys->cand_score[l]; a.cap[l] = sys->geom[l].cap; }
   a.ncand = sys->ncand;
   const size_t P = sys->p.max_points, K = sys->p.max_keyframes;
-  a.meas = sys->map.kf_meas; a.meas_sstride = K * P; a.new_kf = 1; a.only_level = level; a.kf_row = P;
+  a.meas = sys->map.kf_meas; a.meas_sstride = K * P; a.new_kf = 1; a.only_level = level; a.kf_row = P; a.held = sys->fe_held;
   hipLaunchKernelGGL(k_thin_candidates, dim3(1, sys->S), dim3(FE_THREADS), 0, sys->stream, a, sys->map.st);
   HIPCHK(hipGetLastError());
   return VSLAM_OK;
@@ -981,7 +1092,7 @@ int fe_keyframe_corners(vslam_system* sys, int s, int kf) {
     a.w[l] = g[l].w; a.h[l] = g[l].h; a.nchunk[l] = g[l].nchunk; a.thr[l] = g[l].thr; a.cap[l] = g[l].cap;
     a.cmask[l] = scr.cmask[l]; a.rowcnt[l] = scr.rowcnt[l]; a.rowlut[l] = scr.rowlut[l]; a.corners[l] = scr.corners[l];
   }
-  a.ncorners = scr.ncorners; a.overflow = scr.overflow;
+  a.ncorners = scr.ncorners; a.overflow = scr.overflow; a.list = nullptr;
   a.in = a.lvl[0]; a.in_sstride = 0; a.in_pitch = g[0].pitch;
   { const int r = fe_launch_bands(sys, a, sys->stream, 1, false); if (r) return r; }
   hipLaunchKernelGGL(k_compact, dim3((g[0].h + BAND - 1) / BAND, NLEV, 1), dim3(COMPACT_THREADS), 0, sys->stream, a, BAND);

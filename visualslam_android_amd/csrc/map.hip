@@ -265,14 +265,29 @@ extern "C" int vslam_finish_frame(vslam_system* sys) {
   if (sys->prof_on && sys->prof_frame < sys->prof_cap) sys->prof_frame++;
   if (!r) HIPCHK(hipEventRecord(sys->ev_track_done[sys->fr_idx], sys->stream));       // the front-end may now reuse this buffer
   sys->frame_no++;
+  sys->map.held = nullptr;                                                             // between steps no stream is held
   if (profile_serial() && !r) { HIPCHK(hipStreamSynchronize(sys->stream)); int rs = ba_sync_streams(sys); if (rs) return rs; }
   return r;
+}
+
+// TrackFrame behind its front end, for the full step and the subset step alike
+static int track_frame_rest(vslam_system* sys);
+extern "C" int vslam_track_frame_subset(vslam_system* sys, const int* streams, int n, const uint8_t* gray, size_t row_stride, size_t stream_stride,
+                                        int on_device) {
+  int r = vslam_make_keyframe_lite_subset(sys, streams, n, gray, row_stride, stream_stride, on_device);
+  if (r) return r;
+  return track_frame_rest(sys);
 }
 
 extern "C" int vslam_track_frame(vslam_system* sys, const uint8_t* gray, size_t row_stride, size_t stream_stride, int on_device) {
   if (!sys) return VSLAM_E_INVALID;
   int r = fe_make_keyframe_lite(sys, gray, row_stride, stream_stride, on_device);   // jni/Tracker.cc:85
   if (r) return r;
+  return track_frame_rest(sys);
+}
+
+static int track_frame_rest(vslam_system* sys) {
+  int r;
   if (profile_serial()) HIPCHK(hipStreamSynchronize(sys->fe_stream));
   r = vslam_attempt_recovery(sys);                                                   // :133-139, for the lost streams (vslam_params.relocalise)
   if (r) return r;
@@ -280,7 +295,7 @@ extern "C" int vslam_track_frame(vslam_system* sys, const uint8_t* gray, size_t 
   if (!r) r = vslam_pose_update(sys, 0);
   if (!r) r = vslam_patch_search(sys, 1);
   if (!r) r = vslam_pose_update(sys, 1);
-  if (r) { sys->frame_open = false; return r; }
+  if (r) { sys->frame_open = false; sys->map.held = nullptr; return r; }
   return vslam_finish_frame(sys);
 }
 

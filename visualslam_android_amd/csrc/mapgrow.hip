@@ -42,7 +42,7 @@ __global__ void k_copy_kf_corners(MapDev m, TrackParams tp, const uint32_t* c0, 
                                   const int* ncorners, int cap0, int cap1, int cap2, int cap3) {
   const int l = blockIdx.x, s = blockIdx.y;
   const TrackerState* st = &m.st[s];
-  if (!st->kf_pending) return;
+  if (!trk_kf_pending(m.held, s, st)) return;
   const uint32_t* src = (l == 0 ? c0 : (l == 1 ? c1 : (l == 2 ? c2 : c3))) + (size_t)s * (l == 0 ? cap0 : (l == 1 ? cap1 : (l == 2 ? cap2 : cap3)));
   const size_t slot = (size_t)s * tp.max_keyframes + st->n_kf;
   uint32_t* dst = m.kf_corners[l] + slot * tp.kcap[l];
@@ -69,7 +69,7 @@ DEVFN int closest_keyframe(const Pose* kfp, int n_old, const Pose& self) {
 __global__ __launch_bounds__(256) void k_target_implane(MapDev m, TrackParams tp, GrowArgs a, int nLevel) {
   const int s = blockIdx.y;
   const TrackerState* st = &m.st[s];
-  if (!st->kf_pending) return;
+  if (!trk_kf_pending(m.held, s, st)) return;
   const int K = tp.max_keyframes, ksrc = st->n_kf;
   __shared__ int sh_tgt;
   const Pose* kfp = m.kf_pose + (size_t)s * K;
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(GROW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
   constexpr int NPIX = PS * PS, HALF = PS / 2;
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
-  if (!st->kf_pending) return;
+  if (!trk_kf_pending(m.held, s, st)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int K = tp.max_keyframes, P = tp.max_points;
   const int ksrc = st->n_kf;                                       // the slot k_add_keyframe has just filled (n_kf advances in k_ba_assemble)
@@ -415,7 +415,7 @@ template <int PS>
 __global__ __launch_bounds__(GROW_THREADS) void k_refind(MapDev m, TrackParams tp, GrowArgs a) {
   const int s = blockIdx.y;
   TrackerState* st = &m.st[s];
-  if (!st->kf_pending) return;
+  if (!trk_kf_pending(m.held, s, st)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int P = tp.max_points;
   const int ksrc = st->n_kf;
@@ -445,7 +445,7 @@ template <int PS>
 __global__ __launch_bounds__(GROW_THREADS) void k_refind_idle(MapDev m, TrackParams tp, GrowArgs a, int mode) {
   const int s = blockIdx.y;
   TrackerState* st = &m.st[s];
-  if (!st->map_good) return;
+  if (!trk_in_step(m.held, s) || !st->map_good) return;              // a held stream runs no idle job
   if (mode == 0 ? !st->ba_converged_recent : !st->idle_do_fail) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int P = tp.max_points;
@@ -477,7 +477,7 @@ __global__ void k_idle_gate(MapDev m, int S, int what) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S) return;
   TrackerState* st = &m.st[s];
-  if (!st->map_good) return;
+  if (!trk_in_step(m.held, s) || !st->map_good) return;
   if (what == 0) {
     int go = 0;
     if (st->ba_converged_recent && st->ba_converged_full) { go = (st->idle_count % 20) == 0; st->idle_count++; }

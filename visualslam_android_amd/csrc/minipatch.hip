@@ -80,6 +80,7 @@ __global__ __launch_bounds__(64) void k_minipatch_find(const uint8_t* img, int p
 extern "C" int vslam_minipatch_sample(vslam_system* sys, int stream, int n, const int* pos_xy, uint8_t* patches, int* ok) {
   if (!sys || stream < 0 || stream >= sys->S || n < 0 || (n && (!pos_xy || !patches || !ok))) { vslam_set_error("minipatch_sample: bad argument"); return VSLAM_E_INVALID; }
   if (!sys->have_frame) { vslam_set_error("minipatch_sample: no current frame"); return VSLAM_E_STATE; }
+  { const int rs = fe_stream_in_step(sys, stream, "minipatch_sample"); if (rs) return rs; }
   if (n == 0) return VSLAM_OK;
   DevTemp<int> pos, flag; DevTemp<uint8_t> patch;      // of this call, each with 64 bytes of slack
   HIPCHK(pos.get(2 * (size_t)n + 16)); HIPCHK(patch.get((size_t)MP_PIX * n + 64)); HIPCHK(flag.get((size_t)n + 16));
@@ -97,6 +98,7 @@ extern "C" int vslam_minipatch_find(vslam_system* sys, int stream, int n, const 
                                     int* found) {
   if (!sys || stream < 0 || stream >= sys->S || n < 0 || range < 0 || (n && (!pos_xy || !patches || !found))) { vslam_set_error("minipatch_find: bad argument"); return VSLAM_E_INVALID; }
   if (!sys->have_frame) { vslam_set_error("minipatch_find: no current frame"); return VSLAM_E_STATE; }
+  { const int rs = fe_stream_in_step(sys, stream, "minipatch_find"); if (rs) return rs; }
   if (n == 0) return VSLAM_OK;
   DevTemp<int> pos, flag; DevTemp<uint8_t> patch;      // of this call, each with 64 bytes of slack
   HIPCHK(pos.get(2 * (size_t)n + 16)); HIPCHK(patch.get((size_t)MP_PIX * n + 64)); HIPCHK(flag.get((size_t)n + 16));

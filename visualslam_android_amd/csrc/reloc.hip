@@ -29,7 +29,7 @@ __global__ __launch_bounds__(SBI_THREADS) void k_kf_sbi(MapDev m, KfSbiArgs a) {
   if (s < 0) {
     s = blockIdx.x;
     const TrackerState* st = &m.st[s];
-    if (!st->kf_pending) return;
+    if (!trk_kf_pending(m.held, s, st)) return;
     k = st->n_kf;                                                   // the slot k_add_keyframe has just filled (n_kf advances in k_ba_select)
   }
   if (k < 0 || k >= a.K) return;
@@ -54,6 +54,7 @@ __global__ __launch_bounds__(SBI_THREADS) void k_recover(MapDev m, RecoverArgs a
   __shared__ SbiShared sh;
   __shared__ int sh_best;
   const int s = blockIdx.x, tid = threadIdx.x;
+  if (!trk_in_step(m.held, s)) return;                              // a held stream makes no attempt and keeps recovered_now
   TrackerState* st = &m.st[s];
   const bool lost = st->map_good && st->lost_frames >= 3;           // jni/Tracker.cc:103-104, 133
   const int nk = min(st->n_kf, a.K);

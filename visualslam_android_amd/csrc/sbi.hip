@@ -16,6 +16,8 @@ struct SbiArgs {
   const float* last_tmpl; const float* last_jacs;                 // previous frame (== this frame's on the very first frame)
   SbiBlur blur;                                                   // cv::getGaussianKernel(9, 0.75, CV_32F)
   CamModel cam;                                                   // the camera at the small image's size (SE3fromSE2 :254)
+  const int* list;                                                // subset step: workgroup -> stream (null: the identity)
+  const unsigned char* held;                                      // subset step: the step's mask (null: a full step)
 };
 
 // The stages themselves are the device functions of sbi_dev.h, which the relocaliser (reloc.hip) runs on other images.
@@ -24,8 +26,8 @@ template <bool RESTART>
 DEVFN void sbi_frame(const SbiArgs& a, unsigned char* restart) {
   extern __shared__ double sbi_dyn[];
   __shared__ SbiShared sh;
-  const int s = blockIdx.x, tid = threadIdx.x;
-  if (RESTART && !restart[s]) return;
+  const int s = (!RESTART && a.list) ? a.list[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
+  if (RESTART && (!restart[s] || !trk_in_step(a.held, s))) return;   // a held stream keeps its flag for its own next frame
   const int W = a.w3 / 2, H = a.h3 / 2, N = W * H;
   float* t0 = (float*)sbi_dyn;           // zero-mean small image, later the warped template
   float* t1 = t0 + N;                    // row pass, later this frame's template
@@ -53,6 +55,26 @@ __global__ __launch_bounds__(SBI_THREADS) void k_sbi(SbiArgs a) { sbi_frame<fals
 // (jni/Tracker.cc:90-92).  Launched behind k_sbi in that one frame only, for those streams only.
 __global__ __launch_bounds__(SBI_THREADS) void k_sbi_restart(SbiArgs a, unsigned char* restart) { sbi_frame<true>(a, restart); }
 
+// Subset step: the SmallBlurryImage products live in the frame's buffer, and the next frame of a stream aligns to "the other buffer".
+// A held stream's products therefore move along, from the last step's buffer into this one, so that its rotation prior aligns to its
+// own last frame whenever it resumes (and vslam_read_sbi and a snapshot keep finding them).  One workgroup per stream.
+struct SbiCarryArgs {
+  const uint8_t* small0; const float* tmpl0; const float* jacs0; const double* rot0;   // the last step's buffer
+  uint8_t* small1; float* tmpl1; float* jacs1; double* rot1;                           // this step's
+  const unsigned char* held; int N;
+};
+__global__ __launch_bounds__(SBI_THREADS) void k_sbi_carry(SbiCarryArgs a) {
+  const int s = blockIdx.x;
+  if (!a.held[s]) return;
+  const size_t o = (size_t)s * a.N;
+  for (int i = threadIdx.x; i < a.N; i += SBI_THREADS) {
+    a.small1[o + i] = a.small0[o + i];
+    a.tmpl1[o + i] = a.tmpl0[o + i];
+    a.jacs1[2 * (o + i)] = a.jacs0[2 * (o + i)]; a.jacs1[2 * (o + i) + 1] = a.jacs0[2 * (o + i) + 1];
+  }
+  if (threadIdx.x < 8) a.rot1[(size_t)s * 8 + threadIdx.x] = a.rot0[(size_t)s * 8 + threadIdx.x];
+}
+
 static int sbi_args(vslam_system* sys, const FrameDev& last, SbiArgs& a, size_t& lds) {
   const LevelGeom& g3 = sys->geom[3];
   const int W = g3.w / 2, H = g3.h / 2;
@@ -63,14 +85,26 @@ static int sbi_args(vslam_system* sys, const FrameDev& last, SbiArgs& a, size_t&
   sbi_blur_fill(a.blur, 0.75);                                       // gvdSBIBlur, jni/Tracker.cc:87
   cam_fill(a.cam, sys->p.cam, W, H, sys->p.quirks);
   lds = sbi_lds_bytes(W * H);
+  a.list = nullptr; a.held = sys->fe_held;
   return VSLAM_OK;
 }
 
-int fe_sbi(vslam_system* sys, const FrameDev& last) {
+int fe_sbi(vslam_system* sys, const FrameDev& last, const int* list, int n) {
   SbiArgs a; size_t lds;
   int r = sbi_args(sys, last, a, lds); if (r) return r;
+  a.list = list;
   if (lds > 48 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_sbi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_sbi, dim3(sys->S), dim3(SBI_THREADS), lds, sys->fe_stream, a);
+  hipLaunchKernelGGL(k_sbi, dim3(n), dim3(SBI_THREADS), lds, sys->fe_stream, a);
+  HIPCHK(hipGetLastError());
+  return VSLAM_OK;
+}
+
+int fe_sbi_carry(vslam_system* sys, const FrameDev& last) {
+  SbiCarryArgs a;
+  a.small0 = last.sbi_small; a.tmpl0 = last.sbi_tmpl; a.jacs0 = last.sbi_jacs; a.rot0 = last.sbi_rot;
+  a.small1 = sys->fr.sbi_small; a.tmpl1 = sys->fr.sbi_tmpl; a.jacs1 = sys->fr.sbi_jacs; a.rot1 = sys->fr.sbi_rot;
+  a.held = sys->fr.held; a.N = (sys->geom[3].w / 2) * (sys->geom[3].h / 2);
+  hipLaunchKernelGGL(k_sbi_carry, dim3(sys->S), dim3(SBI_THREADS), 0, sys->fe_stream, a);
   HIPCHK(hipGetLastError());
   return VSLAM_OK;
 }

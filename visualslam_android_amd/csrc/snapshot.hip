@@ -288,6 +288,7 @@ extern "C" int vslam_restore_stream(vslam_system* sys, int s, const void* blob, 
   hipLaunchKernelGGL(k_snapshot<false>, dim3(snap_blocks(bytes)), dim3(SNAP_THREADS), 0, sys->stream, plan, on_device ? (uint8_t*)blob : stage.p);
   HIPCHK(hipGetLastError());
   if (sbi) HIPCHK(hipMemsetAsync(sys->sbi_restart + s, 0, 1, sys->stream));   // its next frame is aligned to the carried image, not to itself
+  if (sbi) sys->sbi_seen[(size_t)s] = 1;                                      // (... in a subset step too)
   if (sys->map.kf_ncorners) for (int k = 0; k < c.n_kf; k++) VCHK(fe_keyframe_corners(sys, s, k));   // Level::vCorners of the keyframes
   VCHK(reloc_keyframe_sbi(sys, s, 0, c.n_kf));                                                        // KeyFrame::pSBI
   HIPCHK(hipEventRecord(sys->ev_snap_t[3], sys->stream));

@@ -104,7 +104,20 @@ static int sys_acquire(vslam_system* sys) {
     VCHK(own.alloc(&fr.ncorners, (size_t)S * NLEV, q));
     VCHK(own.alloc(&fr.nmax, (size_t)S * NLEV, q));
     VCHK(own.alloc(&fr.overflow, 1, q));
+    {                                                                // a subset step's list and mask (all zero: nothing held), and their pinned staging block
+      unsigned char* blk = nullptr;
+      VCHK(own.alloc(&blk, (size_t)S * (sizeof(int) + 1), q));
+      fr.step_list = (int*)blk; fr.held = blk + (size_t)S * sizeof(int);
+      void* pin = nullptr;
+      VCHK(own.pinned(&pin, (size_t)S * (sizeof(int) + 1)));
+      sys->step_stage[b] = (unsigned char*)pin;
+      VCHK(own.event(&sys->ev_step_stage[b], false));
+    }
   }
+  sys->step_in.assign((size_t)S, 1);
+  sys->sbi_seen.assign((size_t)S, 0);
+  sys->boot_key_stream.assign((size_t)S, 0);
+  sys->map.held = nullptr;
   for (int l = 0; l < NLEV; l++) { VCHK(own.alloc(&sys->cand[l], (size_t)S * sys->geom[l].cap, q)); VCHK(own.alloc(&sys->cand_score[l], (size_t)S * sys->geom[l].cap, q)); }
   VCHK(own.alloc(&sys->ncand, (size_t)S * NLEV, q));
   sys->have_candidates = false;
@@ -187,6 +200,19 @@ extern "C" int vslam_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, 
   return fe_make_keyframe_lite(sys, gray, row_stride, stream_stride, on_device);
 }
 
+extern "C" int vslam_make_keyframe_lite_subset(vslam_system* sys, const int* streams, int n, const uint8_t* gray, size_t row_stride,
+                                               size_t stream_stride, int on_device) {
+  if (!sys) return VSLAM_E_INVALID;
+  if (n < 0) { vslam_set_error("make_keyframe_lite_subset: n %d", n); return VSLAM_E_INVALID; }
+  return fe_make_keyframe_lite(sys, gray, row_stride, stream_stride, on_device, streams, n);
+}
+
+extern "C" int vslam_get_step_streams(vslam_system* sys, unsigned char* in_step) {
+  if (!sys || !in_step) { vslam_set_error("get_step_streams: null argument"); return VSLAM_E_INVALID; }
+  memcpy(in_step, sys->step_in.data(), (size_t)sys->S);
+  return VSLAM_OK;
+}
+
 extern "C" int vslam_fast_nonmax(vslam_system* sys) {
   if (!sys) return VSLAM_E_INVALID;
   return fe_fast_nonmax(sys);
@@ -195,7 +221,7 @@ extern "C" int vslam_fast_nonmax(vslam_system* sys) {
 static int check_sl(vslam_system* sys, int stream, int level) {
   if (!sys || stream < 0 || stream >= sys->S || level < 0 || level >= NLEV) { vslam_set_error("bad stream/level"); return VSLAM_E_INVALID; }
   if (!sys->have_frame) { vslam_set_error("no current frame"); return VSLAM_E_STATE; }
-  return VSLAM_OK;
+  return fe_stream_in_step(sys, stream, "front-end read-back");
 }
 
 static int check_overflow(vslam_system* sys) {
@@ -240,7 +266,8 @@ extern "C" int vslam_read_row_lut(vslam_system* sys, int stream, int level, int*
 }
 
 extern "C" int vslam_read_sbi(vslam_system* sys, int stream, uint8_t* small_img, float* tmpl, double rot8[8]) {
-  int r = check_sl(sys, stream, 0); if (r) return r;
+  if (!sys || stream < 0 || stream >= sys->S) { vslam_set_error("bad stream/level"); return VSLAM_E_INVALID; }
+  if (!sys->have_frame) { vslam_set_error("no current frame"); return VSLAM_E_STATE; }   // (a held stream's products are carried: no check_sl)
   if (!sys->p.use_sbi || !sys->have_sbi) { vslam_set_error("read_sbi: use_sbi is off or no frame yet"); return VSLAM_E_STATE; }
   HIPCHK(hipStreamSynchronize(sys->fe_stream));
   const size_t ns = (size_t)(sys->geom[3].w / 2) * (sys->geom[3].h / 2);

@@ -90,8 +90,9 @@ static_assert(offsetof(TrackData, derivs) == 40 && offsetof(TrackData, warp_inv)
 __global__ __launch_bounds__(64) void k_motion(MapDev m, int S, const double* sbi_rot /* [S][8] or null */) {
   const int s = blockIdx.x * 64 + threadIdx.x;
   if (s >= S) return;
+  if (!trk_in_step(m.held, s)) return;                             // a held stream: this frame does not exist (no mnFrame++, no flag or counter cleared)
   TrackerState* st = &m.st[s];
-  const bool tracking = trk_runs_track_map(st);                     // jni/Tracker.cc:103-104, 135-136
+  const bool tracking = trk_runs_track_map(m.held, s, st);          // jni/Tracker.cc:103-104, 135-136
   st->frame++;                                                     // :100
   st->kf_pending = 0; st->kf_added = 0;
   if (!tracking) return;
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(64) void k_motion(MapDev m, int S, const double* sb
 __global__ __launch_bounds__(TRK_THREADS) VSLAM_PVS_ATTR void k_pvs(MapDev m, TrackParams tp) {
   const int s = blockIdx.y;
   TrackerState* st = &m.st[s];
-  const bool tracking = trk_runs_track_map(st);                     // jni/Tracker.cc:103-104, 135-136
+  const bool tracking = trk_runs_track_map(m.held, s, st);          // jni/Tracker.cc:103-104, 135-136
   const int n_points = st->n_points, i0 = blockIdx.x * TRK_THREADS;
   if (!tracking || i0 >= n_points) return;
   __shared__ __align__(16) double pbuf[TRK_THREADS * PVS_OUT];
@@ -188,7 +189,7 @@ template <bool SHUFFLE>
 __global__ __launch_bounds__(TRK_THREADS) void k_plan(MapDev m, TrackParams tp, int stage) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
-  if (!trk_runs_track_map(st)) return;
+  if (!trk_runs_track_map(m.held, s, st)) return;
   const int P = tp.max_points;
   TrackData* td = m.td + (size_t)s * P;
   const MapPointDev* pts = m.pts + (size_t)s * P;
@@ -407,7 +408,7 @@ __global__ __launch_bounds__(64) void k_searchN(MapDev m, TrackParams tp, Search
   xcd_stream_block(a.nblk, a.S, s, bx);
   if (s < 0) return;
   TrackerState* st = &m.st[s];
-  if (!trk_runs_track_map(st)) return;
+  if (!trk_runs_track_map(m.held, s, st)) return;
   const int nsearch = st->n_search;
   if (bx * PPW >= nsearch) return;
   const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
@@ -729,7 +730,7 @@ __global__ __launch_bounds__(64) void k_subpixN(MapDev m, TrackParams tp, Search
   xcd_stream_block(a.nblk, a.S, s, bx);
   if (s < 0) return;
   TrackerState* st = &m.st[s];
-  if (!trk_runs_track_map(st)) return;
+  if (!trk_runs_track_map(m.held, s, st)) return;
   const int nsub = stage == 0 ? st->n_search : st->n_l3;             // entries that carry a sub-pixel budget
   for (int blk = bx; blk * (64 / G) < nsub; blk += a.nblk) subpix_block<PS, G>(m, tp, a, st, s, nsub, blk);
 }
@@ -1005,7 +1006,7 @@ DEVFN double kf_linear_dist(const Pose& a, const Pose& b) {
 __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VSLAM_POSE_WAVES, VSLAM_POSE_WAVES))) void k_pose(MapDev m, TrackParams tp, int stage) {
   const int s = blockIdx.x;
   TrackerState* st = &m.st[s];
-  if (!trk_runs_track_map(st)) return;
+  if (!trk_runs_track_map(m.held, s, st)) return;
   const int P = tp.max_points;
   TrackData* td = m.td + (size_t)s * P;
   MapPointDev* pts = m.pts + (size_t)s * P;

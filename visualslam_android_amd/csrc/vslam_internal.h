@@ -58,6 +58,9 @@ struct FrameDev {
   float* sbi_tmpl;                  // [S][hs*ws]       mimTemplate (zero-mean, blurred)
   float* sbi_jacs;                  // [S][hs*ws][2]    mimImageJacs
   double* sbi_rot;                  // [S][8]           mv6SBIRot (6), final ESM score, spare
+  // subset steps (vslam_make_keyframe_lite_subset): the streams of the step this buffer was built for, written by that step only
+  int* step_list;                   // [S]  launch ordinal -> stream, the first n entries
+  unsigned char* held;              // [S]  1: the stream is not in the step (directly behind step_list: one upload brings both)
 };
 
 
@@ -137,8 +140,15 @@ HDFN void tracker_reset_fields(TrackerState& st, unsigned pvs_seed) {
   st.pose_cur = st.pose_final; st.start_pose = st.pose_final;
 }
 HDFN TrackerState tracker_reset_state(unsigned pvs_seed) { TrackerState st = {}; tracker_reset_fields(st, pvs_seed); return st; }
+// Subset steps: `held` is the step's mask (FrameDev::held of the step's buffer), null in a full step and between steps.  A held stream
+// is not in the step: no kernel of the step reads a decision out of its state or writes to it.  Stated once, for every gate:
+DEVFN bool trk_in_step(const unsigned char* held, int s) { return !held || !held[s]; }
 // jni/Tracker.cc:103-104 and :135-136: TrackMap runs for a stream that is not lost, or that the relocaliser has just recovered
-DEVFN bool trk_runs_track_map(const TrackerState* st) { return st->map_good && (st->lost_frames < 3 || st->recovered_now); }
+DEVFN bool trk_runs_track_map(const unsigned char* held, int s, const TrackerState* st) {
+  return trk_in_step(held, s) && st->map_good && (st->lost_frames < 3 || st->recovered_now);
+}
+// the tracker's keyframe request of THIS step (a held stream keeps the flag of its last frame, which has been served)
+DEVFN bool trk_kf_pending(const unsigned char* held, int s, const TrackerState* st) { return trk_in_step(held, s) && st->kf_pending; }
 
 struct TrackParams {        // device copy of the tunables the kernels read
   CamModel cam;
@@ -188,6 +198,7 @@ struct MapDev {             // device pointers of the map + tracker of all strea
   int* iter_list;           // [S][max_points]  vIterationSet
   double* pose_ws;          // [S][POSE_WS_COMPS][max_points]  k_pose working set, component-major, indexed by iteration-set entry
   int* pose_wsi;            // [S][2][max_points]  flags, map point index
+  const unsigned char* held;   // [S] the open subset step's mask (trk_in_step); null in a full step and between steps
 };
 
 // ---- relocaliser (vslam_params.relocalise; reloc.hip): Relocaliser members, jni/Relocaliser.h ----------------------------------
@@ -298,6 +309,16 @@ struct vslam_system {
   bool have_frame;
   bool frame_open = false;  // stage-wise TrackFrame (vslam_patch_search ... vslam_finish_frame) in progress
   bool have_sbi;            // a SmallBlurryImage of a previous frame exists (mpSBILastFrame)
+  // subset steps.  The list and the mask of a step travel through pinned memory, one block per front-end buffer: the front end of
+  // step t+1 uploads its own while the tracker of step t still reads the other buffer's.
+  unsigned char* step_stage[2] = {nullptr, nullptr};   // pinned: [S] ints (the list), then [S] bytes (the mask)
+  hipEvent_t ev_step_stage[2] = {nullptr, nullptr};    // the upload out of step_stage[b] has finished
+  bool step_stage_used[2] = {false, false};
+  bool step_subset = false;                  // the current / last step was a subset step
+  std::vector<unsigned char> step_in;        // [S] host: 1 for the streams of the current / last step
+  const unsigned char* fe_held = nullptr;    // the current buffer's mask (device) while step_subset, else null: gates the front-end products
+  std::vector<unsigned char> sbi_seen;       // [S] host (use_sbi): the stream has had a frame; a first frame in a subset step aligns to itself
+  bool sbi_all_seen = false;
   // KeyFrame::Level::vCandidates of the current frame (jni/KeyFrame.h:62-70), filled by vslam_make_keyframe_rest
   uint32_t* cand[NLEV]; double* cand_score[NLEV]; int* ncand; bool have_candidates;
   // vslam_reset_streams (reset.hip)
@@ -315,6 +336,7 @@ struct vslam_system {
   hipEvent_t ev_snap_t[4] = {nullptr, nullptr, nullptr, nullptr};   // around the last pack [0, 1] and the last unpack [2, 3] on the system's stream
   bool snap_timed[2] = {false, false};       // a pack / an unpack has run
   bool boot_key_pressed = false;   // vslam_press_spacebar since the last frame: that frame launches the start / InitFromStereo pipelines
+  std::vector<unsigned char> boot_key_stream;   // [S] host: ... for which streams (a subset step serves only its own)
   TrackParams tp;
   MapDev map;
   BaSystemWs* ba_ws = nullptr; // bundle-adjustment workspace (ba.hip): ba_alloc makes it, ba_free deletes it
@@ -345,7 +367,8 @@ static inline void prof_mark(vslam_system* sys, int k) {
 
 // frontend.hip
 int fe_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_stride, size_t stream_stride,
-                          int on_device);
+                          int on_device, const int* streams = nullptr, int n = -1);   // n >= 0: a subset step for streams[0..n)
+int fe_stream_in_step(vslam_system* sys, int stream, const char* who);   // VSLAM_E_STATE for a stream the current / last step held
 int fe_fast_nonmax(vslam_system* sys);
 int fe_keyframe_corners(vslam_system* sys, int s, int kf);   // FAST corners of a stored keyframe into MapDev::kf_corners (map upload)
 int fe_keyframe_rest_gated(vslam_system* sys);               // non-max + candidates of the current frame for the streams with kf_pending
@@ -362,7 +385,8 @@ int grow_levels(vslam_system* sys, const int* order, int n);              // Thi
 int ba_launch_add_keyframe(vslam_system* sys);                            // k_add_keyframe for the streams with kf_pending
 enum IdleJob : int { IDLE_BA_RECENT = 0, IDLE_REFIND_NEW = 1, IDLE_BA_ALL = 2, IDLE_REFIND_FAILED = 3, IDLE_N_JOBS };   // the job numbers of vslam_mapmaker_idle_job
 int mm_idle_job(vslam_system* sys, int job);                               // vslam_params.idle_iterations passes through MapMaker::run's idle jobs
-int fe_sbi(vslam_system* sys, const FrameDev& last);   // k_sbi on the front-end stream: this frame's SBI + rotation prior against `last`
+int fe_sbi(vslam_system* sys, const FrameDev& last, const int* list, int n);   // k_sbi on the front-end stream: this frame's SBI + rotation prior against `last`, for n streams (list: null = all, identity)
+int fe_sbi_carry(vslam_system* sys, const FrameDev& last);   // subset step: the held streams' SBI products move from `last` into the current buffer
 int fe_sbi_restart(vslam_system* sys);                 // ... again against the frame itself for the streams vslam_reset_streams flagged (once, then the flags are clear)
 void cam_fill(CamModel& c, const double cam5[5], double width, double height, int quirks);
 int fe_make_keyframe_rest(vslam_system* sys, double min_score);
