@@ -125,6 +125,16 @@ int vslam_synchronize(vslam_system* sys);
  * (on_host != 0) as compiled for the host.  fn: 0 sin, 1 cos, 2 tan, 3 atan, 4 asin, 5 acos, 6 sqrt, 7 reciprocal.  Both sides
  * must return the same bits: one ulp of difference in a projection flips template pixels (jni/vision/ImageHandler.cpp:12-19). */
 int vslam_eval_transcendental(int fn, int n, const double* x, double* y, int on_host);
+/* Self-test hooks for two pieces of the tracker's pose iterations and the bundle adjustment, each run in one workgroup of the
+ * size its kernel uses.
+ * vslam_eval_select: the k-th smallest (0-based) of n non-negative doubles, as the Tukey median takes it (jni/MEstimator.h:67-77).
+ *   form 0: the tracker's workgroup, values in on-chip memory (n <= 4096); form 1: the bundle adjustment's, values in device memory.
+ *   +inf marks an entry that is not part of the median (k counts the others).
+ * vslam_eval_pose_tail: the end of one pose iteration (jni/Tracker.cc:487 / :573) from the 27 sums of the normal equations (upper
+ *   triangle of C row by row, then v): the solve of myWLS::compute (jni/myWLS.h:54-62; a singular C gives a zero update) and
+ *   pose12_out = exp(update6) * pose12. */
+int vslam_eval_select(int form, int n, const double* v, int k, double* out);
+int vslam_eval_pose_tail(const double* sums27, const double* pose12, double* update6, double* pose12_out);
 
 /* ---- frame front-end ------------------------------------------------------------------- */
 

@@ -19,7 +19,7 @@ for t in range(1, 5):
     g.track_frame(np.stack([frames[t]] * S))
 g.synchronize()
 lib.vslam_debug_pose_prof(out, 1)
-names = ['gather', 'step(project/linear)+e2', 'count', 'radix_select', 'accumulate', 'wave_reduce', 'solve(thread0)', 'exp(thread0)', '-', 'scatter+export+tail']
+names = ['gather', 'step(project/linear)+e2', 'count', 'radix_select', 'accumulate', 'wave_reduce', 'solve', 'exp+publish', '-', 'scatter+export+tail']   # (solve, exp: one thread before the tail moved to wavefront 0's lanes, which has no wave_reduce)
 tot = sum(out[i] for i in range(0, 10))
 st = g.state(0)
 print('S', S, 'found', sum(st.found), 'total kcycles per k_pose launch %.1f' % (tot / 1e3 / 8))

@@ -86,6 +86,8 @@ SYMBOLS = {
     "vslam_destroy": (_i, [_sys]),
     "vslam_synchronize": (_i, [_sys]),
     "vslam_eval_transcendental": (_i, [_i, _i, _vp, _vp, _i]),
+    "vslam_eval_select": (_i, [_i, _i, _vp, _i, _vp]),
+    "vslam_eval_pose_tail": (_i, [_vp, _vp, _vp, _vp]),
     "vslam_make_keyframe_lite": (_i, [_sys, _vp, _sz, _sz, _i]),
     "vslam_fast_nonmax": (_i, [_sys]),
     "vslam_read_level_image": (_i, [_sys, _i, _i, _vp, _sz]),
@@ -271,6 +273,23 @@ def eval_transcendental(name, x, on_host=False):
     y = np.zeros_like(x)
     _check(load_library().vslam_eval_transcendental(TRANSCENDENTALS.index(name), len(x), x.ctypes.data, y.ctypes.data, int(on_host)))
     return y
+
+
+def eval_select(v, k, form=0):
+    """The k-th smallest of the non-negative doubles v (+inf: not counted) by the device's radix select, in the tracker's workgroup
+    (form 0, len(v) <= 4096) or the bundle adjustment's (form 1)."""
+    v = _f64(v).reshape(-1)
+    out = np.zeros(1)
+    _check(load_library().vslam_eval_select(int(form), len(v), v.ctypes.data, int(k), out.ctypes.data))
+    return out[0]
+
+
+def eval_pose_tail(sums27, pose12):
+    """The end of one pose iteration on the device: -> (update [6], exp(update) * pose12 [12])."""
+    s, p = _f64(sums27).reshape(27), _f64(pose12).reshape(12)
+    up, out = np.zeros(6), np.zeros(12)
+    _check(load_library().vslam_eval_pose_tail(s.ctypes.data, p.ctypes.data, up.ctypes.data, out.ctypes.data))
+    return up, out
 
 
 def pvs_permutation(seed, frame, lst, n, keys=None, on_host=False):

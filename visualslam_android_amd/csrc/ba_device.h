@@ -31,6 +31,7 @@
 // 4 waves; with amdgpu_waves_per_eu(2,2) on the kernel two problems share a CU (measured: 512 x 1 -4 %, 128 x 4 -4 %)
 #define BA_LDS_N 60      // reduced camera systems up to 60 x 60 (10 adjustable cameras) are solved in LDS
 #define BA_WAVES (BA_THREADS / 64)
+static_assert(BA_THREADS == VSLAM_BA_WG, "vslam_eval_select runs the median in this workgroup");
 #define BA_ILP_PROJ 4   // projection passes: 4 measurements in flight (1 -> 4: -31 % on FindNewError once the view pointers were global and scalar; 6 spills: 5x slower)
 #define BA_ILP_S 1      // Schur-complement tasks: 36 accumulators + two 6x3 blocks per lane leave no registers for a second point
 #define BA_ILP 4        // independent measurements per thread and loop trip: the loops are memory-latency bound at 2 waves/SIMD
@@ -497,7 +498,7 @@ BA_PHASE_FN void ba_build_layout(const BaView& v_, int nc, int np, int* ired, in
 // measurement that stays in the list (state OK now, in front of the camera) goes to `scratch`, +inf for the others, and their
 // number is returned.  Reads the static 32 B of a slot, writes 8 B.
 // ---------------------------------------------------------------------------------------------------------------------
-struct BaNewError { double ne; int nvalid; };
+struct BaNewError { double ne; int nvalid; SelectRange sr; };   // sr: the range of the squared errors this thread left in `scratch` (+inf apart)
 BA_PHASE_FN BaNewError ba_find_new_error(const BaView& v_, const BaConfig& cfg_, int M, double sigma2, int trial, double* lds_ /* LDS: 12 doubles per camera */) {
   const BaViewG v = ba_g(v_);
   const BaConfig cfg = cfg_;
@@ -512,6 +513,7 @@ BA_PHASE_FN BaNewError ba_find_new_error(const BaView& v_, const BaConfig& cfg_,
   const double AS1* pts = trial ? v.pt_new : v.pt_pos;
   double ne = 0.0;
   int nv = 0;
+  SelectRange sr = select_range_empty();
   // The slot fields of the NEXT batch are requested together with this batch's points (which hang on this batch's slot fields):
   // one exposed memory round trip per batch instead of two.  (Deeper pipelining does not survive the compiler: with the stores to
   // `scratch` in the loop, loads and stores share vmcnt and every first use waits for zero.)
@@ -548,11 +550,12 @@ BA_PHASE_FN BaNewError ba_find_new_error(const BaView& v_, const BaConfig& cfg_,
       ne += tukey_objective(e2, sigma2);
       const bool stays = st == MS_OK;                                 // MS_BAD ones are erased at the end of this step
       v.scratch[i] = stays ? e2 : __builtin_huge_val();
+      select_range_add(sr, e2, stays);
       nv += stays ? 1 : 0;
     }
     cb = nb;
   }
-  BaNewError r; r.ne = ne; r.nvalid = nv;
+  BaNewError r; r.ne = ne; r.nvalid = nv; r.sr = sr;
   return r;
 }
 
@@ -1228,6 +1231,7 @@ struct BaFastSums {
   static constexpr int LDS_DOUBLES = LDS_A > LDS_B ? LDS_A : LDS_B;
   const BaView& v_; const BaViewG& v; const BaConfig& cfg;
   double* red; int* ired;                                              // the driver's reduction scratch
+  int* hist; unsigned* selmm;                                      // the driver's median: prepared (block_select_publish) where `scratch` is written
   static __shared__ double lds[LDS_DOUBLES];                           // one phase at a time
 #ifdef VSLAM_BA_PROF
   unsigned long long ba_t0 = clock64();
@@ -1236,7 +1240,11 @@ struct BaFastSums {
   DEVFN void stamp(int id) { BA_STAMP(id); }
   DEVFN void begin(int, int) {}                                        // (no table of its own behind the layout)
   // pass 1 (:209-215): the squared errors of the measurements still in the list, for the median; their number
-  DEVFN int count_valid(int M, int) { return ba_block_sum_i(ba_find_new_error(v_, cfg, M, 1.0, 0, lds).nvalid, ired); }
+  DEVFN int count_valid(int M, int) {
+    const BaNewError fne = ba_find_new_error(v_, cfg, M, 1.0, 0, lds);
+    block_select_publish(fne.sr, hist, selmm);                         // (rides on the sum's barriers)
+    return ba_block_sum_i(fne.nvalid, ired);
+  }
   // passes 1 + 2 (:209-321) in one sweep: weights, objective, V / epsilon_b, U / epsilon_a; A, B, W are re-derived by their consumers
   DEVFN double step(int M, int nc, int np, int nfree, double sigma2) {
     double* stg = lds; double* ured = nullptr; double* camsL = lds + BA_WAVES * 64 * BA_SWEEP_STAGE;
@@ -1293,6 +1301,7 @@ struct BaFastSums {
   // FindNewError (:537-561) at the trial state: dNewError to *new_err, returns the measurements that stay (ssq is map_update's)
   DEVFN int new_error(int M, int, int, int, double sigma2, double&, double* new_err) {
     const BaNewError fne = ba_find_new_error(v_, cfg, M, sigma2, 1, lds);
+    block_select_publish(fne.sr, hist, selmm);                         // (rides on the sums' barriers)
     const double ne = ba_block_sum(fne.ne, red);
     if (threadIdx.x == 0) *new_err = ne;
     return ba_block_sum_i(fne.nvalid, ired);
@@ -1305,8 +1314,9 @@ DEVFN void ba_lm(const BaView& v_, const BaConfig& cfg, const BaOrdView& o) {
   const BaViewG v = ba_g(v_);
   __shared__ double red[BA_WAVES];
   __shared__ int ired[BA_WAVES];
-  __shared__ int hist[768];
+  __shared__ __attribute__((aligned(16))) int hist[768];
   __shared__ unsigned long long sel[1];
+  __shared__ unsigned selmm[2 * BA_WAVES];
   __shared__ double sh_lambda, sh_factor, sh_sigma2, sh_cur_err, sh_new_err;
   __shared__ int sh_converged, sh_hitmax, sh_counter, sh_accepted, sh_error, sh_nout, sh_cache_valid, sh_next_nvalid;
   BaResult AS1* R = v.res;
@@ -1326,6 +1336,7 @@ DEVFN void ba_lm(const BaView& v_, const BaConfig& cfg, const BaOrdView& o) {
   const int nfree = R->n_free, nS = nfree * 6;
   if (nfree > 64) { if (threadIdx.x == 0) { R->accepted = -1; R->converged = 0; R->hit_max = 0; R->counter = 0; R->n_outlier_meas = 0; } __syncthreads(); return; }   // pt_maskF holds 64 ordinals
   Sums sums(v_, v, cfg, o, red, ired);
+  sums.hist = hist; sums.selmm = selmm;
   static_assert(sizeof(Sums::lds) >= 2 * 4097 * sizeof(int) && sizeof(Sums::lds) >= BA_LDS_N * (BA_LDS_N + 1) * sizeof(double) &&
                 sizeof(Sums::lds) >= (65536 / 32) * sizeof(unsigned), "Sums::lds serves the layout, the LDS solve and the erase's bit map");
   ba_build_layout(v_, nc, np, ired, (int*)sums.lds);
@@ -1340,8 +1351,8 @@ DEVFN void ba_lm(const BaView& v_, const BaConfig& cfg, const BaOrdView& o) {
     sums.stamp(1);
     if (nvalid == 0) { if (threadIdx.x == 0) sh_error = 1; __syncthreads(); break; }
     {                                                              // :220-227 Tukey sigma, clamped
-      const double med = M > 4096 ? block_radix_select<16>(v.scratch, M, nvalid / 2, hist, sel)   // (big problems: 16 values per lane in flight, 64 per lane and sweep)
-                                  : block_radix_select<8>(v.scratch, M, nvalid / 2, hist, sel);
+      const double med = M > 4096 ? block_radix_select<16>(v.scratch, M, nvalid / 2, hist, sel, selmm)   // (big problems: 16 values per lane in flight, 64 per lane and sweep)
+                                  : block_radix_select<8>(v.scratch, M, nvalid / 2, hist, sel, selmm);
       double s2 = tukey_sigma_squared(med, (unsigned long)nvalid);
       if (s2 < cfg.min_sigma2) s2 = cfg.min_sigma2;
       if (threadIdx.x == 0) sh_sigma2 = s2;

@@ -35,10 +35,11 @@ struct BaOrdView {       // per-problem arrays of the parity mode (allocated onl
 
 // The projection pass at the committed (trial = 0) or trial state: FindNewError (:537-561) / pass 1 (:209-215).  Leaves each slot's
 // term of the error sum in o.obj and the squared error for the next median in v.scratch; returns this thread's count of
-// measurements that stay in the list.
-DEVFN int ord_errors(const BaViewG& v, const BaConfig& cfg, const BaOrdView& o, int M, double sigma2, int trial, const double* camL) {
+// measurements that stay in the list and, in sr, the range of their squared errors.
+DEVFN int ord_errors(const BaViewG& v, const BaConfig& cfg, const BaOrdView& o, int M, double sigma2, int trial, const double* camL, SelectRange& sr) {
   const double AS1* pts = trial ? v.pt_new : v.pt_pos;
   int nv = 0;
+  sr = select_range_empty();
   for (int s = threadIdx.x; s < M; s += BA_THREADS) {
     const int info = v.sl_info[s], st = SL_STATE(info);
     if (st == MS_ERASED) { o.obj[s] = 0.0; continue; }
@@ -57,6 +58,7 @@ DEVFN int ord_errors(const BaViewG& v, const BaConfig& cfg, const BaOrdView& o, 
     o.obj[s] = tukey_objective(e2, sigma2);
     const bool stays = st == MS_OK;
     v.scratch[s] = stays ? e2 : __builtin_huge_val();
+    select_range_add(sr, e2, stays);
     nv += stays ? 1 : 0;
   }
   return nv;
@@ -260,6 +262,7 @@ struct BaOrdSums {
   static constexpr int LDS_DOUBLES = LDS_SOLVE > LDS_LAYOUT ? LDS_SOLVE : LDS_LAYOUT;
   const BaView& v_; const BaViewG& v; const BaConfig& cfg; const BaOrdView& o;
   int* ired;                                                           // the driver's reduction scratch
+  int* hist; unsigned* selmm;                                      // the driver's median: prepared (block_select_publish) where `scratch` is written
   static __shared__ double lds[LDS_DOUBLES];                           // the driver's layout, solve and erase
   static __shared__ double camL[12 * 128];                             // every camera of a problem (at most 128 keyframes per map)
   static __shared__ double ssq_;                                       // dSumSquaredUpdate, from the lane that walks it to the driver
@@ -280,7 +283,10 @@ struct BaOrdSums {
   }
   DEVFN int count_valid(int M, int nc) {                                       // pass 1 (:209-215)
     load_cams(v.cam_pose, nc);
-    return ba_block_sum_i(ord_errors(v, cfg, o, M, 1.0, 0, camL), ired);
+    SelectRange sr;
+    const int nv = ord_errors(v, cfg, o, M, 1.0, 0, camL, sr);
+    block_select_publish(sr, hist, selmm);                             // (rides on the sum's barriers)
+    return ba_block_sum_i(nv, ired);
   }
   DEVFN double step(int M, int nc, int np, int nfree, double sigma2) {
     load_cams(v.cam_pose, nc);
@@ -313,7 +319,10 @@ struct BaOrdSums {
   // (:467-470: the camera updates, then the points') and dNewError in list order
   DEVFN int new_error(int M, int nc, int np, int nS, double sigma2, double& ssq, double* new_err) {
     load_cams(v.cam_new, nc);
-    const int nv = ba_block_sum_i(ord_errors(v, cfg, o, M, sigma2, 1, camL), ired);
+    SelectRange sr;
+    const int nvt = ord_errors(v, cfg, o, M, sigma2, 1, camL, sr);
+    block_select_publish(sr, hist, selmm);                             // (rides on the sum's barriers)
+    const int nv = ba_block_sum_i(nvt, ired);
     if (threadIdx.x == 0) {
       double acc = 0.0;
       for (int t = 0; t < nS; t++) { const double x = v.cam_up[t]; acc += x * x; }

@@ -228,41 +228,6 @@ HDFN bool lu_solve_n(double* A, double* b, int n) {
   return true;
 }
 
-// 6 x 6 version of lu_solve_n with every index a compile-time constant after unrolling, so A and b stay in registers
-// (a dynamically indexed local array lives in scratch memory: ~1 us per dependent access on one lane).  Same pivot rule.
-HDFN bool lu_solve6(double A[36], double b[6]) {
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    int piv = k; double best = fabs(A[k * 6 + k]);
-#pragma unroll
-    for (int r = k + 1; r < 6; r++) { const double a = fabs(A[r * 6 + k]); if (a > best) { best = a; piv = r; } }
-    if (best == 0.0) return false;
-#pragma unroll
-    for (int r = k + 1; r < 6; r++) {
-      const bool sw = (r == piv);
-#pragma unroll
-      for (int c = 0; c < 6; c++) { const double x = A[k * 6 + c], y = A[r * 6 + c]; A[k * 6 + c] = sw ? y : x; A[r * 6 + c] = sw ? x : y; }
-      const double x = b[k], y = b[r]; b[k] = sw ? y : x; b[r] = sw ? x : y;
-    }
-    const double inv = 1.0 / A[k * 6 + k];
-#pragma unroll
-    for (int r = k + 1; r < 6; r++) {
-      const double f = A[r * 6 + k] * inv;
-#pragma unroll
-      for (int c = k + 1; c < 6; c++) A[r * 6 + c] -= f * A[k * 6 + c];
-      b[r] -= f * b[k];
-    }
-  }
-#pragma unroll
-  for (int k = 5; k >= 0; k--) {
-    double s = b[k];
-#pragma unroll
-    for (int c = k + 1; c < 6; c++) s -= A[k * 6 + c] * b[c];
-    b[k] = s / A[k * 6 + k];
-  }
-  return true;
-}
-
 HDFN void inv3(const double m[9], double o[9]) {   // cofactor inverse (Eigen fixed 3x3)
   const double c00 = m[4] * m[8] - m[5] * m[7], c01 = m[5] * m[6] - m[3] * m[8], c02 = m[3] * m[7] - m[4] * m[6];
   const double det = m[0] * c00 + m[1] * c01 + m[2] * c02;
@@ -311,29 +276,58 @@ DEVFN double wave_multi_sum(double* acc) {
 template <int N> DEVFN int wave_multi_index(int lane) { return N == 64 ? lane : (N == 32 ? (lane >> 1) & 31 : (N == 16 ? (lane >> 2) & 15 : (lane >> 3) & 7)); }
 
 // k-th smallest (0-based) of n non-negative doubles in global memory or LDS (bit patterns order like the values):
-// MSB-first radix select, 8 bits per pass, stopping as soon as the selected bin holds a single value (the usual case
-// after 3 passes).  One barrier per pass: the histogram rotates through three LDS buffers (the one for pass p+2 is
-// cleared while pass p is scanned) and every wavefront scans the 256 bins redundantly, so nothing is broadcast.
-// hist: LDS [768] ints, sel: LDS [1] u64.  All threads of the workgroup call it and get the same result.
+// MSB-first radix select, 8 bits per pass, on the KEYS bits - lo, lo..hi being a range that holds the bit patterns of every
+// value that can be selected (the least and the greatest of their high words, extended by zeros and ones).  The first digit is
+// the top eight significant bits of hi - lo, so the first pass already spreads the values over the bins whatever their
+// exponent (squared pixel errors share the top byte of a double, and its neighbour nearly so); values above hi (the +inf markers
+// of the bundle adjustment) fall behind the prefix or into the last bins and are never selected (k counts values within
+// lo..hi).  It stops as soon as the selected bin holds a single value (the usual case after 2 passes).
+// One barrier per pass: the histogram rotates through three LDS buffers (the one for pass p+2 is cleared while pass p is
+// scanned) and every wavefront scans the 256 bins redundantly, so nothing is broadcast.
+// hist: LDS [768] ints aligned to 16 bytes, sel: LDS [1] u64, mm: LDS [2 * wavefronts] unsigned.  The phase that WRITES the
+// values prepares the select: every thread tracks the range of what it wrote (select_range_add: two integer instructions) and
+// calls block_select_publish before a barrier that the phase has anyway -- it clears the first two histograms (one 16-byte
+// store per thread) and leaves each wavefront's range in mm.  All threads of the workgroup then call block_radix_select and
+// get the same result.
 // The values are read RS_BATCH at a time per thread before any histogram update, so the round trips of a batch overlap
 // (the pointer type is a template parameter: an address_space(1) pointer keeps the loads global instead of flat).
 #define RS_BATCH 8
+#define VSLAM_POSE_WG 128            // the workgroups that run the select: k_pose's (values in LDS, at most VSLAM_SELECT_LDS_CAP) ...
+#define VSLAM_BA_WG 256              // ... and the bundle adjustment's (values in global memory); vslam_eval_select runs either
+#define VSLAM_SELECT_LDS_CAP 4096
+extern "C" __device__ unsigned __ockl_wfred_min_u32(unsigned);        // wavefront reductions of the device library (DPP, no LDS)
+extern "C" __device__ unsigned __ockl_wfred_max_u32(unsigned);
+struct SelectRange { unsigned lo, hi; };                               // of the high words of the bit patterns; empty: lo > hi
+DEVFN SelectRange select_range_empty() { SelectRange r; r.lo = ~0u; r.hi = 0u; return r; }
+DEVFN void select_range_add(SelectRange& r, double x, bool counts = true) {
+  const unsigned h = (unsigned)__double2hiint(x);
+  r.lo = counts && h < r.lo ? h : r.lo; r.hi = counts && h > r.hi ? h : r.hi;
+}
+DEVFN void block_select_publish(const SelectRange& r, int* hist, unsigned* mm) {
+  for (int i = threadIdx.x; i < 128; i += blockDim.x) ((int4*)hist)[i] = make_int4(0, 0, 0, 0);
+  const unsigned lo = __ockl_wfred_min_u32(r.lo), hi = __ockl_wfred_max_u32(r.hi);
+  if ((threadIdx.x & 63) == 0) { mm[2 * (threadIdx.x >> 6)] = lo; mm[2 * (threadIdx.x >> 6) + 1] = hi; }
+}
 template <int BATCH = RS_BATCH, class VP>
-DEVFN double block_radix_select(VP v, int n, int k, int* hist, unsigned long long* sel) {
-  for (int i = threadIdx.x; i < 768; i += blockDim.x) hist[i] = 0;
-  __syncthreads();
-  unsigned long long prefix = 0, mask = 0;
+DEVFN double block_radix_select(VP v, int n, int k, int* hist, unsigned long long* sel, const unsigned* mm) {
+  unsigned lo32 = mm[0], hi32 = mm[1];
+  for (int w = 1; w < (int)(blockDim.x >> 6); w++) { const unsigned l2 = mm[2 * w], h2 = mm[2 * w + 1]; lo32 = l2 < lo32 ? l2 : lo32; hi32 = h2 > hi32 ? h2 : hi32; }
+  if (hi32 < lo32) return 0.0;                                       // nothing can be selected
+  const unsigned long long lo = (unsigned long long)lo32 << 32, hi = ((unsigned long long)hi32 << 32) | 0xFFFFFFFFull;
+  int hs = 64 - __clzll((long long)(hi - lo));                       // significant bits of a key (32 or more); the bits from hs up are resolved (zero)
+  hs = hs > 63 ? 63 : hs;                                            // (non-negative doubles: bit 63 is clear)
+  unsigned long long pre = 0;                                        // the resolved bits: key >> hs of the selected value
   int kk = k;
   const int l = threadIdx.x & 63;
-  for (int pass = 0; pass < 8; pass++) {
-    const int shift = 56 - 8 * pass;
+  for (int pass = 0; ; pass++) {
+    const int shift = hs > 8 ? hs - 8 : 0;                           // this pass's digit: bits shift .. hs-1
     int* H = hist + 256 * (pass % 3);
     for (int i0 = threadIdx.x; i0 < n; i0 += BATCH * blockDim.x) {
       unsigned long long b[BATCH];
 #pragma unroll
-      for (int u = 0; u < BATCH; u++) { const int i = i0 + u * blockDim.x; b[u] = (unsigned long long)__double_as_longlong(v[i < n ? i : n - 1]); }
+      for (int u = 0; u < BATCH; u++) { const int i = i0 + u * blockDim.x; b[u] = (unsigned long long)__double_as_longlong(v[i < n ? i : n - 1]) - lo; }
 #pragma unroll
-      for (int u = 0; u < BATCH; u++) if (i0 + u * (int)blockDim.x < n && (b[u] & mask) == prefix) atomicAdd(&H[(b[u] >> shift) & 255], 1);
+      for (int u = 0; u < BATCH; u++) if (i0 + u * (int)blockDim.x < n && (b[u] >> hs) == pre) atomicAdd(&H[(b[u] >> shift) & 255], 1);
     }
     __syncthreads();
     const int h0 = H[4 * l], h1 = H[4 * l + 1], h2 = H[4 * l + 2], h3 = H[4 * l + 3];   // 4 bins per lane, shuffle prefix sum
@@ -348,25 +342,102 @@ DEVFN double block_radix_select(VP v, int n, int k, int* hist, unsigned long lon
     else if (acc + h0 + h1 + h2 > kk) { acc += h0 + h1; bin += 2; cnt = h2; }
     else { acc += h0 + h1 + h2; bin += 3; cnt = h3; }
     bin = __shfl(bin, L); acc = __shfl(acc, L); cnt = __shfl(cnt, L);
-    prefix |= (unsigned long long)bin << shift;
+    pre = (pre << (hs - shift)) | (unsigned long long)bin;
+    hs = shift;
     kk -= acc;
-    mask |= 255ull << shift;
+    if (hs == 0) break;                                            // every bit is resolved
     int* Z = hist + 256 * ((pass + 2) % 3);
     for (int i = threadIdx.x; i < 256; i += blockDim.x) Z[i] = 0;
-    if (cnt == 1 && pass < 7) {                                    // one value left under the prefix: fetch it whole
+    if (cnt == 1) {                                                // one value left under the prefix: fetch it whole
       for (int i0 = threadIdx.x; i0 < n; i0 += BATCH * blockDim.x) {
         unsigned long long b[BATCH];
 #pragma unroll
-        for (int u = 0; u < BATCH; u++) { const int i = i0 + u * blockDim.x; b[u] = (unsigned long long)__double_as_longlong(v[i < n ? i : n - 1]); }
+        for (int u = 0; u < BATCH; u++) { const int i = i0 + u * blockDim.x; b[u] = (unsigned long long)__double_as_longlong(v[i < n ? i : n - 1]) - lo; }
 #pragma unroll
-        for (int u = 0; u < BATCH; u++) if (i0 + u * (int)blockDim.x < n && (b[u] & mask) == prefix) sel[0] = b[u];
+        for (int u = 0; u < BATCH; u++) if (i0 + u * (int)blockDim.x < n && (b[u] >> hs) == pre) sel[0] = b[u];
       }
       __syncthreads();
-      prefix = sel[0];
+      pre = sel[0];
       break;
     }
   }
-  return __longlong_as_double((long long)prefix);
+  return __longlong_as_double((long long)(pre + lo));
+}
+
+// The tail of a pose iteration (myWLS::compute, then the left-multiplied update) on ONE wavefront, no barrier inside; all 64
+// lanes call both functions.
+//
+// wave_pose_solve: lane q < 27 brings sum q of the normal equations (the upper triangle of C row by row, then v).  Lane
+// 7 r + c holds element (r, c) of [C | v] (c = 6: v; the triangle mirrored as myWLS::compute does) and the elimination is
+// lu_solve_n's operation by operation (without its skip of a zero factor: x - 0 * y is x): the pivot is the first row of the
+// largest magnitude (strict >), f = a * inv, then x -= f * y as a multiply and a subtraction, back-substitution in ascending
+// column order; a zero pivot column gives mu = 0.
+// Per column two shuffle round trips: this lane's entry of the column and of the old row k (they do not depend on the pivot),
+// then the old pivot row; the column itself, which every lane searches for the pivot, and the triangle for the
+// back-substitution are read from their fixed lanes without LDS (v_readlane).  mu is left in every lane.
+DEVFN double wave_read_lane(double x, int l) {                        // l: the same in every lane
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
+}
+DEVFN void wave_pose_solve(double acc, double mu[6]) {
+  const int lane = threadIdx.x & 63;
+  const int e = lane < 42 ? lane : 41;                                // (the idle lanes shadow the last element)
+  const int r = e / 7, c = e - 7 * r;
+  int q = 21 + r;
+  if (c < 6) { const int i = r < c ? r : c, j = r < c ? c : r; q = 6 * i - (i * (i - 1)) / 2 + (j - i); }
+  double x = __shfl(acc, q);
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const double own = __shfl(x, 7 * r + k), xk = __shfl(x, 7 * k + c);   // this lane's row at column k; row k at this lane's column
+    double colk = 0.0, pv = 0.0, best = 0.0;
+    int piv = k;
+#pragma unroll
+    for (int rr = k; rr < 6; rr++) {
+      const double a = wave_read_lane(x, 7 * rr + k), m = fabs(a);
+      if (rr == k) { colk = a; pv = a; best = m; }
+      else if (m > best) { best = m; piv = rr; pv = a; }
+    }
+    if (best == 0.0) ok = false;                                      // (what follows is discarded)
+    const double xp = __shfl(x, 7 * piv + c);                         // the pivot row at this lane's column
+    const double inv = 1.0 / pv;
+    if (r == k) x = xp; else if (r == piv) x = xk;                    // rows k and piv change places
+    const double f = (r == piv ? colk : own) * inv;
+    const double fy = f * xp;
+    if (r > k && c > k) x -= fy;
+  }
+  double U[6][7];
+#pragma unroll
+  for (int k = 0; k < 6; k++)
+#pragma unroll
+    for (int cc = k; cc < 7; cc++) U[k][cc] = wave_read_lane(x, 7 * k + cc);
+#pragma unroll
+  for (int k = 5; k >= 0; k--) {
+    double s = U[k][6];
+#pragma unroll
+    for (int cc = k + 1; cc < 6; cc++) s -= U[k][cc] * mu[cc];
+    mu[k] = s / U[k][k];
+  }
+  if (!ok) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) mu[k] = 0.0;
+  }
+}
+
+// *pose = pose_mul(se3_exp(mu), *pose) with mu the same in every lane: the exponential in every lane (nothing diverges), then
+// lane o < 12 forms entry o of the product (R row-major, then t) with pose_mul's expression.  b: the Pose's 12 doubles
+// (the pointer type is a template parameter: an address_space(3) pointer keeps the accesses LDS instead of flat).
+template <class DP>
+DEVFN void wave_pose_apply(const double mu[6], DP b) {
+  const int lane = threadIdx.x & 63;
+  const Pose a = se3_exp(mu);
+  const int o = lane < 12 ? lane : 11;
+  const int i = o < 9 ? o / 3 : o - 9, j = o - 3 * (o / 3);
+  const double b0 = o < 9 ? b[j] : b[9], b1 = o < 9 ? b[3 + j] : b[10], b2 = o < 9 ? b[6 + j] : b[11];
+  const double a0 = i == 0 ? a.R[0] : (i == 1 ? a.R[3] : a.R[6]), a1 = i == 0 ? a.R[1] : (i == 1 ? a.R[4] : a.R[7]);
+  const double a2 = i == 0 ? a.R[2] : (i == 1 ? a.R[5] : a.R[8]), at = i == 0 ? a.t[0] : (i == 1 ? a.t[1] : a.t[2]);
+  const double rot = a0 * b0 + a1 * b1 + a2 * b2;
+  const double val = o < 9 ? rot : at + rot;
+  if (lane < 12) b[lane] = val;
 }
 
 #endif

@@ -360,3 +360,80 @@ extern "C" int vslam_eval_transcendental(int fn, int n, const double* x, double*
   HIPCHK(hipMemcpy(y, dy.p, sizeof(double) * n, hipMemcpyDeviceToHost));
   return VSLAM_OK;
 }
+
+// ---- self-test hooks: the median's select and the tail of a pose iteration, each in one workgroup of its kernel's size ----
+// The values are handed over as their producers do: the range of what can be selected is gathered while they are read (+inf
+// marks an entry outside the median, as in the bundle adjustment's scratch) and published before the barrier in front of the select.
+template <int THREADS, int BATCH, bool IN_LDS>
+__global__ __launch_bounds__(THREADS) void k_eval_select(const double* v, int n, int k, double* out) {
+  __shared__ __attribute__((aligned(16))) int hist[768];
+  __shared__ unsigned long long sel[1];
+  __shared__ unsigned mm[2 * (THREADS / 64)];
+  __shared__ double buf[IN_LDS ? VSLAM_SELECT_LDS_CAP : 1];
+  SelectRange sr = select_range_empty();
+  for (int i = threadIdx.x; i < n; i += THREADS) {
+    const double x = v[i];
+    if (IN_LDS) buf[i] = x;
+    select_range_add(sr, x, x != __builtin_huge_val());
+  }
+  block_select_publish(sr, hist, mm);
+  __syncthreads();
+  double r;
+  if (IN_LDS) r = block_radix_select<BATCH>(buf, n, k, hist, sel, mm);
+  else r = block_radix_select<BATCH>((const double __attribute__((address_space(1)))*)v, n, k, hist, sel, mm);
+  if (threadIdx.x == 0) out[0] = r;
+}
+
+extern "C" int vslam_eval_select(int form, int n, const double* v, int k, double* out) {
+  if (form < 0 || form > 1 || n < 1 || k < 0 || k >= n || !v || !out || (form == 0 && n > VSLAM_SELECT_LDS_CAP)) { vslam_set_error("eval_select: bad argument"); return VSLAM_E_INVALID; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { vslam_set_error("eval_select: no HIP device visible"); return VSLAM_E_HIP; }
+  DevTemp<double> dv, dr;
+  HIPCHK(dv.get(n));
+  HIPCHK(dr.get(1));
+  HIPCHK(hipMemcpy(dv.p, v, sizeof(double) * n, hipMemcpyHostToDevice));
+  if (form == 0) hipLaunchKernelGGL((k_eval_select<VSLAM_POSE_WG, RS_BATCH, true>), dim3(1), dim3(VSLAM_POSE_WG), 0, 0, (const double*)dv.p, n, k, dr.p);
+  else if (n > 4096) hipLaunchKernelGGL((k_eval_select<VSLAM_BA_WG, 16, false>), dim3(1), dim3(VSLAM_BA_WG), 0, 0, (const double*)dv.p, n, k, dr.p);   // (ba_lm's switch)
+  else hipLaunchKernelGGL((k_eval_select<VSLAM_BA_WG, 8, false>), dim3(1), dim3(VSLAM_BA_WG), 0, 0, (const double*)dv.p, n, k, dr.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(out, dr.p, sizeof(double), hipMemcpyDeviceToHost));
+  return VSLAM_OK;
+}
+
+__global__ __launch_bounds__(VSLAM_POSE_WG) void k_eval_pose_tail(const double* io_in, double* io_out) {   // in: 27 sums, pose12; out: update[6], pose12
+  __shared__ Pose pose;
+  __shared__ double up[6];
+  if (threadIdx.x < 12) ((double*)&pose)[threadIdx.x] = io_in[27 + threadIdx.x];
+  __syncthreads();
+  if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0) {
+    const int lane = threadIdx.x & 63;
+    const double acc = lane < 27 ? io_in[lane] : 0.0;
+    double mu[6];
+    wave_pose_solve(acc, mu);
+    wave_pose_apply(mu, (double*)&pose);
+    if (lane == 0) {
+#pragma unroll
+      for (int r = 0; r < 6; r++) up[r] = mu[r];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) io_out[threadIdx.x] = up[threadIdx.x];
+  if (threadIdx.x < 12) io_out[6 + threadIdx.x] = ((const double*)&pose)[threadIdx.x];
+}
+
+extern "C" int vslam_eval_pose_tail(const double* sums27, const double* pose12, double* update6, double* pose12_out) {
+  if (!sums27 || !pose12 || !update6 || !pose12_out) { vslam_set_error("eval_pose_tail: bad argument"); return VSLAM_E_INVALID; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { vslam_set_error("eval_pose_tail: no HIP device visible"); return VSLAM_E_HIP; }
+  DevTemp<double> din, dout;
+  HIPCHK(din.get(39));
+  HIPCHK(dout.get(18));
+  double in[39], outv[18];
+  memcpy(in, sums27, 27 * sizeof(double)); memcpy(in + 27, pose12, 12 * sizeof(double));
+  HIPCHK(hipMemcpy(din.p, in, sizeof(in), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_eval_pose_tail, dim3(1), dim3(VSLAM_POSE_WG), 0, 0, (const double*)din.p, dout.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpy(outv, dout.p, sizeof(outv), hipMemcpyDeviceToHost));
+  memcpy(update6, outv, 6 * sizeof(double)); memcpy(pose12_out, outv + 6, 12 * sizeof(double));
+  return VSLAM_OK;
+}

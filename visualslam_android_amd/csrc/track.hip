@@ -798,6 +798,7 @@ DEVFN void item_store(const PoseItem& it, const PoseWs& w, int e, bool all) {   
 #define POSE_GRP 8                    // add_mJ calls per register set of the chain (three sets in rotation)
 static_assert(2 * 2 * POSE_CHUNK * POSE_ENT + 2 * POSE_GRP * POSE_ENT + 64 <= SORT_CAP, "two record buffers (and the chain's two groups of read-ahead) in the sort buffer");
 static_assert(POSE_THREADS == 128 && POSE_CHUNK == 32 && POSE_GRP % 2 == 0, "wavefront 0 chains, wavefront 1 produces");
+static_assert(POSE_THREADS == VSLAM_POSE_WG && SORT_CAP == VSLAM_SELECT_LDS_CAP, "vslam_eval_select / vslam_eval_pose_tail run k_pose's workgroup");
 
 DEVFN void pose_chain_load(double (&v)[POSE_GRP], const double __attribute__((address_space(3)))* p) {
 #pragma unroll
@@ -949,12 +950,27 @@ __device__ __attribute__((noinline)) double pose_accumulate(const double PAS1* w
   return acc;
 }
 
+// The tail of an iteration, called by the chain wavefront alone (no barrier inside): lane q < 27 brings sum q.  The solve of
+// myWLS::compute (:54-62), the update multiplied onto *pose (:487 / :573) and left in up[6].  Sums of zero (no measurement found,
+// :712-716) are a singular system: a zero update.  Its own function for its own register allocation, like pose_accumulate.
+__device__ __attribute__((noinline)) void pose_tail(double acc, double PAS3* pose, double PAS3* up) {
+  double mu[6];
+  wave_pose_solve(acc, mu);
+  POSE_STAMP(6);
+  wave_pose_apply(mu, pose);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int r = 0; r < 6; r++) up[r] = mu[r];
+  }
+}
+
+// The update is applied here too: wavefront 0, which holds the sums, runs pose_tail; one barrier publishes the pose and the update.
 DEVFN void calc_pose_update(const PoseWs& ws, MapPointDev* pts, int nf, const TrackParams& tp,
-                            double dOverrideSigma, bool bMarkOutliers, double* sortbuf, double* red /* [28] */,
-                            double* up /* [6] */, int* hist /* [768] */, unsigned long long* sel /* [1] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+                            double dOverrideSigma, bool bMarkOutliers, double* sortbuf, Pose* pose /* LDS */,
+                            double* up /* LDS [6] */, int* hist /* [768] */, unsigned long long* sel /* [1] */, const unsigned* selmm /* [2 POSE_WAVES] */) {
+  const bool wave0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
   if (nf == 0) {                                                    // :712-716
-    if (threadIdx.x < 6) up[threadIdx.x] = 0.0;
+    if (wave0) pose_tail(0.0, (double PAS3*)(double*)pose, (double PAS3*)up);
     __syncthreads();
     return;
   }
@@ -962,7 +978,7 @@ DEVFN void calc_pose_update(const PoseWs& ws, MapPointDev* pts, int nf, const Tr
   double sigma2;
   if (dOverrideSigma > 0) sigma2 = dOverrideSigma;                  // :720-721
   else {                                                            // Tukey::FindSigmaSquared, jni/MEstimator.h:67-77
-    const double med = block_radix_select(sortbuf, nf, nf / 2, hist, sel);   // same order statistic as sort + [n/2]
+    const double med = block_radix_select(sortbuf, nf, nf / 2, hist, sel, selmm);   // same order statistic as sort + [n/2]
     sigma2 = tukey_sigma_squared(med, (unsigned long)nf);
   }
   POSE_STAMP(3);
@@ -976,20 +992,8 @@ DEVFN void calc_pose_update(const PoseWs& ws, MapPointDev* pts, int nf, const Tr
     }
   }
   POSE_STAMP(4);
-  if (wave == 0 && lane < 27) red[lane] = acc;
+  if (wave0) pose_tail(acc, (double PAS3*)(double*)pose, (double PAS3*)up);
   __syncthreads();
-  POSE_STAMP(5);
-  if (threadIdx.x == 0) {
-    double C[36], v[6];
-    int q = 0;
-    for (int r = 0; r < 6; r++)
-      for (int c = r; c < 6; c++) { const double x = red[q++]; C[r * 6 + c] = x; C[c * 6 + r] = x; }   // myWLS::compute mirrors the triangle, :54-58
-    for (int r = 0; r < 6; r++) v[r] = red[21 + r];
-    if (!lu_solve6(C, v)) for (int r = 0; r < 6; r++) v[r] = 0.0;
-    for (int r = 0; r < 6; r++) up[r] = v[r];
-  }
-  __syncthreads();
-  POSE_STAMP(6);
 }
 
 // KeyFrameLinearDist, jni/MapMaker.cc:705-712
@@ -1012,11 +1016,12 @@ __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VS
   MapPointDev* pts = m.pts + (size_t)s * P;
   const int* ilist = m.iter_list + (size_t)s * P;
   __shared__ double sortbuf[SORT_CAP];
-  __shared__ double red[28];
-  __shared__ double up[6], last_up[6];
+  __shared__ double red[2];
+  __shared__ double last_up[6];
   __shared__ int gcnt[4 * POSE_WAVES];
-  __shared__ int hist[768];
+  __shared__ __attribute__((aligned(16))) int hist[768];
   __shared__ unsigned long long sel[1];
+  __shared__ unsigned selmm[2 * POSE_WAVES];
   __shared__ Pose pose;
   if (threadIdx.x == 0) pose = st->pose_cur;
   if (threadIdx.x < 6) last_up[threadIdx.x] = 0.0;
@@ -1075,6 +1080,7 @@ __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VS
     const bool nonlinear = stage == 0 || iter == 0 || iter == 4 || iter == 9;
     // POSE_ILP entries per thread in flight: all their loads are issued (index clamped, no branch in between) before any
     // of them is advanced -- the loop is latency-bound at one workgroup of four waves per stream
+    SelectRange sr = select_range_empty();                           // of the squared errors this thread leaves for the median
     for (int e0 = threadIdx.x; e0 < nf; e0 += POSE_ILP * POSE_THREADS) {
       PoseItem t[POSE_ILP]; double pos[POSE_ILP][3];
 #pragma unroll
@@ -1105,16 +1111,16 @@ __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VS
         }
         const double r0 = (t[u].vfound[0] - t[u].image[0]) * t[u].sqrt_inv_noise;   // v2Error_CovScaled, :707
         const double r1 = (t[u].vfound[1] - t[u].image[1]) * t[u].sqrt_inv_noise;
-        sortbuf[e] = r0 * r0 + r1 * r1;
+        const double e2 = r0 * r0 + r1 * r1;
+        sortbuf[e] = e2;
+        select_range_add(sr, e2);
       }
     }
+    block_select_publish(sr, hist, selmm);                           // (the median's histogram and range ride on this barrier)
     __syncthreads();
     POSE_STAMP(1);
     const double override_sigma = iter > 5 ? (stage == 0 ? 1.0 : 16.0) : 0.0;
-    calc_pose_update(ws, pts, nf, tp, override_sigma, stage == 1 && iter == 9, sortbuf, red, up, hist, sel);
-    if (threadIdx.x == 0) pose = pose_mul(se3_exp(up), pose);        // :487 / :573
-    if (threadIdx.x < 6) last_up[threadIdx.x] = up[threadIdx.x];
-    __syncthreads();
+    calc_pose_update(ws, pts, nf, tp, override_sigma, stage == 1 && iter == 9, sortbuf, &pose, last_up, hist, sel, selmm);
     POSE_STAMP(7);
   }
   POSE_STAMP(8);
