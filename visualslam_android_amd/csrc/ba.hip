@@ -303,17 +303,18 @@ extern "C" int vslam_bundle_compute(vslam_bundle* b) {
         lut[n * C * PP + (size_t)h.mc[i] * PP + h.mp[i]] = i; nmeas[n * PP + h.mp[i]]++;              // GenerateMeasLUTs
       }
     }
-    HIPCHK(hipMemcpyAsync(b->res0, res.data(), sizeof(BaResult) * N, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(b->cam0, cams.data(), sizeof(Pose) * N * C, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(b->pt0, pts.data(), sizeof(double) * N * PP * 3, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(P.cam_fixed, fixed.data(), sizeof(int) * N * C, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(P.ms_p, mp.data(), sizeof(int) * N * M, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(P.ms_c, mc.data(), sizeof(int) * N * M, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(P.ms_found, found.data(), sizeof(double) * N * M * 2, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(P.ms_sin, msin.data(), sizeof(double) * N * M, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(P.lut, lut.data(), sizeof(int) * N * C * PP, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipMemcpyAsync(P.pt_nmeas, nmeas.data(), sizeof(int) * N * PP, hipMemcpyHostToDevice, b->stream));
-    HIPCHK(hipStreamSynchronize(b->stream));           // the staging vectors go out of scope
+    HostCopy c(b->stream);                             // waits before the staging vectors go out of scope
+    VCHK(c.put(b->res0, res.data(), N));
+    VCHK(c.put(b->cam0, cams.data(), N * C));
+    VCHK(c.put(b->pt0, pts.data(), N * PP * 3));
+    VCHK(c.put(P.cam_fixed, fixed.data(), N * C));
+    VCHK(c.put(P.ms_p, mp.data(), N * M));
+    VCHK(c.put(P.ms_c, mc.data(), N * M));
+    VCHK(c.put(P.ms_found, found.data(), N * M * 2));
+    VCHK(c.put(P.ms_sin, msin.data(), N * M));
+    VCHK(c.put(P.lut, lut.data(), N * C * PP));
+    VCHK(c.put(P.pt_nmeas, nmeas.data(), N * PP));
+    VCHK(c.wait());
     b->dirty = false;
   }
   // Compute leaves its result in the cameras and points: every call starts again from the caller's values (device-to-device)
@@ -339,7 +340,7 @@ extern "C" int vslam_bundle_get_timing(vslam_bundle* b, double* ms, unsigned lon
   float t = 0.f;
   HIPCHK(hipEventElapsedTime(&t, b->ev[0], b->ev[1]));
   *ms = t;
-  if (stats) { HIPCHK(hipMemcpy(stats, b->pool.lstat, sizeof(unsigned long long) * BA_LSTAT_N, hipMemcpyDeviceToHost)); stats[7] = 1; }
+  if (stats) { VCHK(host_get(b->stream, stats, b->pool.lstat, BA_LSTAT_N)); stats[7] = 1; }
   return VSLAM_OK;
 }
 
@@ -348,9 +349,7 @@ extern "C" int vslam_bundle_synchronize(vslam_bundle* b) { BCHECK(b, "null"); HI
 static int bundle_result(vslam_bundle* b, int n, BaResult* r) {
   BCHECK(b && n >= 0 && n < b->pool.N, "bad problem index");
   if (!b->uploaded) { vslam_set_error("bundle: compute has not run"); return VSLAM_E_STATE; }
-  HIPCHK(hipMemcpyAsync(r, ba_view(b->pool, n).res, sizeof(BaResult), hipMemcpyDeviceToHost, b->stream));
-  HIPCHK(hipStreamSynchronize(b->stream));
-  return VSLAM_OK;
+  return host_get(b->stream, r, ba_view(b->pool, n).res);
 }
 
 extern "C" int vslam_bundle_get_result(vslam_bundle* b, int n, int* accepted, int* converged, double* sigma_squared, double* lambda, long long* trials) {
@@ -363,29 +362,28 @@ extern "C" int vslam_bundle_get_camera(vslam_bundle* b, int n, int i, double pos
   BaResult r; int rc = bundle_result(b, n, &r); if (rc) return rc;
   BCHECK(i >= 0 && i < r.n_cams, "camera index");
   Pose p;
-  HIPCHK(hipMemcpy(&p, ba_view(b->pool, n).cam_pose + i, sizeof(Pose), hipMemcpyDeviceToHost));
+  VCHK(host_get(b->stream, &p, ba_view(b->pool, n).cam_pose + i));
   pose_to12(p, pose12);
   return VSLAM_OK;
 }
 extern "C" int vslam_bundle_get_point(vslam_bundle* b, int n, int i, double pos[3]) {
   BaResult r; int rc = bundle_result(b, n, &r); if (rc) return rc;
   BCHECK(i >= 0 && i < r.n_pts, "point index");
-  HIPCHK(hipMemcpy(pos, ba_view(b->pool, n).pt_pos + 3 * i, sizeof(double) * 3, hipMemcpyDeviceToHost));
-  return VSLAM_OK;
+  return host_get(b->stream, pos, ba_view(b->pool, n).pt_pos + 3 * i, 3);
 }
 extern "C" int vslam_bundle_get_outlier_meas(vslam_bundle* b, int n, int* pc, int cap) {
   BaResult r; int rc = bundle_result(b, n, &r); if (rc) return rc;
-  const int m = r.n_outlier_meas < cap ? r.n_outlier_meas : cap;
-  if (pc && m > 0) HIPCHK(hipMemcpy(pc, ba_view(b->pool, n).outl, sizeof(int) * 2 * m, hipMemcpyDeviceToHost));
+  HostCopy c(b->stream);
+  VCHK(c.take(pc, ba_view(b->pool, n).outl, r.n_outlier_meas, cap, 2)); VCHK(c.wait());
   return r.n_outlier_meas;
 }
 extern "C" int vslam_bundle_get_outlier_points(vslam_bundle* b, int n, int* idx, int cap) {
   BaResult r; int rc = bundle_result(b, n, &r); if (rc) return rc;
   std::vector<int> nm(r.n_pts), no(r.n_pts);
-  if (r.n_pts) {
-    HIPCHK(hipMemcpy(nm.data(), ba_view(b->pool, n).pt_nmeas, sizeof(int) * r.n_pts, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(no.data(), ba_view(b->pool, n).pt_nout, sizeof(int) * r.n_pts, hipMemcpyDeviceToHost));
-  }
+  HostCopy c(b->stream);
+  VCHK(c.get(nm.data(), ba_view(b->pool, n).pt_nmeas, r.n_pts));
+  VCHK(c.get(no.data(), ba_view(b->pool, n).pt_nout, r.n_pts));
+  VCHK(c.wait());
   int cnt = 0;
   for (int i = 0; i < r.n_pts; i++) if (nm[i] > 0 && nm[i] == no[i]) { if (idx && cnt < cap) idx[cnt] = i; cnt++; }   // GetOutliers :628-637
   return cnt;
@@ -965,19 +963,16 @@ int mm_idle(vslam_system* sys) {
 extern "C" int vslam_get_bundle_stats(vslam_system* sys, int s, int out[6]) {
   if (!sys || !out || s < 0 || s >= sys->S || !sys->ba_ws) { vslam_set_error("get_bundle_stats: bad argument"); return VSLAM_E_INVALID; }
   BaSystemWs* ws = sys->ba_ws;
-  HIPCHK(hipStreamSynchronize(sys->stream));
   { int rs = ba_sync_streams(sys); if (rs) return rs; }
   BaResult r;
-  HIPCHK(hipMemcpy(&r, ws->pool.res + s, sizeof(r), hipMemcpyDeviceToHost));
+  VCHK(host_get(sys->stream, &r, ws->pool.res + s));   // behind the map-maker streams (waited for) and the main stream
   out[0] = r.n_cams; out[1] = r.n_free; out[2] = r.n_pts; out[3] = r.n_meas; out[4] = r.counter; out[5] = r.accepted;
   return VSLAM_OK;
 }
 
 // ---- measurement ----------------------------------------------------------------------------------------------------
 static int ba_read_launch_record(vslam_system* sys, int rec, unsigned long long out[BA_LSTAT_N]) {
-  BaSystemWs* ws = sys->ba_ws;
-  HIPCHK(hipMemcpy(out, ws->pool.lstat + (size_t)rec * BA_LSTAT_N, sizeof(unsigned long long) * BA_LSTAT_N, hipMemcpyDeviceToHost));
-  return VSLAM_OK;
+  return host_get(sys->stream, out, sys->ba_ws->pool.lstat + (size_t)rec * BA_LSTAT_N, BA_LSTAT_N);
 }
 
 extern "C" int vslam_profile_ba_stats(vslam_system* sys, unsigned long long stats[8]) {
@@ -1002,12 +997,11 @@ extern "C" int vslam_profile_ba_stats(vslam_system* sys, unsigned long long stat
 // per-kernel counters cover the whole process and not a window
 extern "C" int vslam_get_ba_launch_totals(vslam_system* sys, unsigned long long stats[8]) {
   if (!sys || !stats || !sys->ba_ws) { vslam_set_error("get_ba_launch_totals: bad argument"); return VSLAM_E_INVALID; }
-  HIPCHK(hipStreamSynchronize(sys->stream));
   { int rs = ba_sync_streams(sys); if (rs) return rs; }
   BaSystemWs* ws = sys->ba_ws;
   const long n = sys->ba_launch_no < BA_LSTAT_RING ? sys->ba_launch_no : BA_LSTAT_RING;
   std::vector<unsigned long long> all((size_t)BA_LSTAT_RING * BA_LSTAT_N);
-  HIPCHK(hipMemcpy(all.data(), ws->pool.lstat, sizeof(unsigned long long) * all.size(), hipMemcpyDeviceToHost));
+  VCHK(host_get(sys->stream, all.data(), ws->pool.lstat, all.size()));
   for (int k = 0; k < BA_LSTAT_N; k++) stats[k] = 0;
   long working = 0;
   for (long i = 0; i < n; i++) { for (int k = 0; k < 7; k++) stats[k] += all[(size_t)i * BA_LSTAT_N + k]; if (all[(size_t)i * BA_LSTAT_N]) working++; }

@@ -662,7 +662,7 @@ extern "C" int vslam_init_from_stereo(vslam_system* sys, const uint8_t* gray_fir
   r = vslam_update(sys, gray_first, row_stride, 0); if (r) return r;                 // TrailTracking_Start: the first keyframe
   r = vslam_get_init_info(sys, 0, info); if (r) return r;
   if (info[0] != 1) { vslam_set_error("init_from_stereo: the first frame did not start the initialisation"); return VSLAM_E_STATE; }
-  if (n_matches > 0) HIPCHK(hipMemcpy(sys->map.trail_pos, matches_xyxy, sizeof(int) * 4 * (size_t)n_matches, hipMemcpyHostToDevice));   // stream 0, trail buffer 0
+  VCHK(host_put(sys->stream, sys->map.trail_pos, matches_xyxy, 4 * (size_t)n_matches));   // stream 0, trail buffer 0
   hipLaunchKernelGGL(k_boot_host_matches, dim3(1), dim3(1), 0, sys->stream, sys->map, 0, n_matches);
   r = vslam_press_spacebar(sys, 0); if (r) return r;
   r = vslam_update(sys, gray_second, row_stride, 0); if (r) return r;                // the frame of the second press: InitFromStereo
@@ -686,8 +686,7 @@ extern "C" int vslam_set_boot_seed(vslam_system* sys, int stream, unsigned seed)
 extern "C" int vslam_get_init_info(vslam_system* sys, int stream, int out[6]) {
   if (!sys || stream < 0 || stream >= sys->S || !out) { vslam_set_error("get_init_info: bad argument"); return VSLAM_E_INVALID; }
   TrackerState st;
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  HIPCHK(hipMemcpy(&st, sys->map.st + stream, sizeof(st), hipMemcpyDeviceToHost));
+  VCHK(host_get(sys->stream, &st, sys->map.st + stream));
   out[0] = st.init_stage; out[1] = st.n_trails; out[2] = st.boot_ok; out[3] = st.n_hom_inliers; out[4] = st.n_init_points; out[5] = st.map_good;
   return VSLAM_OK;
 }
@@ -696,12 +695,11 @@ extern "C" int vslam_get_trails(vslam_system* sys, int stream, int* out4, int ca
   if (!sys || stream < 0 || stream >= sys->S || (cap > 0 && !out4)) { vslam_set_error("get_trails: bad argument"); return VSLAM_E_INVALID; }
   if (!sys->p.bootstrap) { vslam_set_error("get_trails: created with bootstrap = 0"); return VSLAM_E_STATE; }
   TrackerState st;
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  HIPCHK(hipMemcpy(&st, sys->map.st + stream, sizeof(st), hipMemcpyDeviceToHost));
+  HostCopy c(sys->stream);
+  VCHK(c.get(&st, sys->map.st + stream)); VCHK(c.wait());
   if (n) *n = st.n_trails;
-  const int k = st.n_trails < cap ? st.n_trails : cap;
-  if (k > 0) HIPCHK(hipMemcpy(out4, sys->map.trail_pos + ((size_t)stream * 2 + st.trail_buf) * BOOT_MAX_TRAILS * 4, sizeof(int) * 4 * (size_t)k, hipMemcpyDeviceToHost));
-  return VSLAM_OK;
+  VCHK(c.take(out4, sys->map.trail_pos + ((size_t)stream * 2 + st.trail_buf) * BOOT_MAX_TRAILS * 4, st.n_trails, cap, 4));
+  return c.wait();
 }
 
 // ---- the two stages on their own (vslam_probe_homography_init, vslam_probe_plane_aligner) ------------------------------------
@@ -731,19 +729,20 @@ extern "C" int vslam_probe_homography_init(vslam_system* sys, int stream, int n,
   int* d_pos = nullptr;
   double* d_match = sys->map.boot_match + (size_t)stream * BOOT_MAX_TRAILS * 8;
   int* d_inl = sys->map.boot_inl + (size_t)stream * BOOT_MAX_TRAILS;
-  if (n > 0 && matches_xyxy) { d_pos = (int*)((char*)buf.p + off_pos); HIPCHK(hipMemcpyAsync(d_pos, matches_xyxy, sizeof(int) * 4 * (size_t)n, hipMemcpyHostToDevice, q)); }
-  else if (n > 0) HIPCHK(hipMemcpyAsync(d_match, m8, sizeof(double) * 8 * (size_t)n, hipMemcpyHostToDevice, q));
+  HostCopy c(q);                                // (behind buf: it waits before buf is freed)
+  if (n > 0 && matches_xyxy) { d_pos = (int*)((char*)buf.p + off_pos); VCHK(c.put(d_pos, matches_xyxy, 4 * (size_t)n)); }
+  else if (n > 0) VCHK(c.put(d_match, m8, 8 * (size_t)n));
   hipLaunchKernelGGL(k_probe_homography, dim3(1), dim3(BOOT_THREADS), 0, q, sys->map, sys->tp, stream, n, (const int*)d_pos, seed, max_pixel_error * max_pixel_error,
                      (double*)((char*)buf.p + off_scores), (bm::HomographyStages*)buf.p);
   HIPCHK(hipGetLastError());
   bm::HomographyStages hs;
   memset(out, 0, sizeof(*out));
-  HIPCHK(hipMemcpyAsync(&hs, buf.p, sizeof(hs), hipMemcpyDeviceToHost, q));
-  HIPCHK(hipMemcpyAsync(out->scores, (char*)buf.p + off_scores, 300 * sizeof(double), hipMemcpyDeviceToHost, q));
-  if (n > 0) HIPCHK(hipMemcpyAsync(out->matches, d_match, sizeof(double) * 8 * (size_t)n, hipMemcpyDeviceToHost, q));
-  HIPCHK(hipStreamSynchronize(q));
+  VCHK(c.get(&hs, (const bm::HomographyStages*)buf.p));
+  VCHK(c.get(out->scores, (const double*)(buf.p + off_scores), 300));
+  VCHK(c.get(out->matches, (const double*)d_match, 8 * (size_t)n));
+  VCHK(c.wait());
   if (hs.n_inliers < 0 || hs.n_inliers > n) { vslam_set_error("probe_homography_init: inlier count %d of %d matches", hs.n_inliers, n); return VSLAM_E_CAPACITY; }
-  if (hs.n_inliers > 0) HIPCHK(hipMemcpy(out->inliers, d_inl, sizeof(int) * (size_t)hs.n_inliers, hipMemcpyDeviceToHost));
+  VCHK(c.get(out->inliers, (const int*)d_inl, (size_t)hs.n_inliers)); VCHK(c.wait());
   out->ok = hs.ok; out->n = n; out->best_trial = hs.best_trial; out->n_inliers = hs.n_inliers; out->choice = hs.choice;
   for (int i = 0; i < 9; i++) { out->H_mlesac[i] = hs.H_mlesac[i]; out->H_refined[i] = hs.H_refined[i]; out->R[i] = hs.R[i]; }
   for (int i = 0; i < 3; i++) { out->t[i] = hs.t[i]; out->normal[i] = hs.n[i]; out->t_scaled[i] = hs.t_scaled[i]; }
@@ -760,14 +759,15 @@ extern "C" int vslam_probe_plane_aligner(vslam_system* sys, int stream, int n, c
   HIPCHK(buf.get(off_sums + 100 * sizeof(double)));
   hipStream_t q = sys->stream;
   HIPCHK(hipMemsetAsync(buf.p, 0, off_sums + 100 * sizeof(double), q));
-  if (n > 0) HIPCHK(hipMemcpyAsync(sys->map.boot_ws + (size_t)stream * boot_ws_stride((size_t)sys->p.max_points), pos3, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, q));
+  HostCopy c(q);                                // (behind buf: it waits before buf is freed)
+  VCHK(c.put(sys->map.boot_ws + (size_t)stream * boot_ws_stride((size_t)sys->p.max_points), pos3, 3 * (size_t)n));
   hipLaunchKernelGGL(k_probe_plane, dim3(1), dim3(BOOT_THREADS), 0, q, sys->map, sys->tp, stream, n, seed, (double*)((char*)buf.p + off_sums), (bm::PlaneStages*)buf.p);
   HIPCHK(hipGetLastError());
   bm::PlaneStages ps;
   memset(out, 0, sizeof(*out));
-  HIPCHK(hipMemcpyAsync(&ps, buf.p, sizeof(ps), hipMemcpyDeviceToHost, q));
-  HIPCHK(hipMemcpyAsync(out->sums, (char*)buf.p + off_sums, 100 * sizeof(double), hipMemcpyDeviceToHost, q));
-  HIPCHK(hipStreamSynchronize(q));
+  VCHK(c.get(&ps, (const bm::PlaneStages*)buf.p));
+  VCHK(c.get(out->sums, (const double*)(buf.p + off_sums), 100));
+  VCHK(c.wait());
   out->have = ps.have; out->n = n; out->best_trial = ps.best_trial;
   for (int i = 0; i < 3; i++) { out->mean[i] = ps.mean[i]; out->normal[i] = ps.normal[i]; out->t[i] = ps.t[i]; }
   for (int i = 0; i < 9; i++) out->R[i] = ps.R[i];

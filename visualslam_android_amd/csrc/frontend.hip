@@ -883,8 +883,7 @@ static int fe_check_subset(vslam_system* sys, const uint8_t* gray, const int* st
   }
   if (sys->p.bootstrap && n < sys->S) {
     std::vector<TrackerState> st((size_t)sys->S);
-    HIPCHK(hipStreamSynchronize(sys->stream));
-    HIPCHK(hipMemcpy(st.data(), sys->map.st, sizeof(TrackerState) * (size_t)sys->S, hipMemcpyDeviceToHost));
+    VCHK(host_get(sys->stream, st.data(), sys->map.st, (size_t)sys->S));
     for (int s = 0; s < sys->S; s++)
       if (!in_step[s] && st[s].init_stage == 1) { vslam_set_error("make_keyframe_lite_subset: stream %d has trails running and cannot be held", s); return VSLAM_E_STATE; }
   }
@@ -1070,6 +1069,8 @@ int fe_thin_new_keyframe(vslam_system* sys, int level) {
 
 // Level::vCorners of a stored keyframe (map upload with grow_map): the front-end kernels on a one-stream view whose level
 // images are the keyframe's own storage; the mask / list scratch is the front-end buffer that is not the current frame's.
+// Enqueued on the main stream and not waited for: the caller keeps the front-end stream off the scratch -- add_keyframes by the
+// wait of its upload batch, vslam_restore_stream by ordering the front-end stream behind the restore.
 __global__ void k_store_kf_corners(const uint32_t* c0, const uint32_t* c1, const uint32_t* c2, const uint32_t* c3, const int* ncorners,
                                    uint32_t* d0, uint32_t* d1, uint32_t* d2, uint32_t* d3, int* dn, int k0, int k1, int k2, int k3) {
   const int l = blockIdx.x;
@@ -1101,6 +1102,5 @@ int fe_keyframe_corners(vslam_system* sys, int s, int kf) {
   hipLaunchKernelGGL(k_store_kf_corners, dim3(NLEV), dim3(256), 0, sys->stream, scr.corners[0], scr.corners[1], scr.corners[2], scr.corners[3], scr.ncorners,
                      d[0], d[1], d[2], d[3], sys->map.kf_ncorners + ((size_t)s * K + kf) * NLEV, sys->tp.kcap[0], sys->tp.kcap[1], sys->tp.kcap[2], sys->tp.kcap[3]);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(sys->stream));
   return VSLAM_OK;
 }

@@ -1,7 +1,6 @@
 // Map upload, per-frame entry points (Tracker::TrackFrame / JNI-equivalent update) and read-back of the C ABI.
 // Every upload has one body, for n items; its per-item entry point is that body with n = 1.
-// Host-stream ordering: sys->stream is non-blocking, so a hipMemcpy on the null stream does not wait for it.  get_states, put_state and
-// download wait for the main stream themselves; every other copy in this file follows one of the three.
+// Every copy here is a HostCopy on the main stream (vslam_internal.h; DESIGN.md section 3, "Host copies").
 #include "vslam_internal.h"
 #include "patch_dev.h"
 #include <stdlib.h>
@@ -10,25 +9,8 @@
 
 #define CHK_STREAM(sys, s) do { if (!(sys) || (s) < 0 || (s) >= (sys)->S) { vslam_set_error("bad system/stream"); return VSLAM_E_INVALID; } } while (0)
 
-static int get_states(vslam_system* sys, int first, int n, TrackerState* st) {
-  HIPCHK(hipMemcpyAsync(st, sys->map.st + first, sizeof(TrackerState) * n, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  return VSLAM_OK;
-}
-static int get_state(vslam_system* sys, int s, TrackerState* st) { return get_states(sys, s, 1, st); }
-static int put_state(vslam_system* sys, int s, const TrackerState* st) {
-  HIPCHK(hipMemcpyAsync(sys->map.st + s, st, sizeof(TrackerState), hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  return VSLAM_OK;
-}
-// read-back of n elements of a device array (n = 0 allowed), after everything the main stream holds
-template <class T>
-static int download(vslam_system* sys, const T* src, int n, std::vector<T>& out) {
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  out.resize(n > 0 ? n : 0);
-  if (n > 0) HIPCHK(hipMemcpy(out.data(), src, sizeof(T) * n, hipMemcpyDeviceToHost));
-  return VSLAM_OK;
-}
+static int get_state(vslam_system* sys, int s, TrackerState* st) { return host_get(sys->stream, st, sys->map.st + s); }
+static int put_state(vslam_system* sys, int s, const TrackerState* st) { return host_put(sys->stream, sys->map.st + s, st); }
 
 // one pyramid level of n stored keyframes: (a+b+c+d+2)>>2 (jni/KeyFrame.cc:19-23, see frontend.hip); blockIdx.z = image, images
 // sstride / dstride bytes apart
@@ -53,21 +35,22 @@ static int add_keyframes(vslam_system* sys, int s, int n, const double* pose12, 
   const LevelGeom* g = sys->geom;
   uint8_t* lvl[NLEV]; size_t ls[NLEV];
   for (int l = 0; l < NLEV; l++) { ls[l] = (size_t)g[l].pitch * g[l].h; lvl[l] = sys->map.kf_img[l] + ((size_t)s * K + k) * ls[l]; }
-  for (int i = 0; i < n; i++)
-    HIPCHK(hipMemcpy2DAsync(lvl[0] + (size_t)i * ls[0], g[0].pitch, gray + (size_t)i * image_stride, row_stride, g[0].w, g[0].h, hipMemcpyHostToDevice, sys->stream));
+  std::vector<Pose> p((size_t)n); std::vector<int> fx((size_t)n);
+  HostCopy c(sys->stream);                              // one wait, at the end: the host arrays are done with
+  for (int i = 0; i < n; i++) VCHK(c.put2d(lvl[0] + (size_t)i * ls[0], g[0].pitch, gray + (size_t)i * image_stride, row_stride, g[0].w, g[0].h));
   for (int l = 1; l < NLEV; l++)
     hipLaunchKernelGGL(k_halve_batch, dim3((g[l].w + 255) / 256, g[l].h, n), dim3(256), 0, sys->stream, lvl[l - 1], g[l - 1].pitch, ls[l - 1], lvl[l], g[l].pitch, ls[l], g[l].w, g[l].h);
-  std::vector<Pose> p((size_t)n); std::vector<int> fx((size_t)n);
   for (int i = 0; i < n; i++) { p[i] = pose_from12(pose12 + 12 * i); fx[i] = fixed[i] ? 1 : 0; }
-  HIPCHK(hipMemcpyAsync(sys->map.kf_pose + (size_t)s * K + k, p.data(), sizeof(Pose) * n, hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemcpyAsync(sys->map.kf_fixed + (size_t)s * K + k, fx.data(), sizeof(int) * n, hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemcpyAsync(sys->map.kf_depth + ((size_t)s * K + k) * 2, depth_mean_sigma, sizeof(double) * 2 * n, hipMemcpyHostToDevice, sys->stream));
+  VCHK(c.put(sys->map.kf_pose + (size_t)s * K + k, p.data(), n));
+  VCHK(c.put(sys->map.kf_fixed + (size_t)s * K + k, fx.data(), n));
+  VCHK(c.put(sys->map.kf_depth + ((size_t)s * K + k) * 2, depth_mean_sigma, (size_t)2 * n));
   HIPCHK(hipMemsetAsync(sys->map.kf_meas + ((size_t)s * K + k) * sys->p.max_points, 0, sizeof(MeasDev) * sys->p.max_points * (size_t)n, sys->stream));
   if (sys->p.grow_map || sys->p.idle_iterations != 0)                   // Level::vCorners, needed as an epipolar-search target: from the stored
-    for (int i = 0; i < n; i++) { r = fe_keyframe_corners(sys, s, k + i); if (r) return r; }   // images alone, one keyframe at a time
+    for (int i = 0; i < n; i++) { r = fe_keyframe_corners(sys, s, k + i); if (r) return r; }   // images alone, one keyframe at a time (c's wait gives their scratch back)
   r = reloc_keyframe_sbi(sys, s, k, n); if (r) return r;                // KeyFrame::pSBI (relocalise)
   st.n_kf = k + n;
-  r = put_state(sys, s, &st); if (r) return r;         // (synchronises: the host arrays above are done with)
+  VCHK(c.put(sys->map.st + s, &st));
+  VCHK(c.wait());
   return k;
 }
 
@@ -104,16 +87,17 @@ extern "C" int vslam_map_add_points(vslam_system* sys, int s, int n, const doubl
     for (int q = 0; q < 3; q++) { mp[i].pos[q] = pos[3 * i + q]; mp[i].right[q] = right[3 * i + q]; mp[i].down[q] = down[3 * i + q]; }
     mp[i].src_kf = src_keyframe[i]; mp[i].src_level = src_level[i]; mp[i].irx = ir_xy[2 * i]; mp[i].iry = ir_xy[2 * i + 1];
   }
-  HIPCHK(hipMemcpy(sys->map.pts + (size_t)s * P + st.n_points, mp.data(), sizeof(MapPointDev) * n, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(sys->map.td + (size_t)s * P + st.n_points, td.data(), sizeof(TrackData) * n, hipMemcpyHostToDevice));
-  {
-    std::vector<int> lv(n, -1), fl(n, 0);
-    HIPCHK(hipMemcpy(sys->map.pt_level + (size_t)s * P + st.n_points, lv.data(), sizeof(int) * n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(sys->map.pt_flags + (size_t)s * P + st.n_points, fl.data(), sizeof(int) * n, hipMemcpyHostToDevice));
-  }
+  const std::vector<int> lv(n, -1), fl(n, 0);
+  const size_t at = (size_t)s * P + st.n_points;
   st.n_points += n;
   st.newq_head = st.n_points;                 // uploaded points are not "newly made" (mqNewQueue holds AddPointEpipolar's)
-  r = put_state(sys, s, &st); if (r) return r;
+  HostCopy c(sys->stream);
+  VCHK(c.put(sys->map.pts + at, mp.data(), n));
+  VCHK(c.put(sys->map.td + at, td.data(), n));
+  VCHK(c.put(sys->map.pt_level + at, lv.data(), n));
+  VCHK(c.put(sys->map.pt_flags + at, fl.data(), n));
+  VCHK(c.put(sys->map.st + s, &st));
+  VCHK(c.wait());
   return st.n_points;
 }
 
@@ -147,17 +131,19 @@ extern "C" int vslam_map_add_measurements(vslam_system* sys, int s, int n, const
   MapPointDev* d_pts = sys->map.pts + (size_t)s * P + p0;
   std::vector<MeasDev> km(nk * np);
   std::vector<MapPointDev> pts(np);
-  HIPCHK(hipMemcpy2D(km.data(), np * sizeof(MeasDev), d_km, P * sizeof(MeasDev), np * sizeof(MeasDev), nk, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(pts.data(), d_pts, sizeof(MapPointDev) * np, hipMemcpyDeviceToHost));
+  HostCopy c(sys->stream);
+  VCHK(c.get2d(km.data(), np * sizeof(MeasDev), d_km, P * sizeof(MeasDev), np * sizeof(MeasDev), nk));
+  VCHK(c.get(pts.data(), d_pts, np));
+  VCHK(c.wait());
   for (int i = 0; i < n; i++) {
     MeasDev& m = km[(size_t)(keyframe[i] - k0) * np + (point[i] - p0)];
     if (!m.valid) pts[point[i] - p0].n_meas_kfs++;   // MapMakerData::sMeasurementKFs.insert
     memset(&m, 0, sizeof(m));
     m.root[0] = root_pos[2 * i]; m.root[1] = root_pos[2 * i + 1]; m.valid = 1; m.level = (signed char)level[i]; m.subpix = subpix[i] ? 1 : 0; m.source = (signed char)source[i];
   }
-  HIPCHK(hipMemcpy2D(d_km, P * sizeof(MeasDev), km.data(), np * sizeof(MeasDev), np * sizeof(MeasDev), nk, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(d_pts, pts.data(), sizeof(MapPointDev) * np, hipMemcpyHostToDevice));
-  return VSLAM_OK;
+  VCHK(c.put2d(d_km, P * sizeof(MeasDev), km.data(), np * sizeof(MeasDev), np * sizeof(MeasDev), nk));
+  VCHK(c.put(d_pts, pts.data(), np));
+  return c.wait();
 }
 
 extern "C" int vslam_map_add_measurement(vslam_system* sys, int s, int keyframe, int point, int level, const double root_pos[2],
@@ -174,7 +160,7 @@ extern "C" int vslam_map_set_good(vslam_system* sys, int s) {
   int r = get_state(sys, s, &st); if (r) return r;
   if (st.n_kf < 1) { vslam_set_error("map_set_good: no keyframes"); return VSLAM_E_STATE; }
   double dd[2];
-  HIPCHK(hipMemcpy(dd, sys->map.kf_depth + (size_t)s * sys->p.max_keyframes * 2, sizeof(dd), hipMemcpyDeviceToHost));
+  VCHK(host_get(sys->stream, dd, sys->map.kf_depth + (size_t)s * sys->p.max_keyframes * 2, 2));
   st.map_good = 1;
   st.wiggle_depth_norm = sys->p.wiggle_scale / dd[0];   // jni/MapMaker.cc:353
   st.ba_converged_recent = 1; st.ba_converged_full = 1; // MapMaker::Reset :72-73
@@ -225,8 +211,7 @@ int map_init_states(vslam_system* sys) {
   std::vector<TrackerState> v(sys->S);
   memset(v.data(), 0, sizeof(TrackerState) * sys->S);
   for (auto& st : v) tracker_reset_fields(st, sys->p.pvs_shuffle_seed);
-  HIPCHK(hipMemcpy(sys->map.st, v.data(), sizeof(TrackerState) * sys->S, hipMemcpyHostToDevice));
-  return VSLAM_OK;
+  return host_put(sys->stream, sys->map.st, v.data(), sys->S);
 }
 
 // ---- per-frame entry points -------------------------------------------------------------------------------------
@@ -309,10 +294,9 @@ extern "C" int vslam_map_set_point_positions(vslam_system* sys, int s, int first
   if (n == 0) return VSLAM_OK;
   const int P = sys->p.max_points;
   std::vector<MapPointDev> mp(n);
-  HIPCHK(hipMemcpy(mp.data(), sys->map.pts + (size_t)s * P + first, sizeof(MapPointDev) * n, hipMemcpyDeviceToHost));
+  VCHK(host_get(sys->stream, mp.data(), sys->map.pts + (size_t)s * P + first, n));
   for (int i = 0; i < n; i++) for (int q = 0; q < 3; q++) mp[i].pos[q] = pos3[3 * i + q];
-  HIPCHK(hipMemcpy(sys->map.pts + (size_t)s * P + first, mp.data(), sizeof(MapPointDev) * n, hipMemcpyHostToDevice));
-  return VSLAM_OK;
+  return host_put(sys->stream, sys->map.pts + (size_t)s * P + first, mp.data(), n);
 }
 
 extern "C" int vslam_map_set_keyframe_pose(vslam_system* sys, int s, int keyframe, const double pose12[12]) {
@@ -321,8 +305,7 @@ extern "C" int vslam_map_set_keyframe_pose(vslam_system* sys, int s, int keyfram
   int r = get_state(sys, s, &st); if (r) return r;
   if (!pose12 || keyframe < 0 || keyframe >= st.n_kf) { vslam_set_error("map_set_keyframe_pose: bad argument"); return VSLAM_E_INVALID; }
   const Pose p = pose_from12(pose12);
-  HIPCHK(hipMemcpy(sys->map.kf_pose + (size_t)s * sys->p.max_keyframes + keyframe, &p, sizeof(Pose), hipMemcpyHostToDevice));
-  return VSLAM_OK;
+  return host_put(sys->stream, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes + keyframe, &p);
 }
 
 static const char* kStageNames[] = {"pyr_fast0", "fast_lvl", "compact", "pvs", "plan_coarse", "search_coarse", "pose_coarse",
@@ -397,7 +380,7 @@ extern "C" int vslam_get_states(vslam_system* sys, int first, int n, vslam_track
   if (!sys || !out || first < 0 || n < 0 || first + n > sys->S) { vslam_set_error("get_states: bad argument"); return VSLAM_E_INVALID; }
   if (n == 0) return VSLAM_OK;
   std::vector<TrackerState> v((size_t)n);
-  int r = get_states(sys, first, n, v.data()); if (r) return r;
+  int r = host_get(sys->stream, v.data(), sys->map.st + first, n); if (r) return r;
   for (int i = 0; i < n; i++) export_state(sys, v[(size_t)i], out + i);
   return VSLAM_OK;
 }
@@ -492,7 +475,8 @@ extern "C" int vslam_load_map(vslam_system* sys, int s, const char* dir) {
   int np = 0, nkf = 0;
   r = vslam_read_map_dump(dir, pos.data(), lev.data(), n, &np, poses.data(), nk, &nkf); if (r) return r;
   std::vector<MapPointDev> p;
-  r = download(sys, sys->map.pts + (size_t)s * sys->p.max_points, n, p); if (r) return r;
+  HostCopy c(sys->stream);
+  VCHK(c.get(p, sys->map.pts + (size_t)s * sys->p.max_points, n)); VCHK(c.wait());
   int good = 0;
   for (int i = 0; i < n; i++) if (!p[i].bad) good++;
   if (np != good || nkf != nk) { vslam_set_error("load_map: the dump holds %d points and %d keyframes, the map %d good points and %d keyframes", np, nkf, good, nk); return VSLAM_E_STATE; }
@@ -503,7 +487,7 @@ extern "C" int vslam_load_map(vslam_system* sys, int s, const char* dir) {
     for (int q = 0; q < 3; q++) p[i].pos[q] = pos[3 * (size_t)k + q];
     k++;
   }
-  if (n > 0) HIPCHK(hipMemcpy(sys->map.pts + (size_t)s * sys->p.max_points, p.data(), sizeof(MapPointDev) * n, hipMemcpyHostToDevice));
+  VCHK(c.put(sys->map.pts + (size_t)s * sys->p.max_points, p.data(), n)); VCHK(c.wait());
   for (int kf = 0; kf < nk; kf++) { r = vslam_map_set_keyframe_pose(sys, s, kf, poses.data() + 12 * (size_t)kf); if (r) return r; }
   return VSLAM_OK;
 }
@@ -531,9 +515,11 @@ extern "C" int vslam_get_point_tracks(vslam_system* sys, int s, int* found, int*
   const int n = st.n_points < cap ? st.n_points : cap;
   std::vector<TrackData> td;
   std::vector<int> lv, fl;
-  r = download(sys, sys->map.td + (size_t)s * sys->p.max_points, n, td); if (r) return r;
-  r = download(sys, sys->map.pt_level + (size_t)s * sys->p.max_points, n, lv); if (r) return r;
-  r = download(sys, sys->map.pt_flags + (size_t)s * sys->p.max_points, n, fl); if (r) return r;
+  HostCopy c(sys->stream);
+  VCHK(c.get(td, sys->map.td + (size_t)s * sys->p.max_points, n));
+  VCHK(c.get(lv, sys->map.pt_level + (size_t)s * sys->p.max_points, n));
+  VCHK(c.get(fl, sys->map.pt_flags + (size_t)s * sys->p.max_points, n));
+  VCHK(c.wait());
   for (int i = 0; i < n; i++) {
     if (found) found[i] = (fl[i] & TDF_FOUND) ? 1 : 0;
     if (searched) searched[i] = (fl[i] & TDF_SEARCHED) ? 1 : 0;
@@ -550,8 +536,8 @@ extern "C" int vslam_get_points(vslam_system* sys, int s, double* pos3, int* bad
   TrackerState st;
   int r = get_state(sys, s, &st); if (r) return r;
   const int n = st.n_points < cap ? st.n_points : cap;
-  std::vector<MapPointDev> p;
-  r = download(sys, sys->map.pts + (size_t)s * sys->p.max_points, n, p); if (r) return r;
+  std::vector<MapPointDev> p((size_t)(n > 0 ? n : 0));
+  r = host_get(sys->stream, p.data(), sys->map.pts + (size_t)s * sys->p.max_points, p.size()); if (r) return r;
   for (int i = 0; i < n; i++) {
     if (pos3) for (int q = 0; q < 3; q++) pos3[3 * i + q] = p[i].pos[q];
     if (bad) bad[i] = p[i].bad;
@@ -564,9 +550,9 @@ extern "C" int vslam_get_points(vslam_system* sys, int s, double* pos3, int* bad
 extern "C" int vslam_get_keyframe_pose(vslam_system* sys, int s, int k, double pose12[12]) {
   CHK_STREAM(sys, s);
   if (k < 0 || k >= sys->p.max_keyframes || !pose12) return VSLAM_E_INVALID;
-  std::vector<Pose> p;
-  int r = download(sys, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes + k, 1, p); if (r) return r;
-  pose_to12(p[0], pose12);
+  Pose p;
+  int r = host_get(sys->stream, &p, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes + k); if (r) return r;
+  pose_to12(p, pose12);
   return VSLAM_OK;
 }
 
@@ -575,8 +561,8 @@ extern "C" int vslam_get_keyframe_pose(vslam_system* sys, int s, int k, double p
 static int nearest_keyframe_dist(vslam_system* sys, int s, TrackerState* st, double* dist) {
   int r = get_state(sys, s, st); if (r) return r;
   if (st->n_kf < 1) { vslam_set_error("no keyframes"); return VSLAM_E_STATE; }
-  std::vector<Pose> kp;
-  r = download(sys, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes, st->n_kf, kp); if (r) return r;
+  std::vector<Pose> kp((size_t)st->n_kf);
+  r = host_get(sys->stream, kp.data(), sys->map.kf_pose + (size_t)s * sys->p.max_keyframes, kp.size()); if (r) return r;
   const Pose ic = pose_inverse(st->pose_final);
   double best = 9999999999.9;                                      // ClosestKeyFrame :737-758 with KeyFrameLinearDist :705-712
   for (int k = 0; k < st->n_kf; k++) {
@@ -617,9 +603,11 @@ extern "C" int vslam_save_map(vslam_system* sys, int s, const char* dir) {
   int r = get_state(sys, s, &st); if (r) return r;
   const int n = st.n_points, nk = st.n_kf;
   std::vector<MapPointDev> p;
-  r = download(sys, sys->map.pts + (size_t)s * sys->p.max_points, n, p); if (r) return r;
   std::vector<Pose> kp;
-  r = download(sys, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes, nk, kp); if (r) return r;
+  HostCopy c(sys->stream);
+  VCHK(c.get(p, sys->map.pts + (size_t)s * sys->p.max_points, n));
+  VCHK(c.get(kp, sys->map.kf_pose + (size_t)s * sys->p.max_keyframes, nk));
+  VCHK(c.wait());
   char path[4096];
   snprintf(path, sizeof(path), "%s/map.dump", dir);
   FILE* f = fopen(path, "w");
@@ -650,8 +638,8 @@ extern "C" int vslam_get_keyframe_measurements(vslam_system* sys, int s, int k, 
   int r = get_state(sys, s, &st); if (r) return r;
   if (k < 0 || k >= st.n_kf) return VSLAM_E_INVALID;
   const int P = sys->p.max_points;
-  std::vector<MeasDev> km;
-  r = download(sys, sys->map.kf_meas + ((size_t)s * sys->p.max_keyframes + k) * P, st.n_points, km); if (r) return r;
+  std::vector<MeasDev> km((size_t)(st.n_points > 0 ? st.n_points : 0));
+  r = host_get(sys->stream, km.data(), sys->map.kf_meas + ((size_t)s * sys->p.max_keyframes + k) * P, km.size()); if (r) return r;
   int n = 0;
   for (int i = 0; i < st.n_points; i++) {
     if (!km[i].valid) continue;
@@ -674,9 +662,11 @@ extern "C" int vslam_get_templates(vslam_system* sys, int s, int first, int n, u
   std::vector<TrackData> td;
   std::vector<uint8_t> raw;
   std::vector<int> fl;
-  int r = download(sys, sys->map.td + (size_t)s * P + first, n, td); if (r) return r;
-  r = download(sys, sys->map.tmpl + ((size_t)s * P + first) * TMPL_PITCH, n * TMPL_PITCH, raw); if (r) return r;
-  r = download(sys, sys->map.pt_flags + (size_t)s * P + first, n, fl); if (r) return r;
+  HostCopy c(sys->stream);
+  VCHK(c.get(td, sys->map.td + (size_t)s * P + first, n));
+  VCHK(c.get(raw, sys->map.tmpl + ((size_t)s * P + first) * TMPL_PITCH, n * TMPL_PITCH));
+  VCHK(c.get(fl, sys->map.pt_flags + (size_t)s * P + first, n));
+  VCHK(c.wait());
   for (int i = 0; i < n; i++) {
     if (tmpl) memcpy(tmpl + (size_t)i * PS * PS, raw.data() + (size_t)i * TMPL_PITCH, (size_t)PS * PS);
     if (sum) sum[i] = td[i].tsum;

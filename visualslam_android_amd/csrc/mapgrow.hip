@@ -572,14 +572,8 @@ int grow_idle_refind(vslam_system* sys, int mode) {
 extern "C" int vslam_get_keyframe_corners(vslam_system* sys, int stream, int keyframe, int level, uint32_t* corners, int cap, int* n) {
   if (!sys || stream < 0 || stream >= sys->S || keyframe < 0 || keyframe >= sys->p.max_keyframes || level < 0 || level >= NLEV) { vslam_set_error("get_keyframe_corners: bad argument"); return VSLAM_E_INVALID; }
   if (!keeps_kf_corners(sys)) { vslam_set_error("get_keyframe_corners: keyframe corner lists are only kept with grow_map or idle_iterations"); return VSLAM_E_STATE; }
-  HIPCHK(hipStreamSynchronize(sys->stream));
   const size_t slot = (size_t)stream * sys->p.max_keyframes + keyframe;
-  int cnt = 0;
-  HIPCHK(hipMemcpy(&cnt, sys->map.kf_ncorners + slot * NLEV + level, sizeof(int), hipMemcpyDeviceToHost));
-  if (n) *n = cnt;
-  const int m = cnt < cap ? cnt : cap;
-  if (corners && m > 0) HIPCHK(hipMemcpy(corners, sys->map.kf_corners[level] + slot * sys->tp.kcap[level], (size_t)m * 4, hipMemcpyDeviceToHost));
-  return VSLAM_OK;
+  return HostCopy(sys->stream).counted(sys->map.kf_ncorners + slot * NLEV + level, n, corners, sys->map.kf_corners[level] + slot * sys->tp.kcap[level], cap);
 }
 
 #ifdef VSLAM_BA_PROF

@@ -85,13 +85,13 @@ extern "C" int vslam_minipatch_sample(vslam_system* sys, int stream, int n, cons
   DevTemp<int> pos, flag; DevTemp<uint8_t> patch;      // of this call, each with 64 bytes of slack
   HIPCHK(pos.get(2 * (size_t)n + 16)); HIPCHK(patch.get((size_t)MP_PIX * n + 64)); HIPCHK(flag.get((size_t)n + 16));
   int* d_pos = pos.p; uint8_t* d_patch = patch.p; int* d_ok = flag.p;
-  HIPCHK(hipMemcpyAsync(d_pos, pos_xy, sizeof(int) * 2 * n, hipMemcpyHostToDevice, sys->stream));
+  HostCopy c(sys->stream);                             // (behind the buffers: it waits before they are freed)
+  VCHK(c.put(d_pos, pos_xy, 2 * (size_t)n));
   hipLaunchKernelGGL(k_minipatch_sample, dim3(n), dim3(128), 0, sys->stream, sys->fr.img[0] + (size_t)stream * sys->fr.img_sstride[0],
                      sys->fr.img_pitch[0], sys->geom[0].w, sys->geom[0].h, d_pos, n, d_patch, d_ok);
-  HIPCHK(hipMemcpyAsync(patches, d_patch, (size_t)MP_PIX * n, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipMemcpyAsync(ok, d_ok, sizeof(int) * n, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  return VSLAM_OK;
+  VCHK(c.get(patches, (const uint8_t*)d_patch, (size_t)MP_PIX * n));
+  VCHK(c.get(ok, (const int*)d_ok, n));
+  return c.wait();
 }
 
 extern "C" int vslam_minipatch_find(vslam_system* sys, int stream, int n, const uint8_t* patches, int* pos_xy, int range, int max_ssd,
@@ -104,16 +104,16 @@ extern "C" int vslam_minipatch_find(vslam_system* sys, int stream, int n, const 
   HIPCHK(pos.get(2 * (size_t)n + 16)); HIPCHK(patch.get((size_t)MP_PIX * n + 64)); HIPCHK(flag.get((size_t)n + 16));
   int* d_pos = pos.p; uint8_t* d_patch = patch.p; int* d_found = flag.p;
   int nc = 0;
-  HIPCHK(hipMemcpyAsync(&nc, sys->fr.ncorners + stream * NLEV, sizeof(int), hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipMemcpyAsync(d_pos, pos_xy, sizeof(int) * 2 * n, hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipMemcpyAsync(d_patch, patches, (size_t)MP_PIX * n, hipMemcpyHostToDevice, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
+  HostCopy c(sys->stream);                             // (behind the buffers: it waits before they are freed)
+  VCHK(c.get(&nc, sys->fr.ncorners + stream * NLEV));
+  VCHK(c.put(d_pos, (const int*)pos_xy, 2 * (size_t)n));
+  VCHK(c.put(d_patch, patches, (size_t)MP_PIX * n));
+  VCHK(c.wait());
   const LevelGeom& g = sys->geom[0];
   hipLaunchKernelGGL(k_minipatch_find, dim3(n), dim3(64), 0, sys->stream, sys->fr.img[0] + (size_t)stream * sys->fr.img_sstride[0],
                      sys->fr.img_pitch[0], g.w, g.h, sys->fr.corners[0] + (size_t)stream * g.cap, sys->fr.rowlut[0] + (size_t)stream * (g.h + 1), nc,
                      d_patch, d_pos, n, range, max_ssd, d_found);
-  HIPCHK(hipMemcpyAsync(pos_xy, d_pos, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipMemcpyAsync(found, d_found, sizeof(int) * n, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  return VSLAM_OK;
+  VCHK(c.get(pos_xy, (const int*)d_pos, 2 * (size_t)n));
+  VCHK(c.get(found, (const int*)d_found, n));
+  return c.wait();
 }

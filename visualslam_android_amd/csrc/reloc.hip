@@ -177,25 +177,25 @@ extern "C" int vslam_attempt_recovery(vslam_system* sys) {
 static int reloc_check(vslam_system* sys, int stream, const char* who) {
   if (!sys || stream < 0 || stream >= sys->S) { vslam_set_error("%s: bad system/stream", who); return VSLAM_E_INVALID; }
   if (!sys->p.relocalise) { vslam_set_error("%s: created with relocalise = 0", who); return VSLAM_E_STATE; }
-  HIPCHK(hipStreamSynchronize(sys->stream));
   return VSLAM_OK;
 }
 
 extern "C" int vslam_read_keyframe_sbi(vslam_system* sys, int stream, int keyframe, float* tmpl, float* jacs) {
   int r = reloc_check(sys, stream, "read_keyframe_sbi"); if (r) return r;
   int nk = 0;
-  HIPCHK(hipMemcpy(&nk, &sys->map.st[stream].n_kf, sizeof(int), hipMemcpyDeviceToHost));
+  HostCopy c(sys->stream);
+  VCHK(c.get(&nk, &sys->map.st[stream].n_kf)); VCHK(c.wait());
   if (keyframe < 0 || keyframe >= nk) { vslam_set_error("read_keyframe_sbi: keyframe %d of %d", keyframe, nk); return VSLAM_E_INVALID; }
   const size_t N = small_pixels(sys), slot = (size_t)stream * sys->p.max_keyframes + keyframe;
-  if (tmpl) HIPCHK(hipMemcpy(tmpl, sys->reloc.kf_tmpl + slot * N, N * sizeof(float), hipMemcpyDeviceToHost));
-  if (jacs) HIPCHK(hipMemcpy(jacs, sys->reloc.kf_jacs + slot * N * 2, N * 2 * sizeof(float), hipMemcpyDeviceToHost));
-  return VSLAM_OK;
+  if (tmpl) VCHK(c.get(tmpl, sys->reloc.kf_tmpl + slot * N, N));
+  if (jacs) VCHK(c.get(jacs, sys->reloc.kf_jacs + slot * N * 2, N * 2));
+  return c.wait();
 }
 
 extern "C" int vslam_get_reloc_info(vslam_system* sys, int stream, int out_i[4], double out_d[24]) {
   int r = reloc_check(sys, stream, "get_reloc_info"); if (r) return r;
   RelocInfo ri;
-  HIPCHK(hipMemcpy(&ri, sys->reloc.info + stream, sizeof(ri), hipMemcpyDeviceToHost));
+  VCHK(host_get(sys->stream, &ri, sys->reloc.info + stream));
   if (out_i) { out_i[0] = ri.attempts; out_i[1] = ri.successes; out_i[2] = ri.best; out_i[3] = ri.frame; }
   if (out_d) {
     out_d[0] = ri.best_zmssd; out_d[1] = ri.score;
@@ -209,13 +209,12 @@ extern "C" int vslam_get_reloc_info(vslam_system* sys, int stream, int out_i[4],
 extern "C" int vslam_read_reloc_attempt(vslam_system* sys, int stream, float* cur_tmpl, double* zmssd, int cap) {
   int r = reloc_check(sys, stream, "read_reloc_attempt"); if (r) return r;
   RelocInfo ri;
-  HIPCHK(hipMemcpy(&ri, sys->reloc.info + stream, sizeof(ri), hipMemcpyDeviceToHost));
-  if (ri.attempts < 1) { vslam_set_error("read_reloc_attempt: the stream has not attempted a recovery"); return VSLAM_E_STATE; }
   int nk = 0;
-  HIPCHK(hipMemcpy(&nk, &sys->map.st[stream].n_kf, sizeof(int), hipMemcpyDeviceToHost));
+  HostCopy c(sys->stream);
+  VCHK(c.get(&ri, sys->reloc.info + stream)); VCHK(c.get(&nk, &sys->map.st[stream].n_kf)); VCHK(c.wait());
+  if (ri.attempts < 1) { vslam_set_error("read_reloc_attempt: the stream has not attempted a recovery"); return VSLAM_E_STATE; }
   const size_t N = small_pixels(sys);
-  if (cur_tmpl) HIPCHK(hipMemcpy(cur_tmpl, sys->reloc.cur_tmpl + (size_t)stream * N, N * sizeof(float), hipMemcpyDeviceToHost));
-  const int n = nk < cap ? nk : cap;
-  if (zmssd && n > 0) HIPCHK(hipMemcpy(zmssd, sys->reloc.scores + (size_t)stream * sys->p.max_keyframes, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  if (cur_tmpl) VCHK(c.get(cur_tmpl, sys->reloc.cur_tmpl + (size_t)stream * N, N));
+  VCHK(c.take(zmssd, sys->reloc.scores + (size_t)stream * sys->p.max_keyframes, nk, cap)); VCHK(c.wait());
   return nk;
 }

@@ -119,9 +119,7 @@ extern "C" int vslam_reset_streams(vslam_system* sys, const int* streams, int n)
 
 extern "C" int vslam_get_reset_info(vslam_system* sys, int stream, int out[4]) {
   if (!sys || stream < 0 || stream >= sys->S || !out) { vslam_set_error("get_reset_info: bad argument"); return VSLAM_E_INVALID; }
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  HIPCHK(hipMemcpy(out, sys->reset_info + 4 * (size_t)stream, 4 * sizeof(int), hipMemcpyDeviceToHost));
-  return VSLAM_OK;
+  return host_get(sys->stream, out, sys->reset_info + 4 * (size_t)stream, 4);
 }
 
 extern "C" int vslam_get_reset_timing(vslam_system* sys, double* ms) {

@@ -173,8 +173,7 @@ static int snap_blocks(size_t bytes) {
 static int snap_source(vslam_system* sys, int s, const char* who, TrackerState* st, SnapCounts* c) {
   SNAP_CHK_STREAM(sys, s, who);
   if (sys->frame_open) { vslam_set_error("%s: a frame is open (vslam_finish_frame first)", who); return VSLAM_E_STATE; }
-  HIPCHK(hipMemcpyAsync(st, sys->map.st + s, sizeof(TrackerState), hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
+  VCHK(host_get(sys->stream, st, sys->map.st + s));
   if (st->init_stage == 1) { vslam_set_error("%s: the stream's trails are running (the trail tracker reads the previous frame in place)", who); return VSLAM_E_STATE; }
   if (sys->tp.ba_delay > 0 && st->ba_countdown > 0) { vslam_set_error("%s: an adjustment of the stream is pending (due in %d frames)", who, st->ba_countdown); return VSLAM_E_STATE; }
   const int P = sys->p.max_points, K = sys->p.max_keyframes;
@@ -185,7 +184,7 @@ static int snap_source(vslam_system* sys, int s, const char* who, TrackerState* 
   bool sbi = sys->p.use_sbi && sys->have_sbi;
   if (sbi && sys->sbi_restart_pending) {        // reset since its last frame: its next frame is its first, there is nothing to carry
     unsigned char f = 0;
-    HIPCHK(hipMemcpy(&f, sys->sbi_restart + s, 1, hipMemcpyDeviceToHost));
+    VCHK(host_get(sys->stream, &f, sys->sbi_restart + s));
     sbi = !f;
   }
   c->width = sys->p.width; c->height = sys->p.height;
@@ -246,7 +245,7 @@ extern "C" int vslam_restore_stream(vslam_system* sys, int s, const void* blob, 
   struct Head { SnapHeader h; TrackerState st; } head;
   static_assert(offsetof(Head, st) == sizeof(SnapHeader), "the state section follows the header");
   if (bytes < sizeof(head)) return snap_invalid("restore_stream", SNAP_E_SHORT);
-  if (on_device) HIPCHK(hipMemcpy(&head, blob, sizeof(head), hipMemcpyDeviceToHost));
+  if (on_device) VCHK(host_get(sys->stream, &head, (const Head*)blob));
   else memcpy(&head, blob, sizeof(head));
   SnapHeader h;
   { const int e = snap_validate(&head.h, bytes, &h); if (e) return snap_invalid("restore_stream", e); }

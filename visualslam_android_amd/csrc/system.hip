@@ -142,8 +142,7 @@ static int sys_acquire(vslam_system* sys) {
   VCHK(reloc_alloc(sys));
   VCHK(reset_alloc(sys));
   VCHK(snapshot_alloc(sys));
-  HIPCHK(hipStreamSynchronize(q));
-  VCHK(map_init_states(sys));
+  VCHK(map_init_states(sys));            // (on q, behind the zeroing of the states)
   HIPCHK(hipStreamSynchronize(q));       // the zeroing contract (DevOwner::alloc): from here on the memory is zero for every stream
   return VSLAM_OK;
 }
@@ -226,8 +225,7 @@ static int check_sl(vslam_system* sys, int stream, int level) {
 
 static int check_overflow(vslam_system* sys) {
   int ov = 0;
-  HIPCHK(hipMemcpyAsync(&ov, sys->fr.overflow, sizeof(int), hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
+  VCHK(host_get(sys->stream, &ov, sys->fr.overflow));
   if (ov) { vslam_set_error("corner capacity exceeded (raise vslam_params.max_corners)"); return VSLAM_E_CAPACITY; }
   return VSLAM_OK;
 }
@@ -235,46 +233,33 @@ static int check_overflow(vslam_system* sys) {
 extern "C" int vslam_read_level_image(vslam_system* sys, int stream, int level, uint8_t* dst, size_t dst_stride) {
   int r = check_sl(sys, stream, level); if (r) return r;
   const LevelGeom& g = sys->geom[level];
-  HIPCHK(hipMemcpy2DAsync(dst, dst_stride, sys->fr.img[level] + (size_t)stream * sys->fr.img_sstride[level],
-                          sys->fr.img_pitch[level], g.w, g.h, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  return VSLAM_OK;
+  HostCopy c(sys->stream);
+  VCHK(c.get2d(dst, dst_stride, sys->fr.img[level] + (size_t)stream * sys->fr.img_sstride[level], sys->fr.img_pitch[level], g.w, g.h));
+  return c.wait();
 }
 
 extern "C" int vslam_read_corners(vslam_system* sys, int stream, int level, uint32_t* corners, int cap, int* n) {
   int r = check_sl(sys, stream, level); if (r) return r;
   r = check_overflow(sys); if (r) return r;
-  int cnt = 0;
-  HIPCHK(hipMemcpyAsync(&cnt, sys->fr.ncorners + stream * NLEV + level, sizeof(int), hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  if (n) *n = cnt;
-  const int m = cnt < cap ? cnt : cap;
-  if (corners && m > 0) {
-    HIPCHK(hipMemcpyAsync(corners, sys->fr.corners[level] + (size_t)stream * sys->geom[level].cap, (size_t)m * 4,
-                          hipMemcpyDeviceToHost, sys->stream));
-    HIPCHK(hipStreamSynchronize(sys->stream));
-  }
-  return VSLAM_OK;
+  return HostCopy(sys->stream).counted(sys->fr.ncorners + stream * NLEV + level, n, corners, sys->fr.corners[level] + (size_t)stream * sys->geom[level].cap, cap);
 }
 
 extern "C" int vslam_read_row_lut(vslam_system* sys, int stream, int level, int* lut) {
   int r = check_sl(sys, stream, level); if (r) return r;
   const int h = sys->geom[level].h;
-  HIPCHK(hipMemcpyAsync(lut, sys->fr.rowlut[level] + (size_t)stream * (h + 1), (size_t)h * 4, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  return VSLAM_OK;
+  return host_get(sys->stream, lut, sys->fr.rowlut[level] + (size_t)stream * (h + 1), h);
 }
 
 extern "C" int vslam_read_sbi(vslam_system* sys, int stream, uint8_t* small_img, float* tmpl, double rot8[8]) {
   if (!sys || stream < 0 || stream >= sys->S) { vslam_set_error("bad stream/level"); return VSLAM_E_INVALID; }
   if (!sys->have_frame) { vslam_set_error("no current frame"); return VSLAM_E_STATE; }   // (a held stream's products are carried: no check_sl)
   if (!sys->p.use_sbi || !sys->have_sbi) { vslam_set_error("read_sbi: use_sbi is off or no frame yet"); return VSLAM_E_STATE; }
-  HIPCHK(hipStreamSynchronize(sys->fe_stream));
   const size_t ns = (size_t)(sys->geom[3].w / 2) * (sys->geom[3].h / 2);
-  if (small_img) HIPCHK(hipMemcpy(small_img, sys->fr.sbi_small + stream * ns, ns, hipMemcpyDeviceToHost));
-  if (tmpl) HIPCHK(hipMemcpy(tmpl, sys->fr.sbi_tmpl + stream * ns, ns * sizeof(float), hipMemcpyDeviceToHost));
-  if (rot8) HIPCHK(hipMemcpy(rot8, sys->fr.sbi_rot + (size_t)stream * 8, 8 * sizeof(double), hipMemcpyDeviceToHost));
-  return VSLAM_OK;
+  HostCopy c(sys->fe_stream);                  // the SmallBlurryImage is the front-end stream's product
+  if (small_img) VCHK(c.get(small_img, sys->fr.sbi_small + stream * ns, ns));
+  if (tmpl) VCHK(c.get(tmpl, sys->fr.sbi_tmpl + stream * ns, ns));
+  if (rot8) VCHK(c.get(rot8, sys->fr.sbi_rot + (size_t)stream * 8, 8));
+  return c.wait();
 }
 
 extern "C" int vslam_make_keyframe_rest(vslam_system* sys, double min_shi_tomasi_score) {
@@ -291,32 +276,26 @@ extern "C" int vslam_read_candidates(vslam_system* sys, int stream, int level, u
   int r = check_sl(sys, stream, level); if (r) return r;
   if (!sys->have_candidates) { vslam_set_error("read_candidates: call vslam_make_keyframe_rest first"); return VSLAM_E_STATE; }
   int cnt = 0;
-  HIPCHK(hipMemcpyAsync(&cnt, sys->ncand + stream * NLEV + level, sizeof(int), hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
+  HostCopy c(sys->stream);
+  VCHK(c.get(&cnt, sys->ncand + stream * NLEV + level)); VCHK(c.wait());
   if (n) *n = cnt;
   const size_t off = (size_t)stream * sys->geom[level].cap;
-  const size_t m = (size_t)(cnt < cap ? cnt : cap);
-  if (pos && m) HIPCHK(hipMemcpyAsync(pos, sys->cand[level] + off, m * 4, hipMemcpyDeviceToHost, sys->stream));
-  if (score && m) HIPCHK(hipMemcpyAsync(score, sys->cand_score[level] + off, m * 8, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  return VSLAM_OK;
+  VCHK(c.take(pos, sys->cand[level] + off, cnt, cap));
+  VCHK(c.take(score, sys->cand_score[level] + off, cnt, cap));
+  return c.wait();
 }
 
 extern "C" int vslam_read_max_corners(vslam_system* sys, int stream, int level, uint32_t* corners, int* scores, int cap,
                                       int* n) {
   int r = check_sl(sys, stream, level); if (r) return r;
   int cnt = 0, nc = 0;
-  HIPCHK(hipMemcpyAsync(&cnt, sys->fr.nmax + stream * NLEV + level, sizeof(int), hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipMemcpyAsync(&nc, sys->fr.ncorners + stream * NLEV + level, sizeof(int), hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
+  HostCopy c(sys->stream);
+  VCHK(c.get(&cnt, sys->fr.nmax + stream * NLEV + level)); VCHK(c.get(&nc, sys->fr.ncorners + stream * NLEV + level)); VCHK(c.wait());
   if (n) *n = cnt;
   const size_t off = (size_t)stream * sys->geom[level].cap;
-  if (corners && cnt > 0)
-    HIPCHK(hipMemcpyAsync(corners, sys->fr.maxcorners[level] + off, (size_t)(cnt < cap ? cnt : cap) * 4, hipMemcpyDeviceToHost, sys->stream));
-  if (scores && nc > 0)  // scores of ALL corners of the level (same order as vslam_read_corners)
-    HIPCHK(hipMemcpyAsync(scores, sys->fr.scores[level] + off, (size_t)(nc < cap ? nc : cap) * 4, hipMemcpyDeviceToHost, sys->stream));
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  return VSLAM_OK;
+  VCHK(c.take(corners, sys->fr.maxcorners[level] + off, cnt, cap));
+  VCHK(c.take(scores, sys->fr.scores[level] + off, nc, cap));   // scores of ALL corners of the level (same order as vslam_read_corners)
+  return c.wait();
 }
 
 // ---- self-test hook: the transcendentals of vslam_libm.h evaluated on the device ---------------------------------------

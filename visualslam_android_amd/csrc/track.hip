@@ -1413,13 +1413,12 @@ extern "C" int vslam_set_pvs_seed(vslam_system* sys, int stream, unsigned seed) 
 extern "C" int vslam_get_search_plan(vslam_system* sys, int stream, int* iter_idx, int cap, int counts[4]) {
   if (!sys || stream < 0 || stream >= sys->S || cap < 0 || (cap > 0 && !iter_idx)) { vslam_set_error("get_search_plan: bad argument"); return VSLAM_E_INVALID; }
   TrackerState st;
-  HIPCHK(hipStreamSynchronize(sys->stream));
-  HIPCHK(hipMemcpy(&st, sys->map.st + stream, sizeof(st), hipMemcpyDeviceToHost));
+  HostCopy c(sys->stream);
+  VCHK(c.get(&st, sys->map.st + stream)); VCHK(c.wait());
   int n = st.n_iter < 0 ? 0 : st.n_iter;
   if (n > sys->p.max_points) n = sys->p.max_points;
   if (counts) { counts[0] = st.n_coarse; counts[1] = st.n_l3; counts[2] = n - st.n_coarse - st.n_l3; counts[3] = n; }
-  const int ncopy = n < cap ? n : cap;
-  if (ncopy > 0) HIPCHK(hipMemcpy(iter_idx, sys->map.iter_list + (size_t)stream * sys->p.max_points, sizeof(int) * (size_t)ncopy, hipMemcpyDeviceToHost));
+  VCHK(c.take(iter_idx, sys->map.iter_list + (size_t)stream * sys->p.max_points, n, cap)); VCHK(c.wait());
   return n;
 }
 

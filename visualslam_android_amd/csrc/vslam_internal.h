@@ -273,6 +273,52 @@ template <class T> struct DevTemp {
   hipError_t get(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)); }
 };
 
+// Host copies: every synchronous copy between the host and a handle's memory.  A handle's streams are
+// non-blocking, so a copy is ordered only by the stream it is enqueued on: each goes onto the stream named here, never the null stream,
+// and the wait belongs to the batch -- wait() reports it, and a batch that ends without one (an error return) waits as it goes out of
+// scope (so it is declared behind the host arrays it copies).  After the wait every get() has landed and every put()'s source may be
+// reused.  Kernels may be launched on q in between.
+struct HostCopy {
+  hipStream_t q;
+  bool pending = false;        // something has been enqueued since the last wait
+  explicit HostCopy(hipStream_t stream) : q(stream) {}
+  HostCopy(const HostCopy&) = delete;
+  ~HostCopy() { if (pending) (void)hipStreamSynchronize(q); }
+  int copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (bytes) { pending = true; HIPCHK(hipMemcpyAsync(dst, src, bytes, kind, q)); }
+    return VSLAM_OK;
+  }
+  template <class T> int get(T* host, const T* dev, size_t n = 1) { return copy(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost); }
+  template <class T> int put(T* dev, const T* host, size_t n = 1) { return copy(dev, host, sizeof(T) * n, hipMemcpyHostToDevice); }
+  template <class T> int get(std::vector<T>& host, const T* dev, int n) { host.resize(n > 0 ? n : 0); return get(host.data(), dev, host.size()); }
+  // rows of `width` bytes, the pitches in bytes
+  int copy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipMemcpyKind kind) {
+    if (width && rows) { pending = true; HIPCHK(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, kind, q)); }
+    return VSLAM_OK;
+  }
+  int get2d(void* host, size_t hpitch, const void* dev, size_t dpitch, size_t width, size_t rows) { return copy2d(host, hpitch, dev, dpitch, width, rows, hipMemcpyDeviceToHost); }
+  int put2d(void* dev, size_t dpitch, const void* host, size_t hpitch, size_t width, size_t rows) { return copy2d(dev, dpitch, host, hpitch, width, rows, hipMemcpyHostToDevice); }
+  int wait() {
+    if (pending) { pending = false; HIPCHK(hipStreamSynchronize(q)); }
+    return VSLAM_OK;
+  }
+  // The counted read-back: a count that has landed, clamped to the caller's capacity, and that many elements (of `per` Ts each) behind it
+  template <class T> int take(T* host, const T* dev, int count, int cap, size_t per = 1) {
+    const int m = count < cap ? count : cap;
+    return host && m > 0 ? get(host, dev, (size_t)m * per) : VSLAM_OK;
+  }
+  // ... the whole sequence for one array: the device's count into *count (either may be null), then the elements
+  template <class T> int counted(const int* d_count, int* count, T* host, const T* dev, int cap, size_t per = 1) {
+    int cnt = 0;
+    VCHK(get(&cnt, d_count)); VCHK(wait());
+    if (count) *count = cnt;
+    VCHK(take(host, dev, cnt, cap, per)); return wait();
+  }
+};
+// a batch of one
+template <class T> static inline int host_get(hipStream_t q, T* host, const T* dev, size_t n = 1) { HostCopy c(q); VCHK(c.get(host, dev, n)); return c.wait(); }
+template <class T> static inline int host_put(hipStream_t q, T* dev, const T* host, size_t n = 1) { HostCopy c(q); VCHK(c.put(dev, host, n)); return c.wait(); }
+
 struct BaSystemWs;             // bundle-adjustment workspace (ba.hip)
 
 struct vslam_system {
