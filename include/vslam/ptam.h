@@ -108,6 +108,9 @@ class MapMaker {
   void RequestReset() { if (mMap.sys) vslam_detail::check(vslam_reset_streams(mMap.sys, nullptr, 0)); }   // :127-131 -> Reset :60-74, Map::Reset
   bool ResetDone() { return true; }                                                                    // :133-136: the reset is ordered on the system's stream, nothing to spin for
   int QueueSize() { return 0; }
+  // not in the reference (its map grows on the heap): one keyframe leaves the map, with the points it is the patch source of and every bad
+  // point (vslam_retire_keyframes); nKeyFrame < 0: the keyframe farthest from the tracker's pose
+  void RetireKeyFrame(int nKeyFrame = -1) { const int s = 0; vslam_detail::check(vslam_retire_keyframes(mMap.sys, &s, &nKeyFrame, 1)); }
   bool NeedNewKeyFrame(KeyFrame&) { int v = 0; vslam_detail::check(vslam_need_new_keyframe(mMap.sys, 0, &v)); return v != 0; }              // :761-773 (the tracker's current frame)
   bool IsDistanceToNearestKeyFrameExcessive(KeyFrame&) { int v = 0; vslam_detail::check(vslam_distance_to_nearest_keyframe_excessive(mMap.sys, 0, &v)); return v != 0; }   // :1098-1101
   // :204-376, the reference's signature (ImageRef = a pair of ints): the two keyframes' images (KeyFrame::im0, kept by MakeKeyFrame_Lite)
@@ -180,11 +183,13 @@ class Tracker {
   // map-maker grows it on every keyframe (AddKeyFrameFromTopOfQueue, jni/MapMaker.cc:481-506)
   // nPVSShuffleSeed: TrackMap's random_shuffle of the potentially visible set (jni/Tracker.cc:396-397, 525) as the seeded permutation of
   // vslam_params.pvs_shuffle_seed; 0 keeps map order
-  Tracker(int width, int heigth, const ATANCamera& c, Map& m, MapMaker& mm, bool bBootstrap = false, unsigned nPVSShuffleSeed = 0) : mMap(m), mMapMaker(mm) {   // jni/Tracker.cc:16-40
+  // bRetireKeyFrames: vslam_params.keyframe_retire, a full map gives up its farthest keyframe for the next one
+  Tracker(int width, int heigth, const ATANCamera& c, Map& m, MapMaker& mm, bool bBootstrap = false, unsigned nPVSShuffleSeed = 0, bool bRetireKeyFrames = false) : mMap(m), mMapMaker(mm) {   // jni/Tracker.cc:16-40
     vslam_params p;
     vslam_detail::check(vslam_default_params(&p, width, heigth, 1));
     if (bBootstrap) { p.bootstrap = 1; p.grow_map = 3; }
     p.pvs_shuffle_seed = nPVSShuffleSeed;
+    p.keyframe_retire = bRetireKeyFrames ? 1 : 0;
     for (int i = 0; i < 5; i++) p.cam[i] = c.params[i];
     vslam_detail::check(vslam_create(&p, &mMap.sys));
     mCurrentKF.sys = mMap.sys;

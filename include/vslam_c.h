@@ -111,6 +111,12 @@ typedef struct vslam_params {
                                       here the order is the seeded permutation of csrc/pvs_perm.h, a function of (seed, frame, list, length).
                                       0 (default): the identity order, map order.  Non-zero: every stream starts with this seed
                                       (vslam_set_pvs_seed changes one stream's) */
+  int keyframe_retire;             /* What a stream does whose map holds max_keyframes keyframes when its tracker wants another one (NeedNewKeyFrame,
+                                      jni/MapMaker.cc:761-773).  0 (default): nothing, the map stops growing (the reference's map has no limit,
+                                      jni/Map.h:21-34).  1: it asks for the keyframe after all, and vslam_finish_frame / vslam_add_keyframe first
+                                      retire one keyframe by policy (vslam_retire_keyframes below) into whose place the others move, so the new
+                                      keyframe takes the last slot.  While an adjustment of the asynchronous map-maker is pending for the stream the
+                                      request waits for a later frame.  No host synchronisation.  Needs max_keyframes >= 3 */
 } vslam_params;
 
 const char* vslam_last_error(void);
@@ -259,6 +265,31 @@ int vslam_get_reset_info(vslam_system* sys, int stream, int out[4]);
 /* HIP-event milliseconds of the last vslam_reset_streams on the system's stream: the flag copy, the wait for the map-maker streams
  * (asynchronous map-maker) and the reset kernels.  Synchronises.  VSLAM_E_STATE before the first call. */
 int vslam_get_reset_timing(vslam_system* sys, double* ms);
+
+/* ---- keyframe retirement ---------------------------------------------------------------------
+ * One keyframe of each listed stream leaves its map, on the device and in place.  The reference has no such operation (its Map grows on
+ * the heap, jni/Map.h:21-34, and nothing leaves vpKeyFrames): like max_points this is the build's own, for a stream that runs
+ * indefinitely in bounded memory.  With keyframe r of stream streams[i] (keyframes[i]; < 0: by policy, the keyframe whose camera centre
+ * is farthest from the stream's current pose, KeyFrameLinearDist jni/MapMaker.cc:705-712, lowest index on ties):
+ *   - keyframe r leaves; the later keyframes move down one and keep their order of creation (the newest is still n_keyframes - 1);
+ *   - the map points whose patch source it was (MapPoint::pPatchSourceKF, jni/MapPoint.h:36) leave with it, and so does every bad point;
+ *     the survivors keep their relative order and are renumbered, in every per-point array, measurement row, never-retry set, the
+ *     failure queue and the last frame's iteration set; pPatchSourceKF and the measurement-keyframe count of a survivor follow;
+ *   - if r was the map's only fixed keyframe the oldest survivor becomes fixed (BundleAdjustAll keeps its gauge, jni/MapMaker.cc:776-798);
+ *   - Relocaliser::mnBest (jni/Relocaliser.h) follows, -1 if it was r.
+ * Between frames, on any system whatever its keyframe_retire.  Stream indices must be distinct.  The call waits once for the device to
+ * read the listed streams' states; everything is decided before anything changes, and a refused call changes nothing for any stream.
+ * VSLAM_E_INVALID: NULL system, n < 0, an index outside the batch, a duplicate stream, keyframes[i] >= the stream's keyframes.
+ * VSLAM_E_STATE: a stage-wise frame is open; a listed stream has no good map, fewer than 3 keyframes (a map keeps at least two), its
+ * trails running, or an adjustment of the asynchronous map-maker pending.  All listed streams go in one set of three launches. */
+int vslam_retire_keyframes(vslam_system* sys, const int* streams, const int* keyframes, int n);
+/* out[0..5] = retirements of the stream so far (explicit and automatic); of the last one: the index the keyframe had before it left, the
+ * points dropped because it was their source, the bad points reclaimed, the failure-queue entries dropped, and mnFrame
+ * (jni/Tracker.h:116) at that time.  vslam_reset_streams and vslam_restore_stream zero the record. */
+int vslam_get_retire_info(vslam_system* sys, int stream, int out[6]);
+/* HIP-event milliseconds of the last vslam_retire_keyframes that retired, its three launches on the system's stream.  Waits for them.
+ * VSLAM_E_STATE before the first such call. */
+int vslam_get_retire_timing(vslam_system* sys, double* ms);
 
 /* ---- stream snapshots ------------------------------------------------------------------------
  * One stream taken out of a live batch whole, and put back bit for bit into any slot of any compatible system.  The reference's only

@@ -33,7 +33,7 @@ class Params(C.Structure):
         ("ba_min_tukey_sigma", C.c_double), ("ba_window", C.c_int), ("ba_min_keyframes", C.c_int),
         ("cam", C.c_double * 5), ("quirks", C.c_int), ("device", C.c_int), ("ba_delay_frames", C.c_int),
         ("grow_map", C.c_int), ("ba_batch_frames", C.c_int), ("idle_iterations", C.c_int), ("bootstrap", C.c_int), ("ba_sum_order", C.c_int),
-        ("relocalise", C.c_int), ("reloc_blur", C.c_double), ("pvs_shuffle_seed", C.c_uint),
+        ("relocalise", C.c_int), ("reloc_blur", C.c_double), ("pvs_shuffle_seed", C.c_uint), ("keyframe_retire", C.c_int),
     ]
 
 
@@ -119,6 +119,9 @@ SYMBOLS = {
     "vslam_reset_streams": (_i, [_sys, _vp, _i]),
     "vslam_get_reset_info": (_i, [_sys, _i, _vp]),
     "vslam_get_reset_timing": (_i, [_sys, C.POINTER(_d)]),
+    "vslam_retire_keyframes": (_i, [_sys, _vp, _vp, _i]),
+    "vslam_get_retire_info": (_i, [_sys, _i, _vp]),
+    "vslam_get_retire_timing": (_i, [_sys, C.POINTER(_d)]),
     "vslam_snapshot_size": (_i, [_sys, _i, C.POINTER(_sz)]),
     "vslam_snapshot_stream": (_i, [_sys, _i, _vp, _sz, _i, C.POINTER(_sz)]),
     "vslam_restore_stream": (_i, [_sys, _i, _vp, _sz, _i]),
@@ -502,6 +505,25 @@ class System:
         """-> HIP-event ms of the last reset on the system's stream (vslam_get_reset_timing)"""
         ms = C.c_double(0.0)
         _check(self.lib.vslam_get_reset_timing(self.h, C.byref(ms)))
+        return ms.value
+
+    def retire_keyframes(self, streams, keyframes=None):
+        """One keyframe of each listed stream leaves its map (vslam_retire_keyframes); keyframes[i] < 0, or keyframes=None: by policy,
+        the keyframe farthest from the stream's pose"""
+        a = np.ascontiguousarray(np.atleast_1d(streams), np.int32)
+        k = np.full(len(a), -1, np.int32) if keyframes is None else np.ascontiguousarray(np.atleast_1d(keyframes), np.int32)
+        assert len(k) == len(a)
+        _check(self.lib.vslam_retire_keyframes(self.h, a.ctypes.data, k.ctypes.data, len(a)))
+
+    def retire_info(self, stream):
+        o = np.zeros(6, np.int32)
+        _check(self.lib.vslam_get_retire_info(self.h, stream, o.ctypes.data))
+        return dict(zip(("retired", "keyframe", "points_sourced", "points_bad", "queue_dropped", "frame"), (int(x) for x in o)))
+
+    def retire_timing(self):
+        """-> HIP-event ms of the last retire_keyframes on the system's stream (vslam_get_retire_timing)"""
+        ms = C.c_double(0.0)
+        _check(self.lib.vslam_get_retire_timing(self.h, C.byref(ms)))
         return ms.value
 
     # ---- stream snapshots --------------------------------------------------------------------

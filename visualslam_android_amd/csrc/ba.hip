@@ -435,12 +435,6 @@ __global__ __launch_bounds__(256) void k_add_keyframe(MapDev m, TrackParams tp, 
   }
 }
 
-DEVFN double kfdist(const Pose& a, const Pose& b) {   // KeyFrameLinearDist :705-712
-  const Pose ia = pose_inverse(a), ib = pose_inverse(b);
-  const double d0 = ib.t[0] - ia.t[0], d1 = ib.t[1] - ia.t[1], d2 = ib.t[2] - ia.t[2];
-  return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-}
-
 // The job (BaJob, vslam_internal.h) says which streams are adjusted and whether all their keyframes or the window around the
 // newest one.  Two kernels build the Bundle problem of BundleAdjust (:854-902) in the pool:
 // k_ba_select (one lane per stream, on the tracker's stream) takes the decisions that the next frame's tracking must see --
@@ -482,7 +476,7 @@ __global__ __launch_bounds__(64) void k_ba_select(MapDev m, TrackParams tp, BaPo
         int best = -1; double bd = 0;
         for (int k = 0; k < nk; k++) {
           if (k == newest || ((taken[k >> 6] >> (k & 63)) & 1ull)) continue;
-          const double d = kfdist(kfp[newest], kfp[k]);
+          const double d = kf_linear_dist(kfp[newest], kfp[k]);
           if (best < 0 || d < bd) { best = k; bd = d; }
         }
         if (best < 0) break;
@@ -932,6 +926,7 @@ int ba_run(vslam_system* sys, BaJob job, bool host_driven_keyframe) {
   if (ba_job_on_request(job)) { int r = ba_drain(sys); if (r) return r; }
   if (job == BaJob::Keyframe) {
     prof_mark(sys, PROF_ADD_KEYFRAME);
+    { int r = retire_on_keyframe(sys); if (r) return r; }               // keyframe_retire: a full stream gives up a keyframe first
     { int r = ba_add_keyframe_prologue(sys, true); if (r) return r; }
     prof_mark(sys, PROF_BA_ASSEMBLE);
     if (sys->tp.ba_delay > 0 && !host_driven_keyframe) return ba_adjust_keyframe_async(sys, token);
@@ -1032,7 +1027,7 @@ __global__ void k_request_keyframe(MapDev m, TrackParams tp, int S, int stream) 
   if (s >= S) return;
   TrackerState* st = &m.st[s];
   if (!trk_in_step(m.held, s)) return;
-  const bool want = (stream < 0 || s == stream) && st->map_good && st->n_kf < tp.max_keyframes;
+  const bool want = (stream < 0 || s == stream) && st->map_good && (st->n_kf < tp.max_keyframes || tp.keyframe_retire);   // full: k_retire_plan frees a slot (the caller has drained)
   st->kf_pending = want ? 1 : 0;                      // a request left over from the last frame has been served already
   if (want) st->last_kf_dropped = st->frame;          // Tracker::AddNewKeyFrame, jni/Tracker.cc:823-827
 }

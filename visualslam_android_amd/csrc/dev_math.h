@@ -46,6 +46,13 @@ HDFN Pose pose_inverse(const Pose& a) {                                 // jni/R
   return r;
 }
 
+// KeyFrameLinearDist, jni/MapMaker.cc:705-712: the distance between the camera centres of two poses
+HDFN double kf_linear_dist(const Pose& a, const Pose& b) {
+  const Pose ia = pose_inverse(a), ib = pose_inverse(b);
+  const double d0 = ib.t[0] - ia.t[0], d1 = ib.t[1] - ia.t[1], d2 = ib.t[2] - ia.t[2];
+  return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
+}
+
 HDFN void rodrigues(const double w[3], double A, double B, double R[9]) {   // jni/RT.h:98-129
   const double wx2 = w[0] * w[0], wy2 = w[1] * w[1], wz2 = w[2] * w[2];
   R[0] = 1.0 - B * (wy2 + wz2); R[4] = 1.0 - B * (wx2 + wz2); R[8] = 1.0 - B * (wx2 + wy2);

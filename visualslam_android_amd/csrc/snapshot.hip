@@ -12,7 +12,7 @@
 //   remade    keyframe corner lists (fe_keyframe_corners) and keyframe SmallBlurryImages (reloc_keyframe_sbi), from the restored pyramids
 //             through the map upload's own path: FAST and the SmallBlurryImage are pure functions of the stored images, the read-backs come
 //             out equal, and a blob of a system without grow_map / relocalise restores into one with it
-//   not       the frame's front-end products, reset_info, profile and timing records, the bundle-adjustment pool record (every
+//   not       the frame's front-end products, reset_info, retire_info, profile and timing records, the bundle-adjustment pool record (every
 //             adjustment rewrites it from the map before it reads it: k_ba_select, k_ba_assemble)
 //
 // One kernel moves the bytes in both directions, driven by a table of copies passed by value: a section of the blob is `rows` dense

@@ -54,6 +54,7 @@ extern "C" int vslam_default_params(vslam_params* p, int width, int height, int 
   p->relocalise = 0;
   p->reloc_blur = 2.5;                                  // jni/SmallBlurryImage.h:19-20
   p->pvs_shuffle_seed = 0;                              // identity order (jni/Tracker.cc:396-397, 525 shuffle with rand())
+  p->keyframe_retire = 0;                               // a full map stops making keyframes
   return VSLAM_OK;
 }
 
@@ -142,6 +143,7 @@ static int sys_acquire(vslam_system* sys) {
   VCHK(reloc_alloc(sys));
   VCHK(reset_alloc(sys));
   VCHK(snapshot_alloc(sys));
+  if (p->keyframe_retire) VCHK(retire_alloc(sys));
   VCHK(map_init_states(sys));            // (on q, behind the zeroing of the states)
   HIPCHK(hipStreamSynchronize(q));       // the zeroing contract (DevOwner::alloc): from here on the memory is zero for every stream
   return VSLAM_OK;
@@ -162,6 +164,7 @@ extern "C" int vslam_create(const vslam_params* p, vslam_system** out) {
     vslam_set_error("create: bootstrap needs grow_map != 0 (keyframe corner lists for InitFromStereo's AddSomeMapPoints) and ba_delay_frames = 0, got grow_map %d, ba_delay_frames %d", p->grow_map, p->ba_delay_frames);
     return VSLAM_E_INVALID;
   }
+  if (p->keyframe_retire && p->max_keyframes < 3) { vslam_set_error("create: keyframe_retire needs max_keyframes >= 3 (a map keeps at least two), got %d", p->max_keyframes); return VSLAM_E_INVALID; }
   if (p->relocalise && !(p->reloc_blur > 0.0)) { vslam_set_error("create: relocalise needs reloc_blur > 0, got %g", p->reloc_blur); return VSLAM_E_INVALID; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {

@@ -996,13 +996,6 @@ DEVFN void calc_pose_update(const PoseWs& ws, MapPointDev* pts, int nf, const Tr
   __syncthreads();
 }
 
-// KeyFrameLinearDist, jni/MapMaker.cc:705-712
-DEVFN double kf_linear_dist(const Pose& a, const Pose& b) {
-  const Pose ia = pose_inverse(a), ib = pose_inverse(b);
-  const double d0 = ib.t[0] - ia.t[0], d1 = ib.t[1] - ia.t[1], d2 = ib.t[2] - ia.t[2];
-  return sqrt(d0 * d0 + d1 * d1 + d2 * d2);
-}
-
 // stage 0: coarse GN iterations (:463-490); stage 1: fine GN iterations + end of TrackMap/TrackFrame.
 #ifndef VSLAM_POSE_WAVES
 #define VSLAM_POSE_WAVES 2
@@ -1227,7 +1220,8 @@ __global__ __launch_bounds__(POSE_THREADS) __attribute__((amdgpu_waves_per_eu(VS
     double dDist = closest;
     dDist *= (1.0 / st->depth_mean);
     const bool need = dDist > tp.max_kf_dist_wiggle_mult * st->wiggle_depth_norm;
-    if (st->quality == 2 && need && st->frame - st->last_kf_dropped > tp.min_frames_between_kf && st->n_kf < tp.max_keyframes) {
+    if (st->quality == 2 && need && st->frame - st->last_kf_dropped > tp.min_frames_between_kf &&
+        (st->n_kf < tp.max_keyframes || (tp.keyframe_retire && st->ba_countdown <= 0))) {   // a full map: k_retire_plan frees a slot first (retire.hip)
       st->kf_pending = 1;
       st->last_kf_dropped = st->frame;
     }
@@ -1306,6 +1300,7 @@ void trk_fill_params(const vslam_params& p, TrackParams& t) {
   t.ba_sum_order = p.ba_sum_order ? 1 : 0;
   t.grow_map = p.grow_map;
   t.idle = p.idle_iterations != 0; t.fq_cap = 8192;
+  t.keyframe_retire = p.keyframe_retire ? 1 : 0;
   {                                                                  // ATANCamera::OnePixelDist, jni/ATANCamera.cc:86-91
     double a[2], b[2];
     cam_unproject(t.cam, t.cam.size[0] / 2, t.cam.size[1] / 2, a);

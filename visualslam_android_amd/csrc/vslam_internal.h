@@ -168,6 +168,7 @@ struct TrackParams {        // device copy of the tunables the kernels read
   int fq_cap;               // capacity of a stream's failure queue
   double one_pixel_dist;    // ATANCamera::OnePixelDist, jni/ATANCamera.cc:86-91
   int kcap[NLEV];           // capacity of a keyframe's stored corner list per level (grow_map)
+  int keyframe_retire;      // vslam_params.keyframe_retire: a full stream asks for its keyframe after all, retire.hip frees the slot
 };
 
 struct MapDev {             // device pointers of the map + tracker of all streams
@@ -378,6 +379,14 @@ struct vslam_system {
   hipEvent_t ev_reset_t[2] = {nullptr, nullptr};   // around the last call's work on the system's stream (vslam_get_reset_timing)
   hipEvent_t ev_reset = nullptr;             // the reset kernels are done (the front-end and map-maker streams wait for it)
   std::vector<hipEvent_t> ev_reset_ba;       // one per map-maker stream: what it held when the reset was called
+  // keyframe retirement (retire.hip): allocated with keyframe_retire != 0 or by the first vslam_retire_keyframes, else null
+  int* retire_remap = nullptr;               // [S][max_points] device: new index of a surviving point, -1 of a dropped one
+  int* retire_plan = nullptr;                // [S][RETIRE_PLAN_N] device: what k_retire_plan decided, for the kernels that move
+  int* retire_req = nullptr;                 // [S] device: the explicit call's request per stream
+  int* retire_info = nullptr;                // [S][6] device: vslam_get_retire_info
+  int* retire_req_stage = nullptr;           // [S] pinned host copy of the request
+  hipEvent_t ev_retire_t[2] = {nullptr, nullptr};   // around the last explicit call's launches (vslam_get_retire_timing)
+  long retire_calls = 0;
   // vslam_snapshot_stream / vslam_restore_stream (snapshot.hip)
   hipEvent_t ev_snap_t[4] = {nullptr, nullptr, nullptr, nullptr};   // around the last pack [0, 1] and the last unpack [2, 3] on the system's stream
   bool snap_timed[2] = {false, false};       // a pack / an unpack has run
@@ -500,4 +509,7 @@ int map_init_states(vslam_system* sys);
 int reset_alloc(vslam_system* sys);
 // snapshot.hip
 int snapshot_alloc(vslam_system* sys);
+// retire.hip
+int retire_alloc(vslam_system* sys);          // the scratch of keyframe retirement, if the system does not hold it yet
+int retire_on_keyframe(vslam_system* sys);    // keyframe_retire: one keyframe by policy for the full streams with kf_pending, before k_add_keyframe
 
