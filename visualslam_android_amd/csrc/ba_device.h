@@ -166,6 +166,27 @@ DEVFN int ba_block_sum_i(int v, int* red) {
   return t;
 }
 
+// The commit of an accepted trial (jni/Bundle.cc:503-514): nc poses (12 doubles each, nc <= BA_COMMIT_CAMS) and np points
+// (3 doubles each) copied by the whole workgroup.  Source and destination cannot be proven distinct, so a plain element loop is
+// one load -> store round trip per iteration; here the loads of a lane are issued together before its stores: every pose word
+// and the first eight point words in one round trip, then eight point words per trip.  (Out of line like the other phases:
+// inlined into ba_lm its fourteen live doubles cost both kernels 80 B of scratch per lane.)
+#define BA_COMMIT_CAMS 128   // = the cameras a problem can hold
+BA_PHASE_FN void ba_commit_copy(const BaView& v, int nc, int np) {
+  double AS1* cam_dst = (double AS1*)ba_uniform_ptr(v.cam_pose); const double AS1* cam_src = (const double AS1*)ba_uniform_ptr(v.cam_new);
+  double AS1* pt_dst = ba_uniform_ptr(v.pt_pos); const double AS1* pt_src = ba_uniform_ptr(v.pt_new);
+  constexpr int CC = (12 * BA_COMMIT_CAMS + BA_THREADS - 1) / BA_THREADS, CB = 8;
+  const int ncw = 12 * nc, npw = 3 * np;
+  double cx[CC];
+  _Pragma("unroll") for (int u = 0; u < CC; u++) { const int t = threadIdx.x + u * BA_THREADS; cx[u] = t < ncw ? cam_src[t] : 0.0; }
+  for (int t0 = threadIdx.x; t0 < npw; t0 += CB * BA_THREADS) {
+    double x[CB];
+    _Pragma("unroll") for (int u = 0; u < CB; u++) { const int t = t0 + u * BA_THREADS; x[u] = t < npw ? pt_src[t] : 0.0; }
+    _Pragma("unroll") for (int u = 0; u < CB; u++) { const int t = t0 + u * BA_THREADS; if (t < npw) pt_dst[t] = x[u]; }
+  }
+  _Pragma("unroll") for (int u = 0; u < CC; u++) { const int t = threadIdx.x + u * BA_THREADS; if (t < ncw) cam_dst[t] = cx[u]; }
+}
+
 // Slot accessors: component k of slot i of a measurement-indexed fp64 array (component-major, see MS()).
 #define SL(arr, k, i) v.arr[(size_t)(k) * v.max_meas + (i)]
 #define SL_CAM(info) ((info) & 255)
@@ -571,12 +592,20 @@ BA_PHASE_FN BaNewError ba_find_new_error(const BaView& v_, const BaConfig& cfg_,
 // ---------------------------------------------------------------------------------------------------------------------
 #define BA_MFMA_FREE 5    // adjustable cameras of one pass of the matrix-core form of the reduced camera system
 #define BA_FAST_FREE 10   // adjustable cameras up to which U / epsilon_a are summed inside the sweep and the map update runs over the dense F slots
-#define BA_U_PAIRS ((BA_FAST_FREE * 27 + 63) / 64)
 #define BA_MAX_CAMS_LDS 128  // cameras whose poses the step sweep keeps in LDS (= the most keyframes a map holds)
+static_assert(BA_COMMIT_CAMS == BA_MAX_CAMS_LDS && sizeof(Pose) == 12 * sizeof(double), "ba_commit_copy: a problem's poses are 12 doubles each and fit one batch");
 #define BA_SWEEP_STAGE 27   // doubles per lane of a wavefront's staging area in the step sweep (V / epsilon_b use 9 of them)
-BA_PHASE_FN double ba_step_sweep(const BaView& v_, const BaConfig& cfg_, int region, double sigma2, int nfree,
-                                                        double* stg_ /* LDS [BA_WAVES][64][BA_SWEEP_STAGE] */, double* ured_ /* unused: a wavefront leaves its U / epsilon_a sums at the head of its own staging area, [camera][27] */,
+// REGION: 0 = F, 1 = X.  UFREE: the adjustable cameras whose U / epsilon_a the sweep sums (region F: BA_MFMA_FREE or BA_FAST_FREE,
+// whichever is the first to hold nfree; its ballot and consumer loops are unrolled to that), 0: none (region X; more than
+// BA_FAST_FREE cameras).
+template <int REGION, int UFREE>
+BA_PHASE_FN double ba_step_sweep(const BaView& v_, const BaConfig& cfg_, double sigma2, int nfree,
+                                                        double* stg_ /* LDS [BA_WAVES][64][BA_SWEEP_STAGE]; a wavefront leaves its U / epsilon_a sums at the head of its own staging area, [camera][27] */,
                                                         const double* cams_ /* LDS: the committed camera poses, 12 doubles each */) {
+  static_assert(REGION == 0 || UFREE == 0, "U / epsilon_a are sums over region F");
+  constexpr int region = REGION;
+  constexpr bool fastU = UFREE > 0;
+  constexpr int U_PAIRS = fastU ? (UFREE * 27 + 63) / 64 : 1;
   const BaViewG v = ba_g(v_);
   const BaConfig cfg = cfg_;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -585,10 +614,9 @@ BA_PHASE_FN double ba_step_sweep(const BaView& v_, const BaConfig& cfg_, int reg
   const int nch = v.ch_n[region];
   const int AS1* ch = region ? v.chX : v.chF;
   const int base = region ? v.ch_n[2] : 0;
-  const bool fastU = region == 0 && nfree <= BA_FAST_FREE;
   double cur = 0.0;
-  double uacc[BA_U_PAIRS];                                             // lane's sums: (camera, value) pairs lane, lane + 64, lane + 128
-  _Pragma("unroll") for (int k = 0; k < BA_U_PAIRS; k++) uacc[k] = 0.0;
+  double uacc[U_PAIRS];                                                // lane's sums: (camera, value) pairs lane, lane + 64, lane + 128
+  _Pragma("unroll") for (int k = 0; k < U_PAIRS; k++) uacc[k] = 0.0;
   // The static part of a slot (32 B) is loaded a chunk ahead: the chunk table entry of the next chunk at the top of this one,
   // its slots' fields behind this chunk's projection -- a wavefront has at most one other wavefront on its SIMD to hide a
   // dependent chain of global loads behind.  The camera poses come out of LDS.
@@ -608,14 +636,14 @@ BA_PHASE_FN double ba_step_sweep(const BaView& v_, const BaConfig& cfg_, int reg
   // (the reduced camera system and the map update re-derive W from them; v3Cam is re-derived there from the point and the pose);
   // v3Cam and epsilon too when more than BA_FAST_FREE cameras are adjusted (the wave-per-block forms read them).  An X slot is
   // consumed here and now: nothing else is stored for it.
-  const bool storeD = region == 0, storeAll = region == 0 && nfree > BA_FAST_FREE;
+  constexpr bool storeD = region == 0, storeAll = region == 0 && !fastU;   // (region F without the U sums: more than BA_FAST_FREE cameras)
   for (int k = wave; k < nch; k += BA_WAVES) {
     const int a0 = base + cs0, ntot = cs1 - cs0;                       // <= 64 slots, or ONE point with more (a keyframe-rich map: fixed cameras)
     const int kn = k + BA_WAVES;
     int ns0 = 0, ns1 = 0;
     if (kn < nch) { ns0 = ch[kn]; ns1 = ch[kn + 1]; }
     SlotIn nin = cin;
-    const int ntrip = (ntot + 63) >> 6;
+    const int ntrip = region == 1 ? (ntot + 63) >> 6 : 1;              // (a point has at most 64 F slots, one per adjustable camera: region F never needs a second trip)
     double carry[9];                                                   // lane 0: the running sums of a point that spans several trips
     _Pragma("unroll") for (int q = 0; q < 9; q++) carry[q] = 0.0;
     for (int trip = 0; trip < (ntrip > 0 ? ntrip : 1); trip++) {
@@ -642,40 +670,44 @@ BA_PHASE_FN double ba_step_sweep(const BaView& v_, const BaConfig& cfg_, int reg
     int st = act ? SL_STATE(info) : MS_ERASED;
     bool valid = false;
     double c[3] = {0, 0, 1}, d[4] = {0, 0, 0, 0}, e0 = 0, e1 = 0;
-    if (st != MS_ERASED) {
+    // The state nest (erased / behind the camera / weight 0 / valid) runs flat: projection, derivatives and weight on every lane
+    // -- a lane behind the camera divides by 1 instead -- and the state, the objective's term and the stores are chosen at the end.
+    // A valid lane executes what it executed inside the nest, on the same values; nothing of another lane is stored or summed.
+    {
+      const bool live = st != MS_ERASED;
       pose_xform(T, X, c);
-      if (storeAll) { SL(sl_cm, 0, s) = c[0]; SL(sl_cm, 1, s) = c[1]; SL(sl_cm, 2, s) = c[2]; }
-      if (c[2] <= 0) { st = MS_BAD; cur += 1.0; }                       // pass 1: bBad (:186-189); pass 2: :243-246
-      else {
-        const CamProj pr = cam_project(cfg.cam, c[0] / c[2], c[1] / c[2]);
-        double dd[4];
-        cam_derivs(cfg.cam, pr, dd);
-        e0 = (f0 - pr.im[0]) * sn; e1 = (f1 - pr.im[1]) * sn;
-        const double e2 = e0 * e0 + e1 * e1;
-        const double dWeight = tukey_sqrt_weight(e2, sigma2);
-        e0 *= dWeight; e1 *= dWeight;
-        if (storeAll) { SL(sl_eps, 0, s) = e0; SL(sl_eps, 1, s) = e1; }
-        if (dWeight == 0) { st = MS_BAD; cur += 1.0; }
-        else {
-          st = MS_OK; valid = true;
-          cur += tukey_objective(e2, sigma2);
-          _Pragma("unroll") for (int q = 0; q < 4; q++) { d[q] = sn * (dWeight * dd[q]); if (storeD) SL(sl_d, q, s) = d[q]; }   // weighted from here on
-        }
+      const bool front = !(c[2] <= 0);                                  // pass 1: bBad (:186-189); pass 2: :243-246
+      const double cz = front ? c[2] : 1.0;
+      const CamProj pr = cam_project(cfg.cam, c[0] / cz, c[1] / cz);
+      double dd[4];
+      cam_derivs(cfg.cam, pr, dd);
+      e0 = (f0 - pr.im[0]) * sn; e1 = (f1 - pr.im[1]) * sn;
+      const double e2 = e0 * e0 + e1 * e1;
+      const double dWeight = tukey_sqrt_weight(e2, sigma2);
+      e0 *= dWeight; e1 *= dWeight;
+      valid = live && front && !(dWeight == 0);
+      const double term = valid ? tukey_objective(e2, sigma2) : 1.0;
+      cur = live ? cur + term : cur;
+      _Pragma("unroll") for (int q = 0; q < 4; q++) d[q] = sn * (dWeight * dd[q]);   // weighted from here on (used where valid)
+      if (live) {
+        st = valid ? MS_OK : MS_BAD;
+        if (storeAll) { SL(sl_cm, 0, s) = c[0]; SL(sl_cm, 1, s) = c[1]; SL(sl_cm, 2, s) = c[2]; }
+        if (storeAll && front) { SL(sl_eps, 0, s) = e0; SL(sl_eps, 1, s) = e1; }
+        if (storeD && valid) { _Pragma("unroll") for (int q = 0; q < 4; q++) SL(sl_d, q, s) = d[q]; }
+        v.sl_info[s] = SL_WITH_STATE(info, st);
       }
-      v.sl_info[s] = SL_WITH_STATE(info, st);
     }
     // ---- V, epsilon_b ----
     {
       double pr9[9];
-      _Pragma("unroll") for (int q = 0; q < 9; q++) pr9[q] = 0.0;
-      if (valid) {
+      {                                                                // (flat like the state nest: every lane forms the products, a lane that is not valid leaves zeros)
         double B[6];
         ba_jac_B(T.R, c, d, B);
         int q = 0;
         _Pragma("unroll") for (int r = 0; r < 3; r++) for (int cc = 0; cc <= r; cc++) pr9[q++] = B[r] * B[cc] + B[3 + r] * B[3 + cc];   // :49-56 LL triangle
         _Pragma("unroll") for (int r = 0; r < 3; r++) pr9[6 + r] = B[r] * e0 + B[3 + r] * e1;
       }
-      _Pragma("unroll") for (int q = 0; q < 9; q++) stg[lane * 9 + q] = pr9[q];
+      _Pragma("unroll") for (int q = 0; q < 9; q++) stg[lane * 9 + q] = valid ? pr9[q] : 0.0;
       __builtin_amdgcn_s_waitcnt(0xC07F);
       __builtin_amdgcn_wave_barrier();
       if (kn < nch && trip == (ntrip > 0 ? ntrip : 1) - 1) load_in(base + ns0, min(64, ns1 - ns0), nin);   // the next chunk's slots, behind the sums below
@@ -712,23 +744,24 @@ BA_PHASE_FN double ba_step_sweep(const BaView& v_, const BaConfig& cfg_, int reg
     // ballots); lane (f, q) then adds value q of camera f's entries in that order.  (The predecessor multiplied the 27 products
     // by a 0 / 1 mask for each of the five cameras and reduced each masked set across the wavefront: five times the products and
     // ~1500 shuffle-address / select / bpermute instructions per chunk.)
-    if (fastU) {
+    if constexpr (fastU) {
       double A[12];
-      _Pragma("unroll") for (int q = 0; q < 12; q++) A[q] = 0.0;
-      if (valid) ba_jac_A(c, d, A);
+      ba_jac_A(c, d, A);                                               // (every lane; only a valid lane's products are stored below)
       const int ford = valid ? SL_FORD(info) : 255;
-      int offf[BA_FAST_FREE], cntf[BA_FAST_FREE];
-      int mypos = 0, run = 0;
-      _Pragma("unroll") for (int f = 0; f < BA_FAST_FREE; f++) {
-        offf[f] = run; cntf[f] = 0;
+      // where camera f's entries start in the staging area and how many they are: both wavefront-uniform, left in lane f's
+      // register (offset | count << 8) and fetched by the consumer lanes with one cross-lane read per pass
+      int mypos = 0, run = 0, offcnt = 0;
+      _Pragma("unroll") for (int f = 0; f < UFREE; f++) {
         if (f < nfree) {                                               // (uniform)
           const unsigned long long mk = __ballot(ford == f);
           const int cf = (int)__popcll(mk);
-          if (ford == f) mypos = run + (int)__popcll(mk & ((1ull << lane) - 1ull));
-          cntf[f] = cf; run += cf;
+          const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));   // camera f's slots in lower lanes
+          mypos = ford == f ? run + below : mypos;
+          if (lane == f) offcnt = run | (cf << 8);
+          run += cf;
         }
       }
-      if (ford < BA_FAST_FREE) {
+      if (ford < UFREE) {
         double AS3* dst = stg + mypos * 27;
         int q = 0;
         _Pragma("unroll") for (int r = 0; r < 6; r++) for (int cc = 0; cc <= r; cc++) dst[q++] = A[r] * A[cc] + A[6 + r] * A[6 + cc];       // :40-47
@@ -736,13 +769,13 @@ BA_PHASE_FN double ba_step_sweep(const BaView& v_, const BaConfig& cfg_, int reg
       }
       __builtin_amdgcn_s_waitcnt(0xC07F);
       __builtin_amdgcn_wave_barrier();
-      _Pragma("unroll") for (int k = 0; k < BA_U_PAIRS; k++) {
+      _Pragma("unroll") for (int k = 0; k < U_PAIRS; k++) {
         if (64 * k >= nfree * 27) break;                               // (uniform)
         const int pid = lane + 64 * k;
+        const int f = pid / 27, q = pid - 27 * f;                      // f <= (63 + 64 (U_PAIRS - 1)) / 27 < 64
+        const int oc = __shfl(offcnt, f);                              // (every lane takes part: a lane that is switched off hands out nothing)
         if (pid < nfree * 27) {
-          const int f = pid / 27, q = pid - 27 * f;
-          int o = offf[0], cf = cntf[0];
-          _Pragma("unroll") for (int g = 1; g < BA_FAST_FREE; g++) if (g < nfree && f == g) { o = offf[g]; cf = cntf[g]; }
+          const int o = oc & 255, cf = oc >> 8;
           double acc = uacc[k];
           const double AS3* src = stg + o * 27 + q;
           int r = 0;
@@ -765,9 +798,8 @@ BA_PHASE_FN double ba_step_sweep(const BaView& v_, const BaConfig& cfg_, int reg
     if (kn < nch) { _Pragma("unroll") for (int q = 0; q < 3; q++) cX[q] = v.pt_pos[3 * nin.pt + q]; }   // the next chunk's points (its slot fields have arrived by now)
     cs0 = ns0; cs1 = ns1; cin = nin;
   }
-  if (fastU) {
-    (void)ured_;
-    _Pragma("unroll") for (int k = 0; k < BA_U_PAIRS; k++) {
+  if constexpr (fastU) {
+    _Pragma("unroll") for (int k = 0; k < U_PAIRS; k++) {
       const int pid = lane + 64 * k;
       if (pid < nfree * 27) stg[pid] = uacc[k];                        // [camera][27]: the staging area is free after the last chunk
     }
@@ -1247,10 +1279,12 @@ struct BaFastSums {
   }
   // passes 1 + 2 (:209-321) in one sweep: weights, objective, V / epsilon_b, U / epsilon_a; A, B, W are re-derived by their consumers
   DEVFN double step(int M, int nc, int np, int nfree, double sigma2) {
-    double* stg = lds; double* ured = nullptr; double* camsL = lds + BA_WAVES * 64 * BA_SWEEP_STAGE;
+    double* stg = lds; double* camsL = lds + BA_WAVES * 64 * BA_SWEEP_STAGE;
     for (int t = threadIdx.x; t < nc * 12; t += BA_THREADS) camsL[t] = ((const double AS1*)v.cam_pose)[t];   // Pose = R[9], t[3]
     __syncthreads();
-    double cur = ba_step_sweep(v_, cfg, 0, sigma2, nfree, stg, ured, camsL);
+    double cur = nfree <= BA_MFMA_FREE ? ba_step_sweep<0, BA_MFMA_FREE>(v_, cfg, sigma2, nfree, stg, camsL)
+               : nfree <= BA_FAST_FREE ? ba_step_sweep<0, BA_FAST_FREE>(v_, cfg, sigma2, nfree, stg, camsL)
+                                       : ba_step_sweep<0, 0>(v_, cfg, sigma2, nfree, stg, camsL);
     __syncthreads();
     if (nfree <= BA_FAST_FREE) {
       for (int t = threadIdx.x; t < nfree * 27; t += BA_THREADS) {     // wave partials in wave order
@@ -1263,7 +1297,7 @@ struct BaFastSums {
       __syncthreads();                                                 // the sums sit in the staging areas the next sweep writes
     }
     BA_STAMP(3);
-    cur += ba_step_sweep(v_, cfg, 1, sigma2, nfree, stg, ured, camsL);
+    cur += ba_step_sweep<1, 0>(v_, cfg, sigma2, nfree, stg, camsL);
     cur = ba_block_sum(cur, red);
     BA_STAMP(4);
     if (nfree > BA_FAST_FREE) { ba_accum_U_generic(v_, nfree, np); __syncthreads(); }
@@ -1405,8 +1439,7 @@ DEVFN void ba_lm(const BaView& v_, const BaConfig& cfg, const BaOrdView& o) {
     }
     if (sh_error) break;
     if (sh_new_err < sh_cur_err) {                                     // :503-514
-      for (int j = threadIdx.x; j < nc; j += BA_THREADS) ba_store_pose(v.cam_pose + j, ba_load_pose(v.cam_new + j));
-      for (int t = threadIdx.x; t < 3 * np; t += BA_THREADS) v.pt_pos[t] = v.pt_new[t];
+      ba_commit_copy(v_, nc, np);
       if (threadIdx.x == 0) { sh_factor = 2.0; sh_lambda *= 0.3; sh_accepted++; sh_cache_valid = 1; }   // ModifyLambda_GoodStep :609-612
     } else if (threadIdx.x == 0) sh_cache_valid = 0;
     __syncthreads();
