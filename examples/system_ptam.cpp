@@ -3,6 +3,8 @@
 // Usage: system_ptam [n_frames]        a ground-truth map is uploaded, then n_frames are tracked
 //        system_ptam [n_frames] boot   no map: the screen is touched at frames 0 and 12 and the tracker makes its own
 //                                      (trail tracking + MapMaker::InitFromStereo on the device), then keeps tracking
+//        system_ptam [n_frames] draw <path>   as boot; the colour frame is cleared before every update, and the last one -- what
+//                                      TrackFrame drew on it -- is written raw (640 x 480 x 4 bytes R, G, B, A) to <path>
 //        system_ptam [n_frames] reset  as boot, then Tracker::Reset() drops the map and a second one is made from the frames that follow
 // (needs an MI355X; prints the tracker's user message per frame)
 #include <cstdio>
@@ -47,6 +49,27 @@ int main(int argc, char** argv) {
     KeyFrame k0, k1; std::vector<std::pair<MapMaker::ImageRef, MapMaker::ImageRef>> none; mySE3 T;
     const bool ok = boot.mpMapMaker->InitFromStereo(k0, k1, none, T);   // the map exists: reports it
     printf("InitFromStereo: %s, camera at t = (%.3f %.3f %.3f)\n", ok ? "map made" : "no map", T.t[0], T.t[1], T.t[2]);
+    vslam_feeder_destroy(f);
+    return ok ? 0 : 1;
+  }
+  if (argc > 3 && std::string(argv[2]) == "draw") {               // the one output of TrackFrame a person looks at: the colour frame it draws on
+    SystemPTAM boot(W, H, true);
+    cv::Mat bw(H, W, CV_8UC1), rgb(H, W, CV_8UC4);
+    for (int t = 0; t < n; t++) {
+      double p[12];
+      vslam_feeder_pose(f, t, p);
+      vslam_feeder_render_pose(f, p, 100 + t, bw.data, bw.step);
+      if (t == 0 || t == 12) boot.onTouchScreen();
+      for (int y = 0; y < H; y++) memset(rgb.ptr<unsigned char>(y), 0, (size_t)W * 4);
+      boot.update(bw, rgb);
+    }
+    int info[4] = {0, 0, 0, 0};
+    vslam_get_overlay_info(boot.mpMap->sys, 0, info);
+    printf("frame %d: %d discs, %d lines | %s\n", n - 1, info[1], info[2], boot.mpTracker->GetMessageForUser().c_str());
+    FILE* out = fopen(argv[3], "wb");
+    bool ok = out != nullptr;
+    for (int y = 0; ok && y < H; y++) ok = fwrite(rgb.ptr<unsigned char>(y), 1, (size_t)W * 4, out) == (size_t)W * 4;
+    if (out) ok = fclose(out) == 0 && ok;
     vslam_feeder_destroy(f);
     return ok ? 0 : 1;
   }

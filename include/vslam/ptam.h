@@ -43,6 +43,15 @@ struct Mat {  // minimal stand-in for cv::Mat as used by jni/KeyFrame.cc:12-23 (
 
 namespace vslam_detail {
 inline void check(int rc) { if (rc < 0) throw std::runtime_error(std::string("vslam: ") + vslam_last_error()); }
+// What Tracker::TrackFrame draws on imageColor (jni/Tracker.cc:580-588 the found patches, always; :322-336 the trails, if bDraw), in
+// place on stream 0's colour frame; any Mat that is not CV_8UC4 of the frame's size is left alone.  Returns whether it drew.
+template <class MatT> inline bool draw(vslam_system* sys, MatT& imageColor, int width, int height, bool bDraw) {
+  if (!imageColor.data || imageColor.type() != CV_8UC4 || imageColor.cols != width || imageColor.rows != height) return false;
+  const int stream = 0;
+  check(vslam_render_overlay(sys, &stream, 1, imageColor.data, (size_t)imageColor.step, 0, 0,
+                             VSLAM_DRAW_POINTS | (bDraw ? VSLAM_DRAW_TRAILS : 0) | VSLAM_DRAW_IN_PLACE));
+  return true;
+}
 }
 
 // jni/RT.h:247-312: camera-from-world rigid transform; R row-major.
@@ -190,15 +199,19 @@ class Tracker {
     if (bBootstrap) { p.bootstrap = 1; p.grow_map = 3; }
     p.pvs_shuffle_seed = nPVSShuffleSeed;
     p.keyframe_retire = bRetireKeyFrames ? 1 : 0;
+    p.overlay = 1;                                                                                       // TrackFrame draws on imageColor
+    mnWidth = width; mnHeight = heigth;
     for (int i = 0; i < 5; i++) p.cam[i] = c.params[i];
     vslam_detail::check(vslam_create(&p, &mMap.sys));
     mCurrentKF.sys = mMap.sys;
   }
-  // jni/Tracker.cc:76-146.  imageColor is only drawn on in the reference; it is ignored here.
-  void TrackFrame(cv::Mat& imFrame, cv::Mat& /*imageColor*/, bool /*bDraw*/) {
+  // jni/Tracker.cc:76-146.  imageColor (CV_8UC4 of the frame's size; anything else is ignored) is drawn on as in the reference: the found
+  // patches always, the trails if bDraw (vslam_render_overlay, in place).
+  void TrackFrame(cv::Mat& imFrame, cv::Mat& imageColor, bool bDraw) {
     if (mbUserPressedReset) Reset();                                                                     // the GUI's "Reset" (jni/Tracker.h:139), taken up by the next frame
     if (mbUserPressedSpacebar) { mbUserPressedSpacebar = false; vslam_touch(mMap.sys); }
     vslam_detail::check(vslam_update(mMap.sys, imFrame.data, imFrame.step, 0));
+    vslam_detail::draw(mMap.sys, imageColor, mnWidth, mnHeight, bDraw);
   }
   mySE3 GetCurrentPose() {                                                                              // jni/Tracker.h:58
     vslam_track_state s; vslam_detail::check(vslam_get_state(mMap.sys, 0, &s));
@@ -216,6 +229,7 @@ class Tracker {
   KeyFrame mCurrentKF;
   Map& mMap;
   MapMaker& mMapMaker;
+  int mnWidth = 0, mnHeight = 0;
 };
 
 // jni/Bundle.h:107-160 (public surface), one problem per object.

@@ -111,6 +111,11 @@ typedef struct vslam_params {
                                       here the order is the seeded permutation of csrc/pvs_perm.h, a function of (seed, frame, list, length).
                                       0 (default): the identity order, map order.  Non-zero: every stream starts with this seed
                                       (vslam_set_pvs_seed changes one stream's) */
+  int overlay;                     /* 1: the system can draw what Tracker::TrackFrame draws on its colour frame (vslam_render_overlay below).  It keeps
+                                      one int per stream, the mnFrame at which TrackMap last ran for it, written by one 64-lane launch in front of the
+                                      motion model; every other read-back gives the bits it gives with 0.  0 (default): nothing is allocated, nothing
+                                      is launched, vslam_render_overlay returns VSLAM_E_STATE.
+                                      (It stands in front of keyframe_retire, which stays the struct's last member.) */
   int keyframe_retire;             /* What a stream does whose map holds max_keyframes keyframes when its tracker wants another one (NeedNewKeyFrame,
                                       jni/MapMaker.cc:761-773).  0 (default): nothing, the map stops growing (the reference's map has no limit,
                                       jni/Map.h:21-34).  1: it asks for the keyframe after all, and vslam_finish_frame / vslam_add_keyframe first
@@ -290,6 +295,44 @@ int vslam_get_retire_info(vslam_system* sys, int stream, int out[6]);
 /* HIP-event milliseconds of the last vslam_retire_keyframes that retired, its three launches on the system's stream.  Waits for them.
  * VSLAM_E_STATE before the first such call. */
 int vslam_get_retire_timing(vslam_system* sys, double* ms);
+
+/* ---- overlay: the tracker's points and trails drawn into RGBA (vslam_params.overlay) -------------
+ * What Tracker::TrackFrame draws on imageColor (jni/Tracker.cc:580-588 the patches TrackMap found, as discs coloured by pyramid level, the
+ * `if(mbDraw)` guard commented out; :322-336 the bootstrap trails, as lines) and native_update hands back to the Java view
+ * (jni/jni_part.cpp:59-71, 132-145).  The raster rules -- pixel format R, G, B, A; colours; the 21-pixel disc; the 4-pixel corner mark; the
+ * closed form of the 8-connected line; clipping; drawing order -- are this build's own (OpenCV's cv::circle / cv::line are third-party
+ * arithmetic, parity unpinned) and are stated once, in csrc/overlay_dev.h.  What is drawn for a stream is a pure function of read-backs
+ * taken at the time of the call:
+ *   base                 level 0 of the stream's current frame (vslam_read_level_image) as R = G = B = gray, A = 255; with
+ *                        VSLAM_DRAW_IN_PLACE the caller's image, of which only drawn pixels are written (the reference's behaviour);
+ *   VSLAM_DRAW_POINTS    a disc for every entry of the iteration set (vslam_get_search_plan) whose point has `found` set, centre = `image`
+ *                        truncated, colour by `level` (vslam_get_point_tracks); the first entry ends on top.  Only if TrackMap ran for the
+ *                        stream in its latest frame: a lost stream, a stream without a map and one just reset, restored or retired from
+ *                        get no discs;
+ *   VSLAM_DRAW_TRAILS    a line per trail (vslam_get_trails), initial -> current position, while init_stage == 1;
+ *   VSLAM_DRAW_FAST      a mark at every level-0 corner of the current frame (vslam_read_corners; Tracker::drawFast, :148-155);
+ *   VSLAM_DRAW_ALPHA0    a drawn pixel's alpha is 0 (what cv::Scalar's unset fourth value writes), not 255.
+ * Marks lie under lines under discs. */
+#define VSLAM_DRAW_POINTS 1
+#define VSLAM_DRAW_TRAILS 2
+#define VSLAM_DRAW_FAST 4
+#define VSLAM_DRAW_IN_PLACE 8
+#define VSLAM_DRAW_ALPHA0 16
+/* image i (rgba + i*stream_stride, rows row_stride bytes apart, any alignment) belongs to streams[i]; streams == NULL: every stream, image s =
+ * stream s (n is not read).  Between frames, and in a stage-wise frame after vslam_pose_update(sys, 1); earlier in an open frame
+ * VSLAM_E_STATE.  on_device != 0: rgba is device memory and is written directly, asynchronously on the system's stream (a call with a stream
+ * list waits once, for the list's upload).  Host memory: the call synchronises; in place the images go up, are drawn on and come down.
+ * VSLAM_E_INVALID: NULL system, n < 0 or n > n_streams, an index outside the batch or a duplicate, NULL rgba with n > 0, row_stride <
+ * 4 * width, stream_stride < row_stride * height with more than one image, unknown flag bits.  VSLAM_E_STATE: overlay = 0, no current
+ * frame, or a listed stream was held in the last step (it has no front-end products).  A refused call writes nothing. */
+int vslam_render_overlay(vslam_system* sys, const int* streams, int n, uint8_t* rgba, size_t row_stride, size_t stream_stride, int on_device, int flags);
+/* out[0..3] = mnFrame at which TrackMap last ran (-1 none); discs, lines, marks of the stream's last render */
+int vslam_get_overlay_info(vslam_system* sys, int stream, int out[4]);
+int vslam_get_render_timing(vslam_system* sys, double* ms);   /* HIP events around the last render's launches; waits for them */
+/* self-test hook, no system: the same device raster routines over primitives given by the caller, one image, host memory, synchronous.
+ * width, height 1..4096; coordinates within +-32767; flags: VSLAM_DRAW_IN_PLACE (gray is not read) and VSLAM_DRAW_ALPHA0 */
+int vslam_eval_overlay(int width, int height, const uint8_t* gray, size_t gray_stride, int n_marks, const int* marks_xy, int n_lines, const int* lines_xyxy,
+                       int n_discs, const int* discs_xy_level /* 3 ints each, list order = iteration-set order */, uint8_t* rgba, size_t row_stride, int flags);
 
 /* ---- stream snapshots ------------------------------------------------------------------------
  * One stream taken out of a live batch whole, and put back bit for bit into any slot of any compatible system.  The reference's only

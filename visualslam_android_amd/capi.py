@@ -14,6 +14,13 @@ Q_CAM_INT_RADIUS = 1
 Q_POSE_INT_RESIDUAL = 2
 Q_NONMAX_RIGHT_NEIGHBOUR = 4
 
+# vslam_render_overlay / vslam_eval_overlay flags
+DRAW_POINTS = 1
+DRAW_TRAILS = 2
+DRAW_FAST = 4
+DRAW_IN_PLACE = 8
+DRAW_ALPHA0 = 16
+
 
 class VslamError(RuntimeError):
     pass
@@ -33,7 +40,7 @@ class Params(C.Structure):
         ("ba_min_tukey_sigma", C.c_double), ("ba_window", C.c_int), ("ba_min_keyframes", C.c_int),
         ("cam", C.c_double * 5), ("quirks", C.c_int), ("device", C.c_int), ("ba_delay_frames", C.c_int),
         ("grow_map", C.c_int), ("ba_batch_frames", C.c_int), ("idle_iterations", C.c_int), ("bootstrap", C.c_int), ("ba_sum_order", C.c_int),
-        ("relocalise", C.c_int), ("reloc_blur", C.c_double), ("pvs_shuffle_seed", C.c_uint), ("keyframe_retire", C.c_int),
+        ("relocalise", C.c_int), ("reloc_blur", C.c_double), ("pvs_shuffle_seed", C.c_uint), ("overlay", C.c_int), ("keyframe_retire", C.c_int),
     ]
 
 
@@ -122,6 +129,10 @@ SYMBOLS = {
     "vslam_retire_keyframes": (_i, [_sys, _vp, _vp, _i]),
     "vslam_get_retire_info": (_i, [_sys, _i, _vp]),
     "vslam_get_retire_timing": (_i, [_sys, C.POINTER(_d)]),
+    "vslam_render_overlay": (_i, [_sys, _vp, _i, _vp, _sz, _sz, _i, _i]),
+    "vslam_get_overlay_info": (_i, [_sys, _i, _vp]),
+    "vslam_get_render_timing": (_i, [_sys, C.POINTER(_d)]),
+    "vslam_eval_overlay": (_i, [_i, _i, _vp, _sz, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _i]),
     "vslam_snapshot_size": (_i, [_sys, _i, C.POINTER(_sz)]),
     "vslam_snapshot_stream": (_i, [_sys, _i, _vp, _sz, _i, C.POINTER(_sz)]),
     "vslam_restore_stream": (_i, [_sys, _i, _vp, _sz, _i]),
@@ -303,6 +314,32 @@ def pvs_permutation(seed, frame, lst, n, keys=None, on_host=False):
     assert k is None or len(k) == n
     _check(load_library().vslam_pvs_permutation(seed, frame, lst, n, None if k is None else k.ctypes.data, out.ctypes.data, int(on_host)))
     return out
+
+
+def _prims(a, per):
+    a = np.ascontiguousarray(np.zeros((0, per)) if a is None else a, np.int32).reshape(-1, per)
+    return a, (a.ctypes.data if len(a) else None)
+
+
+def eval_overlay(gray, marks=None, lines=None, discs=None, flags=0, rgba=None, row_stride=None):
+    """vslam_eval_overlay: the renderer's device raster routines over the caller's primitives -- marks (n, 2) x y, lines (n, 4)
+    x y x y, discs (n, 3) x y level in iteration-set order -- on one image.  gray: uint8 (H, W), the base.  With DRAW_IN_PLACE rgba is
+    the image drawn on (a uint8 buffer of at least row_stride * (H - 1) + 4 * W bytes; gray then only gives the size).  -> the buffer as
+    a flat uint8 array when row_stride is given, else (H, W, 4)."""
+    gray = np.ascontiguousarray(gray, np.uint8)
+    h, w = gray.shape
+    stride = 4 * w if row_stride is None else int(row_stride)
+    nbytes = stride * (h - 1) + 4 * w
+    if rgba is None:
+        out = np.zeros(nbytes, np.uint8)
+    else:
+        out = np.ascontiguousarray(rgba, np.uint8).reshape(-1).copy()
+        assert out.size >= nbytes, (out.size, nbytes)
+    m, pm = _prims(marks, 2)
+    l, pl = _prims(lines, 4)
+    d, pd = _prims(discs, 3)
+    _check(load_library().vslam_eval_overlay(w, h, gray.ctypes.data, w, len(m), pm, len(l), pl, len(d), pd, out.ctypes.data, stride, int(flags)))
+    return out if row_stride is not None else out.reshape(h, w, 4)
 
 
 class System:
@@ -527,6 +564,39 @@ class System:
         return ms.value
 
     # ---- stream snapshots --------------------------------------------------------------------
+    # ---- overlay (vslam_params.overlay = 1) ----------------------------------------------------------
+    def _overlay_streams(self, streams):
+        if streams is None:
+            return None, self.S
+        a = np.ascontiguousarray(np.atleast_1d(streams), np.int32)
+        return a, len(a)
+
+    def render_overlay(self, streams=None, flags=DRAW_POINTS | DRAW_TRAILS, rgba=None):
+        """vslam_render_overlay into host memory -> uint8 [n, H, W, 4] (R, G, B, A), image i for streams[i] (None: every stream).  With
+        DRAW_IN_PLACE rgba [n, H, W, 4] is the image drawn on (a copy is returned)."""
+        a, n = self._overlay_streams(streams)
+        h, w = self.params.height, self.params.width
+        out = np.zeros((n, h, w, 4), np.uint8) if rgba is None else np.ascontiguousarray(rgba, np.uint8).reshape(n, h, w, 4).copy()
+        _check(self.lib.vslam_render_overlay(self.h, None if a is None else (a.ctypes.data if n else None), n, out.ctypes.data if n else None,
+                                             4 * w, 4 * w * h, 0, int(flags)))
+        return out
+
+    def render_overlay_device(self, streams, dev_ptr, row_stride, stream_stride, flags=DRAW_POINTS | DRAW_TRAILS):
+        """... into device memory, asynchronous on the system's stream"""
+        a, n = self._overlay_streams(streams)
+        _check(self.lib.vslam_render_overlay(self.h, None if a is None else (a.ctypes.data if n else None), n, dev_ptr, row_stride, stream_stride, 1, int(flags)))
+
+    def overlay_info(self, stream):
+        o = np.zeros(4, np.int32)
+        _check(self.lib.vslam_get_overlay_info(self.h, stream, o.ctypes.data))
+        return dict(zip(("track_map_frame", "discs", "lines", "marks"), (int(x) for x in o)))
+
+    def render_timing(self):
+        """-> HIP-event ms of the last render_overlay's launches (vslam_get_render_timing)"""
+        ms = C.c_double(0.0)
+        _check(self.lib.vslam_get_render_timing(self.h, C.byref(ms)))
+        return ms.value
+
     def snapshot_size(self, stream):
         n = _sz(0)
         _check(self.lib.vslam_snapshot_size(self.h, stream, C.byref(n)))

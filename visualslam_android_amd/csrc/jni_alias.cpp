@@ -3,7 +3,8 @@
 //   Java_vision_ar_monoslam_SystemPTAM_native_1createTest   -> vslam_create   (800x480, jni_part.cpp:41; one stream)
 //   Java_vision_ar_monoslam_SystemPTAM_native_1disposeTest  -> vslam_destroy
 //   Java_vision_ar_monoslam_SystemPTAM_native_1touchScreen  -> vslam_touch    (mbUserPressedSpacebar, jni_part.cpp:49-51)
-//   Java_vision_ar_monoslam_SystemPTAM_native_1update       -> vslam_update   (gray cv::Mat* smuggled as jlong, :132-145)
+//   Java_vision_ar_monoslam_SystemPTAM_native_1update       -> vslam_update + vslam_render_overlay (gray and rgba cv::Mat* smuggled as
+//                                                              jlong, :132-145; the rgba frame is drawn on in place, bDraw true :66-68)
 //   Java_vision_ar_monoslam_MainActivity_FindFeatures       -> empty, as in the reference (:84-103, body commented out)
 // The Java side (src/vision/ar/monoslam/SystemPTAM.java:8-35) is unchanged.  cv::Mat is only read through data / step, so the
 // stand-in of include/vslam/ptam.h is layout-INcompatible with OpenCV's: a build against the Android OpenCV SDK defines
@@ -27,6 +28,7 @@ extern "C" {
 JNIEXPORT jlong JNICALL Java_vision_ar_monoslam_SystemPTAM_native_1createTest(JNIEnv*, jobject) {
   vslam_params p;
   if (vslam_default_params(&p, 800, 480, 1) != VSLAM_OK) return 0;      // jni/jni_part.cpp:41 constructs the tracker at 800 x 480
+  p.overlay = 1;                                                        // native_update draws on the colour frame
   vslam_system* sys = nullptr;
   return vslam_create(&p, &sys) == VSLAM_OK ? reinterpret_cast<jlong>(sys) : 0;
 }
@@ -39,9 +41,16 @@ JNIEXPORT void JNICALL Java_vision_ar_monoslam_SystemPTAM_native_1touchScreen(JN
   vslam_touch(reinterpret_cast<vslam_system*>(cptr));
 }
 
-JNIEXPORT jint JNICALL Java_vision_ar_monoslam_SystemPTAM_native_1update(JNIEnv*, jobject, jlong cptr, jlong addrGray, jlong /*addrRgba*/) {
+JNIEXPORT jint JNICALL Java_vision_ar_monoslam_SystemPTAM_native_1update(JNIEnv*, jobject, jlong cptr, jlong addrGray, jlong addrRgba) {
   cv::Mat& gray = *reinterpret_cast<cv::Mat*>(addrGray);               // CV_8UC1, as MainActivity.onCameraFrame passes it
-  vslam_update(reinterpret_cast<vslam_system*>(cptr), gray.data, gray.step, 0);   // Tracker::TrackFrame
+  vslam_system* sys = reinterpret_cast<vslam_system*>(cptr);
+  if (vslam_update(sys, gray.data, gray.step, 0) == VSLAM_OK && addrRgba) {       // Tracker::TrackFrame(gray, rgba, true), jni/jni_part.cpp:66-68
+    cv::Mat& rgba = *reinterpret_cast<cv::Mat*>(addrRgba);             // CV_8UC4 of the gray frame's size; anything else is left alone
+    if (rgba.data && rgba.type() == CV_8UC4 && rgba.cols == gray.cols && rgba.rows == gray.rows) {
+      const int stream = 0;
+      vslam_render_overlay(sys, &stream, 1, rgba.data, (size_t)rgba.step, 0, 0, VSLAM_DRAW_POINTS | VSLAM_DRAW_TRAILS | VSLAM_DRAW_IN_PLACE);
+    }
+  }
   return 0;                                                            // the reference returns constant 0 (:144)
 }
 

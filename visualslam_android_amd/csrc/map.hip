@@ -228,7 +228,7 @@ extern "C" int vslam_patch_search(vslam_system* sys, int stage) {
     if (sys->frame_open) { vslam_set_error("patch_search: the previous frame was not finished (vslam_finish_frame)"); return VSLAM_E_STATE; }
     int r = ba_frame_start(sys);                                                       // deferred map-maker results that are due now
     if (r) return r;
-    sys->frame_open = true;
+    sys->frame_open = true; sys->frame_tracked = false;
   } else if (!sys->frame_open) { vslam_set_error("patch_search: stage 1 before stage 0"); return VSLAM_E_STATE; }
   return trk_search_stage(sys, stage);
 }
@@ -236,6 +236,7 @@ extern "C" int vslam_patch_search(vslam_system* sys, int stage) {
 extern "C" int vslam_pose_update(vslam_system* sys, int stage) {
   if (!sys || stage < 0 || stage > 1) { vslam_set_error("pose_update: bad argument"); return VSLAM_E_INVALID; }
   if (!sys->frame_open) { vslam_set_error("pose_update: no search stage has run on this frame"); return VSLAM_E_STATE; }
+  if (stage == 1) sys->frame_tracked = true;                                           // from here the overlay may be drawn (overlay.hip)
   return trk_pose_stage(sys, stage);
 }
 

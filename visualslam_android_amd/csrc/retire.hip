@@ -376,6 +376,7 @@ extern "C" int vslam_retire_keyframes(vslam_system* sys, const int* streams, con
   }
   HIPCHK(hipEventRecord(sys->ev_retire_t[0], sys->stream));
   VCHK(retire_launch(sys, sys->retire_req));
+  VCHK(overlay_forget_listed(sys, sys->retire_req, RETIRE_NOT_LISTED));   // the listed streams draw no discs until TrackMap has run again
   HIPCHK(hipEventRecord(sys->ev_retire_t[1], sys->stream));
   sys->retire_calls++;
   return VSLAM_OK;

@@ -55,6 +55,7 @@ extern "C" int vslam_default_params(vslam_params* p, int width, int height, int 
   p->reloc_blur = 2.5;                                  // jni/SmallBlurryImage.h:19-20
   p->pvs_shuffle_seed = 0;                              // identity order (jni/Tracker.cc:396-397, 525 shuffle with rand())
   p->keyframe_retire = 0;                               // a full map stops making keyframes
+  p->overlay = 0;                                       // no renderer: nothing allocated, nothing launched
   return VSLAM_OK;
 }
 
@@ -144,6 +145,7 @@ static int sys_acquire(vslam_system* sys) {
   VCHK(reset_alloc(sys));
   VCHK(snapshot_alloc(sys));
   if (p->keyframe_retire) VCHK(retire_alloc(sys));
+  VCHK(overlay_alloc(sys));
   VCHK(map_init_states(sys));            // (on q, behind the zeroing of the states)
   HIPCHK(hipStreamSynchronize(q));       // the zeroing contract (DevOwner::alloc): from here on the memory is zero for every stream
   return VSLAM_OK;

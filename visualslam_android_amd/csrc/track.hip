@@ -1339,6 +1339,7 @@ int trk_search_stage(vslam_system* sys, int stage) {
   a.S = S; a.nblk = 1;
   if (stage == 0) {
     prof_mark(sys, PROF_PVS);
+    overlay_note_track_map(sys);                                     // vslam_params.overlay: on the state k_motion is about to read
     hipLaunchKernelGGL(k_motion, dim3((S + 63) / 64), dim3(64), 0, sys->stream, m, S, sys->p.use_sbi ? (const double*)sys->fr.sbi_rot : (const double*)nullptr);
     hipLaunchKernelGGL(k_pvs, dim3((P + TRK_THREADS - 1) / TRK_THREADS, S), dim3(TRK_THREADS), 0, sys->stream, m, tp);
     prof_mark(sys, PROF_PLAN_COARSE);

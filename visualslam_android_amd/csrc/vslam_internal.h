@@ -355,6 +355,7 @@ struct vslam_system {
   DevOwner own;               // everything the handle holds on the device; vslam_destroy releases it
   bool have_frame;
   bool frame_open = false;  // stage-wise TrackFrame (vslam_patch_search ... vslam_finish_frame) in progress
+  bool frame_tracked = false;   // ... and its vslam_pose_update(sys, 1) has been enqueued: the frame's tracker read-backs are final
   bool have_sbi;            // a SmallBlurryImage of a previous frame exists (mpSBILastFrame)
   // subset steps.  The list and the mask of a step travel through pinned memory, one block per front-end buffer: the front end of
   // step t+1 uploads its own while the tracker of step t still reads the other buffer's.
@@ -387,6 +388,12 @@ struct vslam_system {
   int* retire_req_stage = nullptr;           // [S] pinned host copy of the request
   hipEvent_t ev_retire_t[2] = {nullptr, nullptr};   // around the last explicit call's launches (vslam_get_retire_timing)
   long retire_calls = 0;
+  // the overlay renderer (overlay.hip; vslam_params.overlay): null with overlay = 0
+  int* overlay_ran = nullptr;                // [S] device: mnFrame at which TrackMap last ran for the stream, -1 never (or forgotten by a reset)
+  int* overlay_info = nullptr;               // [S][3] device: discs, lines, marks of the stream's last render
+  int* overlay_list = nullptr;               // [S] device: image -> stream of the last render that had a list
+  hipEvent_t ev_overlay_t[2] = {nullptr, nullptr};   // around the last render's launches (vslam_get_render_timing)
+  long overlay_calls = 0;
   // vslam_snapshot_stream / vslam_restore_stream (snapshot.hip)
   hipEvent_t ev_snap_t[4] = {nullptr, nullptr, nullptr, nullptr};   // around the last pack [0, 1] and the last unpack [2, 3] on the system's stream
   bool snap_timed[2] = {false, false};       // a pack / an unpack has run
@@ -509,6 +516,10 @@ int map_init_states(vslam_system* sys);
 int reset_alloc(vslam_system* sys);
 // snapshot.hip
 int snapshot_alloc(vslam_system* sys);
+// overlay.hip
+int overlay_alloc(vslam_system* sys);
+int overlay_note_track_map(vslam_system* sys);   // overlay = 1: records the frame for the streams whose TrackMap runs; the launch in front of k_motion
+int overlay_forget_listed(vslam_system* sys, const int* d_req, int not_listed);   // ... back to -1 for the streams a retirement lists
 // retire.hip
 int retire_alloc(vslam_system* sys);          // the scratch of keyframe retirement, if the system does not hold it yet
 int retire_on_keyframe(vslam_system* sys);    // keyframe_retire: one keyframe by policy for the full streams with kf_pending, before k_add_keyframe
