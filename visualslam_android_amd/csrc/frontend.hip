@@ -4,17 +4,18 @@
 // Kernels (byte/integer work, one pass over each level image; VALU-issue bound):
 //   k_fast_slide<PYR>  the form used whenever the level widths are multiples of 4 and the input is 16-B aligned: a lane owns
 //                 a strip 16 pixels wide, walks down it with a sliding window of seven rows in registers (no LDS staging),
-//                 runs a branch-free quick reject on every pixel, compacts the ~2 % survivors per wavefront and runs the
+//                 runs a branch-free quick reject on every pixel, two pixels per instruction (fast_reject_dev.h), compacts the ~2 % survivors per wavefront and runs the
 //                 16-pixel run-of-10 test on them; level 0 also writes its share of levels 1..3 from the same registers.
 //   k_pyr_fast0 / k_fast_lvl   the general path (any width / alignment): one workgroup per 16-row band staged in LDS,
 //                 pyramid from LDS, quick reject + compacted full test per 4 rows, corner-mask words in LDS.
-//   k_compact     per (band of rows, level, stream): the workgroup adds the row counts above its band, scans the popcounts
-//                 of its mask words (raster order) and every thread expands its words at its scanned offset -> bit-exact
-//                 raster-ordered corner list and row LUT (jni/KeyFrame.cc:43-49) without ordered atomics.
+//   k_compact     per (band of rows, level, stream) one wavefront: it adds the row counts above its band, scans the popcounts
+//                 of its mask words (raster order) and every lane expands its words at its scanned offset -> bit-exact
+//                 raster-ordered corner list and row LUT (jni/KeyFrame.cc:43-49) without ordered atomics or barriers.
 //   k_score / k_nonmax   compute_fast_score_old + nonmax_suppression, one lane per corner.
 //   k_candidates / k_thin_candidates   MakeKeyFrame_Rest's Shi-Tomasi candidates (jni/KeyFrame.cc:66-95) and
 //                 MapMaker::ThinCandidates (jni/MapMaker.cc:393-422), ordered block compaction.
 #include "vslam_internal.h"
+#include "fast_reject_dev.h"
 #include <stdlib.h>
 #include <stdio.h>
 
@@ -246,13 +247,15 @@ __global__ __launch_bounds__(FE_THREADS) void k_fast_lvl(FeArgs a) {
 // 1..3 from the same registers (2x2 sums by v_perm + v_sad_u8) with lane-contiguous stores.
 // Quick reject (cvfast.cpp:6088-9241 as a filter): ten contiguous ring pixels contain two ADJACENT compass pixels
 // (0, 4, 8, 12), so a corner has such a pair both brighter than c + t or both darker than c - t.  ~2 % of the pixels of the
-// feeder's frames pass (0.4 % are corners).  Every seven rows a wavefront compacts its survivors (prefix sum of the lanes'
+// feeder's frames pass (0.4 % are corners).  Every eight rows a wavefront compacts its survivors (prefix sum of the lanes'
 // bit counts) into its own LDS list and runs the full 16-pixel run-of-10 test on them with dense lanes, the ring read back
-// through L1/L2 as aligned dwords; corners are OR-ed into the workgroup's mask words in LDS, which leave with coalesced
+// through L1/L2, 12 bytes per ring row; corners are OR-ed into the workgroup's mask words in LDS, which leave with coalesced
 // stores together with the row counts.  A workgroup owns 256 / (w / 16) whole strips-rows ("bands") of consecutive frames.
 #define SL_RMAX 64         // most rows of a strip; the height R (a multiple of 8: the three halvings stay inside a strip) is chosen per launch
 #define SL_THREADS 256
 #define SL_CAP 1024        // entries of a wavefront's candidate list (one row of a wavefront: 64 lanes x 16 pixels)
+#define SL_RING 8          // row steps per round of the strip loop = named register sets of the window: its seven rows plus the one in flight
+#define SL_AHEAD (SL_RING - 7)
 
 struct SlArgs {
   int w16[NLEV], nb[NLEV], bpw[NLEV], wg_first[NLEV + 1];   // strips per row, bands per frame, bands per workgroup, first workgroup of a level
@@ -267,19 +270,33 @@ DEVFN unsigned sl_half2(unsigned wa, unsigned wb) {
 }
 DEVFN unsigned sl_half4(unsigned a0, unsigned a1, unsigned b0, unsigned b1) { return sl_half2(a0, b0) | (sl_half2(a1, b1) << 16); }
 
-// full segment test of pixel (x, y) of an image read through the caches: per ring row the aligned dwords around x - 3
+// full segment test of pixel (x, y) of an image read through the caches: per ring row ONE 12-byte load that covers x - 3 .. x + 3.
+// It starts at the aligned dword xb that holds x - 3, or one dword earlier where xb + 12 would pass the end of the row (x - 3 then
+// lies in the row's last two dwords and the ring ends inside them), so nothing beyond the row's w pixels is ever read.  One address
+// per row instead of two leaves the registers, beside the strip's window, to have all seven loads in flight together.
+struct __attribute__((packed, aligned(4))) SlRow3 { unsigned x, y, z; };
 DEVFN bool sl_full_test(const uint8_t* img, int pitch, int w, int x, int y, int thr) {
   const int xb = (x - 3) & ~3, o = (x - 3) & 3;
-  const int x2 = min(xb + 8, w - 4);                                 // the third dword is only needed (and then inside the row) when o >= 2
-  unsigned A[7], B[7];
-  const uint8_t* r = img + (size_t)(y - 3) * pitch;
+  const int xl = min(xb, w - 12);                                    // w >= 16
+  const bool late = xl != xb;                                        // x - 3 is in the load's second dword
+  unsigned A[7], B[7], v0[7], v1[7], v2[7];
+  const uint8_t* r = img + (size_t)(y - 3) * pitch + xl;
 #pragma unroll
   for (int k = 0; k < 7; k++) {
-    const uint2 v = *(const uint2*)(r + xb);
-    const unsigned t = *(const unsigned*)(r + x2);
-    A[k] = __builtin_amdgcn_alignbyte(v.y, v.x, o);                  // pixels x-3 .. x
-    B[k] = __builtin_amdgcn_alignbyte(t, v.y, o);                    // pixels x+1 .. x+4
+    const SlRow3 v = *(const SlRow3*)r;
+    v0[k] = v.x; v1[k] = v.y; v2[k] = v.z;
     r += pitch;
+  }
+  // All 21 dwords are live here, so the loads are issued together and cost one round trip.  Left to itself the scheduler, short of
+  // registers beside the strip's window, waits for the first rows before it asks for the last.
+  asm volatile("" : "+v"(v0[0]), "+v"(v0[1]), "+v"(v0[2]), "+v"(v0[3]), "+v"(v0[4]), "+v"(v0[5]), "+v"(v0[6]),
+                    "+v"(v1[0]), "+v"(v1[1]), "+v"(v1[2]), "+v"(v1[3]), "+v"(v1[4]), "+v"(v1[5]), "+v"(v1[6]));
+  asm volatile("" : "+v"(v2[0]), "+v"(v2[1]), "+v"(v2[2]), "+v"(v2[3]), "+v"(v2[4]), "+v"(v2[5]), "+v"(v2[6]));
+#pragma unroll
+  for (int k = 0; k < 7; k++) {
+    const unsigned lo = late ? v1[k] : v0[k], mid = late ? v2[k] : v1[k];
+    A[k] = __builtin_amdgcn_alignbyte(mid, lo, o);                   // pixels x-3 .. x
+    B[k] = __builtin_amdgcn_alignbyte(v2[k], mid, o);                // pixels x+1 .. x+4 (x+4 is not on the ring: when late, o < 2 and it is a byte of mid or any byte)
   }
   const int c = (A[3] >> 24) & 255u, cb = c + thr, c_b = c - thr;
   unsigned mb = 0, md = 0;                                          // ring pixel k -> bit k: the sign bits of cb - v / v - c_b are shifted in, k = 15 first
@@ -322,106 +339,96 @@ __global__ __launch_bounds__(SL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
   if (!active) xvalid = 0;
   const bool eL = active && lane == 0 && cg > 0, eR = active && lane == 63 && cg < W16 - 1;
 
-  auto load_row = [&](int i, uint4& v, unsigned& vl, unsigned& vr) {  // row step i of the strip: image row yb - 3 + i
-    const int y = yb - HALO + i;
-    v = make_uint4(0, 0, 0, 0); vl = 0; vr = 0;
-    if (active && i < SL_NSTEP && y >= 0 && y < h) {
-      const uint8_t* p = base + (size_t)y * pitch;
-      v = *(const uint4*)p;
-      if (eL) vl = *(const unsigned*)(p - 4);
-      if (eR) vr = *(const unsigned*)(p + 16);
-    }
+  // Row step i of the strip (image row yb - 3 + i) straight into the window slot it is read from.  The address is clamped into the
+  // image: a row outside it is never consumed (the pyramid and the quick reject test their own row against h below), so no register
+  // is cleared.  r[0] / r[5] are loaded by the edge lanes of a wavefront only; the other lanes take theirs from their neighbours.
+  auto load_row = [&](int i, unsigned (&r)[6]) {
+    const int y = min(max(yb - HALO + i, 0), h - 1);
+    const uint8_t* p = base + (size_t)y * pitch;
+    const uint4 v = *(const uint4*)p;
+    r[1] = v.x; r[2] = v.y; r[3] = v.z; r[4] = v.w;
+    if (eL) r[0] = *(const unsigned*)(p - 4);
+    if (eR) r[5] = *(const unsigned*)(p + 16);
   };
-  unsigned W[7][6];                                                  // the window: slot = row step % 7; [0] left neighbour dword, [1..4] own, [5] right
+  // The window and the prefetch are one ring of SL_RING named register sets: seven rows of window and one row in flight.  Row step i
+  // lives in slot i % 8 from its load to its last use as row y - 3, and the loop is unrolled by 8, so the ring closes and no row is
+  // ever copied; a strip is a multiple of 8 rows, so which pyramid rows a step closes is known when it is compiled.
+  // (Two rows in flight, a ring of 9, bought nothing: the row is waited for at the end of the step that asked for it either way, and
+  // its six registers more left the full test too few to have its loads in flight together.)
+  // Per slot: [0] left neighbour dword, [1..4] own, [5] right neighbour.
+  unsigned W[SL_RING][6];
 #pragma unroll
-  for (int u = 0; u < 7; u++)
+  for (int u = 0; u < SL_RING; u++) W[u][0] = W[u][5] = 0;           // [1..4] are loaded before they are read
 #pragma unroll
-    for (int k = 0; k < 6; k++) W[u][k] = 0;
-  uint4 pf0, pf1; unsigned pl0, pr0, pl1, pr1;
-  load_row(0, pf0, pl0, pr0);
-  load_row(1, pf1, pl1, pr1);
+  for (int k = 0; k < SL_AHEAD; k++) load_row(k, W[k]);
   unsigned l1p[2] = {0, 0}, l2p = 0;                                 // pyramid pieces waiting for their second row
 
-  for (int i0 = 0; i0 < SL_NSTEP; i0 += 7) {
-    unsigned pw[4] = {0, 0, 0, 0};                                   // quick-reject survivors of this round: 16 bits per row
+  for (int i0 = 0; i0 < SL_NSTEP; i0 += SL_RING) {
+    unsigned pw[(SL_RING + 1) / 2];                                  // quick-reject survivors of this round: 16 bits per row
 #pragma unroll
-    for (int u = 0; u < 7; u++) {
+    for (int k = 0; k < (SL_RING + 1) / 2; k++) pw[k] = 0;
+#pragma unroll
+    for (int u = 0; u < SL_RING; u++) {
       const int i = i0 + u;
       if (i >= SL_NSTEP) continue;
-      const uint4 cur = pf0; const unsigned cl = pl0, cr = pr0;
-      pf0 = pf1; pl0 = pl1; pr0 = pr1;
-      load_row(i + 2, pf1, pl1, pr1);
-      unsigned nl = __shfl_up(cur.w, 1), nr = __shfl_down(cur.x, 1);
-      if (lane == 0) nl = cl;
-      if (lane == 63) nr = cr;
-      W[u][0] = nl; W[u][1] = cur.x; W[u][2] = cur.y; W[u][3] = cur.z; W[u][4] = cur.w; W[u][5] = nr;
+      load_row(i + SL_AHEAD, W[(u + SL_AHEAD) % SL_RING]);
+      const unsigned nl = __shfl_up(W[u][4], 1), nr = __shfl_down(W[u][1], 1);
+      if (lane != 0) W[u][0] = nl;
+      if (lane != 63) W[u][5] = nr;
       if (PYR) {                                                     // jni/KeyFrame.cc:19-23 (2:1 area filter)
         const int rb = i - HALO, y = yb + rb;                        // row of the band
         if (active && rb >= 0 && rb < SL_R && y < h && (rb & 1)) {
-          const int up = (u + 6) % 7;
+          const int up = (u + SL_RING - 1) % SL_RING;
           const unsigned o0 = sl_half4(W[up][1], W[up][2], W[u][1], W[u][2]), o1 = sl_half4(W[up][3], W[up][4], W[u][3], W[u][4]);
           if ((y >> 1) < a.h[1]) *(uint2*)(a.lvl[1] + (size_t)s * a.lvl_sstride[1] + (size_t)(y >> 1) * a.lvl_pitch[1] + cg * 8) = make_uint2(o0, o1);
           if ((rb & 3) == 3) {
             const unsigned o2 = sl_half4(l1p[0], l1p[1], o0, o1);
             if ((y >> 2) < a.h[2]) *(unsigned*)(a.lvl[2] + (size_t)s * a.lvl_sstride[2] + (size_t)(y >> 2) * a.lvl_pitch[2] + cg * 4) = o2;
             if ((rb & 7) == 7) {
-              if ((y >> 3) < a.h[3]) *(unsigned short*)(a.lvl[3] + (size_t)s * a.lvl_sstride[3] + (size_t)(y >> 3) * a.lvl_pitch[3] + cg * 2) = (unsigned short)sl_half2(l2p, o2);
+              int s3 = s;                                            // opaque: the level-3 slot's address is worked out here, once in eight rows, not kept in two registers all along
+              asm volatile("" : "+v"(s3));
+              if ((y >> 3) < a.h[3]) *(unsigned short*)(a.lvl[3] + (size_t)s3 * a.lvl_sstride[3] + (size_t)(y >> 3) * a.lvl_pitch[3] + cg * 2) = (unsigned short)sl_half2(l2p, o2);
             } else l2p = o2;
           } else { l1p[0] = o0; l1p[1] = o1; }
         }
       }
-      // quick reject on the centre row (row step i - 3 = slot (u + 4) % 7): band row rel = i - 6
+      // quick reject on the centre row (row step i - 3): band row rel = i - 6.  Row y + 3 is slot u, row y - 3 row step i - 6.
       const int rel = i - 2 * HALO, yc = yb + rel;
       if (rel >= 0 && yc >= HALO && yc < h - HALO) {                  // uniform but for yc (per band)
-        const int sc = (u + 4) % 7, sd = (u + 1) % 7;             // centre, row y - 3; row y + 3 is slot u
-        // branch-free: a pair of adjacent compass pixels both above c + t  <=>  min(max(p0, p8), max(p4, p12)) - c > t, both
-        // below c - t  <=>  c - max(min(p0, p8), min(p4, p12)) > t; the sign of t - max(...) is shifted into the row's bit word
-        unsigned pass = 0;
-#pragma unroll
-        for (int d = 3; d >= 0; d--) {
-          const unsigned cw = W[sc][1 + d], uw = W[u][1 + d], dw = W[sd][1 + d];
-          const unsigned p12w = __builtin_amdgcn_alignbyte(cw, W[sc][d], 1);        // pixels x-3 .. x
-          const unsigned p4w = __builtin_amdgcn_alignbyte(W[sc][2 + d], cw, 3);     // pixels x+3 .. x+6
-#pragma unroll
-          for (int j = 3; j >= 0; j--) {
-            const int c = (cw >> (8 * j)) & 255u;
-            const int p0 = (uw >> (8 * j)) & 255u, p8 = (dw >> (8 * j)) & 255u;
-            const int p4 = (p4w >> (8 * j)) & 255u, p12 = (p12w >> (8 * j)) & 255u;
-            const int bm = min(max(p0, p8), max(p4, p12)), dm = max(min(p0, p8), min(p4, p12));
-            const int v = max(bm - c, c - dm);
-            pass = __builtin_amdgcn_alignbit(pass, (unsigned)(thr - v), 31);
-          }
-        }
-        pass &= xvalid;
+        const int sc = (u + SL_RING - 3) % SL_RING, sd = (u + SL_RING - 6) % SL_RING;
+        const unsigned pass = fast_reject16(W[sc], W[u], W[sd], thr) & xvalid;   // two pixels per instruction, fast_reject_dev.h
         pw[u >> 1] |= pass << (16 * (u & 1));
       }
     }
     // ---- the round's survivors: compact per wavefront, full test on dense lanes ----
     const int relg = i0 - 2 * HALO;                                  // band row of the round's slot 0
-    int cnt = __popc(pw[0]) + __popc(pw[1]) + __popc(pw[2]) + __popc(pw[3]);
+    int cnt = 0;
+#pragma unroll
+    for (int k = 0; k < (SL_RING + 1) / 2; k++) cnt += __popc(pw[k]);
     const int tot = wave_sum(cnt);
 #ifdef VSLAM_SL_SKIP_FLUSH
     if (tot != 123456) continue;
 #endif
     if (tot == 0) continue;
-    const int nsub = tot <= SL_CAP ? 1 : 7;                          // a round that overflows the list goes row by row
+    const int nsub = tot <= SL_CAP ? 1 : SL_RING;                    // a round that overflows the list goes row by row
     for (int sub = 0; sub < nsub; sub++) {
-      unsigned m4[4] = {pw[0], pw[1], pw[2], pw[3]};
-      if (nsub > 1) {
+      unsigned m4[(SL_RING + 1) / 2];
+      int c4 = 0;
 #pragma unroll
-        for (int k = 0; k < 4; k++) m4[k] = (sub >> 1) == k ? (pw[k] & (0xFFFFu << (16 * (sub & 1)))) : 0u;
+      for (int k = 0; k < (SL_RING + 1) / 2; k++) {
+        m4[k] = nsub == 1 ? pw[k] : ((sub >> 1) == k ? (pw[k] & (0xFFFFu << (16 * (sub & 1)))) : 0u);
+        c4 += __popc(m4[k]);
       }
-      const int c4 = __popc(m4[0]) + __popc(m4[1]) + __popc(m4[2]) + __popc(m4[3]);
       int inc = c4;
       for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(inc, d); if (lane >= d) inc += t; }
       const int n = __shfl(inc, 63);
       int pos = inc - c4;
 #pragma unroll
-      for (int k = 0; k < 4; k++) {
+      for (int k = 0; k < (SL_RING + 1) / 2; k++) {
         unsigned m = m4[k];
         while (m) {
           const int bit = __ffs((int)m) - 1;
-          list[pos++] = (unsigned short)((lane << 7) | (k * 32 + bit));
+          list[pos++] = (unsigned short)((lane << 8) | (k * 32 + bit));   // lane, row of the round, column
           m &= m - 1;
         }
       }
@@ -429,8 +436,8 @@ __global__ __launch_bounds__(SL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
       __builtin_amdgcn_wave_barrier();
       for (int k = lane; k < n; k += 64) {
         const int e = list[k];
-        const int4 t = tb[wave * 64 + (e >> 7)];
-        const int rr = relg + ((e >> 4) & 7), x = t.z + (e & 15), y = t.y + rr;
+        const int4 t = tb[wave * 64 + (e >> 8)];
+        const int rr = relg + ((e >> 4) & 15), x = t.z + (e & 15), y = t.y + rr;
 #ifdef VSLAM_SL_SKIP_FULL
         if (x == 7 && y == 7)
 #else
@@ -460,58 +467,83 @@ __global__ __launch_bounds__(SL_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4
   }
 }
 
-// Raster-ordered corner lists + row LUT from the corner bit-masks, one workgroup per (band of 16 rows, level, stream): the
-// workgroup adds the row counts above its band (its list offset = lut of its first row), scans the popcounts of its band's
-// mask words (word index = row * nchunk + chunk, i.e. raster order) and every thread expands its words at its scanned
-// offset -> the list is bit-exactly the reference's push_back order (cvfast.cpp:9237-9238) with no ordered atomics;
-// lut[y] is the offset of the first word of row y (jni/KeyFrame.cc:43-49).  (One workgroup per (level, stream) walking the
-// whole level was the fourth largest kernel of the path: the level-0 workgroup did nearly all the work.)
+// Raster-ordered corner lists + row LUT from the corner bit-masks, one WAVEFRONT per (band of rows, level, stream) and no barrier: the
+// wavefront adds the row counts above its band (its list offset = lut of its first row; the loads are issued together, four per lane
+// and trip), scans the popcounts of its band's mask words (word index = row * nchunk + chunk, i.e. raster order; a lane owns one to
+// four consecutive words) and every lane expands its words at its scanned offset -> the list is bit-exactly the reference's push_back
+// order (cvfast.cpp:9237-9238) with no ordered atomics; lut[y] is the offset of the first word of row y (jni/KeyFrame.cc:43-49).
+// The grid's x counts the bands the four levels really have (CpArgs::first), four to a workgroup whose wavefronts never meet.
+// (A workgroup of four wavefronts per band of level-0 height spent 63 % of its cycles waiting at its four barriers, and three quarters
+// of the workgroups of levels 1..3 returned at once; one workgroup per (level, stream) walking the whole level was slower still.)
 #define COMPACT_THREADS 256
-__global__ __launch_bounds__(COMPACT_THREADS) void k_compact(FeArgs a, int cband /* rows per workgroup */) {
-  __shared__ int wsum[COMPACT_THREADS / 64];
-  __shared__ int sh_above;
-  const int b = blockIdx.x, l = blockIdx.y, s = fe_stream_of(a, blockIdx.z);
+#define COMPACT_WORDS 256   // most mask words of a band: four per lane
+struct CpArgs {
+  int first[NLEV + 1];      // first band of each level in the grid's x order, [NLEV] = all bands
+  int rows[NLEV];           // rows per band: COMPACT_WORDS / nchunk, so 4 (4096 pixels wide, 64 words a row) to 256
+};
+static CpArgs fe_compact_args(const FeArgs& a) {
+  CpArgs c;
+  c.first[0] = 0;
+  for (int l = 0; l < NLEV; l++) {
+    c.rows[l] = COMPACT_WORDS / a.nchunk[l];                        // nchunk <= 64: vslam_create accepts no level wider than 4096
+    c.first[l + 1] = c.first[l] + (a.h[l] + c.rows[l] - 1) / c.rows[l];
+  }
+  return c;
+}
+static dim3 fe_compact_grid(const CpArgs& c, int S) { return dim3((c.first[NLEV] + COMPACT_THREADS / 64 - 1) / (COMPACT_THREADS / 64), S); }
+
+__global__ __launch_bounds__(COMPACT_THREADS) void k_compact(FeArgs a, CpArgs q) {
+  const int lane = threadIdx.x & 63;
+  const int gb = (int)blockIdx.x * (COMPACT_THREADS / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (gb >= q.first[NLEV]) return;
+  int l = 0;
+  if (gb >= q.first[1]) l = 1;
+  if (gb >= q.first[2]) l = 2;
+  if (gb >= q.first[3]) l = 3;
+  const int s = fe_stream_of(a, blockIdx.y);
   const int h = a.h[l], nchunk = a.nchunk[l], cap = a.cap[l];
-  const int y0 = b * cband;
-  if (y0 >= h) return;
-  const int nrows = min(cband, h - y0);
+  const int y0 = (gb - q.first[l]) * q.rows[l];
+  const int nrows = min(q.rows[l], h - y0);
   const int* rc = a.rowcnt[l] + (size_t)s * h;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int above = 0;
-  for (int y = threadIdx.x; y < y0; y += COMPACT_THREADS) above += rc[y];
-  above = wave_sum(above);
-  if (lane == 0) wsum[wave] = above;
-  __syncthreads();
-  if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < COMPACT_THREADS / 64; w++) t += wsum[w]; sh_above = t; }
-  __syncthreads();
-  const int first = sh_above;
   const int nw = nrows * nchunk;
   const unsigned long long* cm = a.cmask[l] + ((size_t)s * h + y0) * nchunk;
   uint32_t* out = a.corners[l] + (size_t)s * cap;
   int* lut = a.rowlut[l] + (size_t)s * (h + 1);
-  const int per = (nw + COMPACT_THREADS - 1) / COMPACT_THREADS;
-  const int lo = min((int)threadIdx.x * per, nw), hi = min(lo + per, nw);
+  int above = 0;
+  for (int y = lane; y < y0; y += 256) {                            // the row counts above the band, four loads in flight per lane
+    const int r0 = rc[y], r1 = y + 64 < y0 ? rc[y + 64] : 0, r2 = y + 128 < y0 ? rc[y + 128] : 0, r3 = y + 192 < y0 ? rc[y + 192] : 0;
+    above += (r0 + r1) + (r2 + r3);
+  }
+  const int per = (nw + 63) >> 6;                                    // 1..4 consecutive words per lane
+  const int lo = min(lane * per, nw), hi = min(lo + per, nw);
+  unsigned long long m[COMPACT_WORDS / 64];
   int cnt = 0;
-  for (int i = lo; i < hi; i++) cnt += __popcll(cm[i]);
+#pragma unroll
+  for (int k = 0; k < COMPACT_WORDS / 64; k++) {
+    m[k] = lo + k < hi ? cm[lo + k] : 0ull;
+    cnt += __popcll(m[k]);
+  }
+  const int first = wave_sum(above);
   int inc = cnt;
   for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(inc, d); if (lane >= d) inc += v; }
-  __syncthreads();
-  if (lane == 63) wsum[wave] = inc;
-  __syncthreads();
-  int base = first + inc - cnt, total = first;
-  for (int w = 0; w < COMPACT_THREADS / 64; w++) { if (w < wave) base += wsum[w]; total += wsum[w]; }
-  for (int i = lo; i < hi; i++) {
-    unsigned long long m = cm[i];
-    const int rr = i / nchunk, c = i - rr * nchunk, y = y0 + rr;
-    if (c == 0) lut[y] = min(base, cap);
-    while (m) {
-      const int bit = __ffsll((long long)m) - 1;
-      if (base < cap) out[base] = (uint32_t)((c << 6) + bit) | ((uint32_t)y << 16);
-      base++;
-      m &= m - 1;
+  int pos = first + inc - cnt;
+  const int total = first + __shfl(inc, 63);
+  int y = y0 + lo / nchunk, c = lo - (lo / nchunk) * nchunk;         // row and chunk of the lane's first word
+#pragma unroll
+  for (int k = 0; k < COMPACT_WORDS / 64; k++) {
+    if (lo + k >= hi) break;
+    if (c == nchunk) { c = 0; y++; }
+    if (c == 0) lut[y] = min(pos, cap);
+    unsigned long long mm = m[k];
+    while (mm) {
+      const int bit = __ffsll((long long)mm) - 1;
+      if (pos < cap) out[pos] = (uint32_t)((c << 6) + bit) | ((uint32_t)y << 16);
+      pos++;
+      mm &= mm - 1;
     }
+    c++;
   }
-  if (threadIdx.x == 0 && y0 + nrows == h) {                         // the last band of the level closes the list
+  if (lane == 0 && y0 + nrows == h) {                                // the last band of the level closes the list
     lut[h] = min(total, cap);
     a.ncorners[s * NLEV + l] = min(total, cap);
     if (total > cap) *a.overflow = 1;
@@ -960,8 +992,8 @@ int fe_make_keyframe_lite(vslam_system* sys, const uint8_t* gray, size_t row_str
   }
   prof_mark(sys, PROF_COMPACT);
   if (S > 0) {
-    static const int cb = getenv("VSLAM_COMPACT_BAND") ? atoi(getenv("VSLAM_COMPACT_BAND")) : 32;   // rows of a level per workgroup of the compaction (measured alone, 1024 frames: 16 rows 96 us, 32: 62, 64: 96, 128: 78, 256: 156)
-    hipLaunchKernelGGL(k_compact, dim3((g[0].h + cb - 1) / cb, NLEV, S), dim3(COMPACT_THREADS), 0, fs, a, cb);
+    const CpArgs cp = fe_compact_args(a);
+    hipLaunchKernelGGL(k_compact, fe_compact_grid(cp, S), dim3(COMPACT_THREADS), 0, fs, a, cp);
   }
   if (sys->p.use_sbi) {                                           // jni/Tracker.cc:86-97, 104-105
     const FrameDev& last = sys->have_sbi ? sys->frbuf[b ^ 1] : sys->fr;
@@ -1096,7 +1128,8 @@ int fe_keyframe_corners(vslam_system* sys, int s, int kf) {
   a.ncorners = scr.ncorners; a.overflow = scr.overflow; a.list = nullptr;
   a.in = a.lvl[0]; a.in_sstride = 0; a.in_pitch = g[0].pitch;
   { const int r = fe_launch_bands(sys, a, sys->stream, 1, false); if (r) return r; }
-  hipLaunchKernelGGL(k_compact, dim3((g[0].h + BAND - 1) / BAND, NLEV, 1), dim3(COMPACT_THREADS), 0, sys->stream, a, BAND);
+  const CpArgs cp = fe_compact_args(a);
+  hipLaunchKernelGGL(k_compact, fe_compact_grid(cp, 1), dim3(COMPACT_THREADS), 0, sys->stream, a, cp);
   uint32_t* d[NLEV];
   for (int l = 0; l < NLEV; l++) d[l] = sys->map.kf_corners[l] + ((size_t)s * K + kf) * sys->tp.kcap[l];
   hipLaunchKernelGGL(k_store_kf_corners, dim3(NLEV), dim3(256), 0, sys->stream, scr.corners[0], scr.corners[1], scr.corners[2], scr.corners[3], scr.ncorners,
