@@ -153,6 +153,41 @@ int orc_sys_get_template(void* sv, int pt, uint8_t* tmpl, int* sum, int* sumsq, 
 int orc_sys_bundle_adjust_recent(void* sv) { System* s = (System*)sv; const int r = s->BundleAdjustRecent(); s->HandleBadPoints(); return r; }
 int orc_sys_bundle_adjust_all(void* sv) { System* s = (System*)sv; const int r = s->BundleAdjustAll(); s->HandleBadPoints(); return r; }
 
+// ---- what the map-maker keeps beside the map (tests/mapmaker_cases.py) --------------------------------------
+int orc_sys_get_failure_queue(void* sv, int* kf_pt, int cap) {
+  System* s = (System*)sv;
+  int n = 0;
+  for (auto& e : s->failure_queue) { if (n < cap) { kf_pt[2 * n] = e.first; kf_pt[2 * n + 1] = e.second; } n++; }
+  return n;
+}
+// per point: |sMeasurementKFs| and sNeverRetryKFs as a 128-bit set (two words, bit k = keyframe k)
+int orc_sys_get_point_mapmaker_data(void* sv, int* n_meas_kfs, unsigned long long* never_retry2, int cap) {
+  System* s = (System*)sv;
+  const int n = (int)s->pts.size();
+  for (int i = 0; i < n && i < cap; i++) {
+    n_meas_kfs[i] = (int)s->pts[i]->meas_kfs.size();
+    never_retry2[2 * i] = never_retry2[2 * i + 1] = 0ull;
+    for (int k : s->pts[i]->never_retry) if (k >= 0 && k < 128) never_retry2[2 * i + (k >> 6)] |= 1ull << (k & 63);
+  }
+  return n;
+}
+void orc_sys_get_converged(void* sv, int out[2]) { System* s = (System*)sv; out[0] = s->ba_converged_recent; out[1] = s->ba_converged_full; }
+// bBad and the tracker's M-estimator counts of a point, which no upload sets
+void orc_sys_set_point_flags(void* sv, int pt, int bad, int n_in, int n_out) {
+  MapPoint& p = *((System*)sv)->pts[pt]; p.bad = bad != 0; p.n_inlier = n_in; p.n_outlier = n_out;
+}
+double orc_sys_keyframe_linear_dist(void* sv, int a, int b) { System* s = (System*)sv; return s->KeyFrameLinearDist(s->kfs[a]->pose, s->kfs[b]->pose); }
+// the last problem of BundleAdjust: info = {BundleAdjust calls so far, cameras, adjusted cameras, points, measurements, outliers, return value of
+// Compute, points made bad part-way through the outlier walk}; the arrays (each may be null) hold what their capacity allows
+void orc_sys_get_last_problem(void* sv, int info[8], int* cam_kf, int cam_cap, int* point_id, int point_cap, int* outlier_kf_pt, int outlier_cap) {
+  const System::LastProblem& L = ((System*)sv)->last_problem;
+  info[0] = L.n_runs; info[1] = (int)L.id_view.size(); info[2] = L.n_adj; info[3] = (int)L.id_point.size(); info[4] = L.n_meas;
+  info[5] = (int)L.outliers.size(); info[6] = L.accepted; info[7] = L.n_bad_mid_walk;
+  for (int i = 0; cam_kf && i < (int)L.id_view.size() && i < cam_cap; i++) cam_kf[i] = L.id_view[i];
+  for (int i = 0; point_id && i < (int)L.id_point.size() && i < point_cap; i++) point_id[i] = L.id_point[i];
+  for (int i = 0; outlier_kf_pt && i < (int)L.outliers.size() && i < outlier_cap; i++) { outlier_kf_pt[2 * i] = L.outliers[i].first; outlier_kf_pt[2 * i + 1] = L.outliers[i].second; }
+}
+
 // ---- stand-alone Bundle ------------------------------------------------------------------------------------
 void* orc_ba_create(const double cam5[5], int width, int height, int quirks, int max_iterations, double convergence_limit, double min_sigma) {
   Bundle* b = new Bundle;

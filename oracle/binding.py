@@ -388,6 +388,48 @@ class OracleSystem:
     def bundle_adjust_all(self):
         return self.L.orc_sys_bundle_adjust_all(self.h)
 
+    # ---- what the map-maker keeps beside the map ----
+    def failure_queue(self, cap=16384):
+        """-> the failure queue's (keyframe, point) entries in queue order"""
+        out = np.zeros((cap, 2), np.int32)
+        n = self.L.orc_sys_get_failure_queue(self.h, _p(out), cap)
+        assert n <= cap
+        return out[:n]
+
+    def point_mapmaker_data(self):
+        """-> per point: the size of sMeasurementKFs, and sNeverRetryKFs as two 64-bit words (bit k = keyframe k)"""
+        n = self.state().n_points
+        nm, nr = np.zeros(n, np.int32), np.zeros((n, 2), np.uint64)
+        self.L.orc_sys_get_point_mapmaker_data(self.h, _p(nm), _p(nr), n)
+        return {"n_meas_kfs": nm, "never_retry": nr}
+
+    def converged(self):
+        """-> (mbBundleConverged_Recent, mbBundleConverged_Full)"""
+        o = np.zeros(2, np.int32)
+        self.L.orc_sys_get_converged.restype = None
+        self.L.orc_sys_get_converged(self.h, _p(o))
+        return int(o[0]), int(o[1])
+
+    def set_point_flags(self, pt, bad, n_in, n_out):
+        self.L.orc_sys_set_point_flags.restype = None
+        self.L.orc_sys_set_point_flags(self.h, int(pt), int(bad), int(n_in), int(n_out))
+
+    def keyframe_linear_dist(self, a, b):
+        self.L.orc_sys_keyframe_linear_dist.restype = C.c_double
+        return self.L.orc_sys_keyframe_linear_dist(self.h, int(a), int(b))
+
+    def last_problem(self):
+        """the last problem BundleAdjust built, in map indices: the adjusted and the fixed keyframes (camera-id order), the map points
+        (point-id order), the measurement count, Compute's return value, the outlier list as (keyframe, point) in list order, and the
+        number of points an outlier entry made bad after an earlier entry of the same list had erased a measurement of theirs"""
+        self.L.orc_sys_get_last_problem.restype = None
+        info = np.zeros(8, np.int32)
+        self.L.orc_sys_get_last_problem(self.h, _p(info), None, 0, None, 0, None, 0)
+        cams, pts, outl = np.zeros(max(int(info[1]), 1), np.int32), np.zeros(max(int(info[3]), 1), np.int32), np.zeros((max(int(info[5]), 1), 2), np.int32)
+        self.L.orc_sys_get_last_problem(self.h, _p(info), _p(cams), len(cams), _p(pts), len(pts), _p(outl), len(outl))
+        return {"runs": int(info[0]), "adjusted": cams[:info[2]].tolist(), "fixed": cams[info[2]:info[1]].tolist(), "points": pts[:info[3]].copy(),
+                "n_meas": int(info[4]), "accepted": int(info[6]), "outliers": outl[:info[5]].copy(), "bad_mid_walk": int(info[7])}
+
 
 class OracleBundle:
     """jni/Bundle.h:111-121 surface of the oracle."""

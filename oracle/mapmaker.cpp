@@ -104,7 +104,12 @@ int System::BundleAdjust(const std::vector<int>& adj, const std::vector<int>& fi
   }
   abort_flag = false;
   pb->recent = recent;
+  last_problem.n_runs++;
+  last_problem.n_adj = (int)adj.size(); last_problem.n_meas = (int)b.meas.size();
+  last_problem.id_view = pb->id_view; last_problem.id_point = pb->id_point;
+  last_problem.outliers.clear(); last_problem.n_bad_mid_walk = 0;
   pb->accepted = b.Compute(&abort_flag);
+  last_problem.accepted = pb->accepted;
   const int acc = pb->accepted;
   if (defer_ba && p.ba_delay_frames > 0) { pb->countdown = p.ba_delay_frames; delete pending; pending = pb; return acc; }
   ApplyBundle(*pb);
@@ -126,11 +131,16 @@ void System::ApplyBundle(PendingBA& pb) {
     ba_converged_full = false;
   }
   if (b.converged) { ba_converged_recent = true; if (!recent) ba_converged_full = true; }   // :931-935
+  std::set<int> erased_here;                                                                       // (statistics only)
   for (auto& pc : b.outlier_meas) {                                                                 // :941-959
     const int pp = pb.id_point[pc.first], pk = pb.id_view[pc.second];
+    last_problem.outliers.push_back(std::make_pair(pk, pp));
     Measurement& m = kfs[pk]->meas[pp];
-    if ((int)pts[pp]->meas_kfs.size() <= 2 || m.source == SRC_ROOT) pts[pp]->bad = true;
-    else {
+    if ((int)pts[pp]->meas_kfs.size() <= 2 || m.source == SRC_ROOT) {
+      if (!pts[pp]->bad && erased_here.count(pp)) last_problem.n_bad_mid_walk++;
+      pts[pp]->bad = true;
+    } else {
+      erased_here.insert(pp);
       if (m.source == SRC_TRACKER || m.source == SRC_EPIPOLAR) failure_queue.push_back(std::make_pair(pk, pp));
       else pts[pp]->never_retry.insert(pk);
       kfs[pk]->meas.erase(pp);

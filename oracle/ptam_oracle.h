@@ -170,6 +170,17 @@ int orc_sys_get_grow_detail(void* sys, int* out6, int cap);
 int orc_sys_get_refind_log(void* sys, int* out8, int cap);
 int orc_sys_bundle_adjust_recent(void* sys);   /* MapMaker::BundleAdjustRecent, jni/MapMaker.cc:801-851 */
 int orc_sys_bundle_adjust_all(void* sys);      /* MapMaker::BundleAdjustAll,    jni/MapMaker.cc:776-798 */
+/* what the map-maker keeps beside the map: mvFailureQueue as (keyframe, point) pairs in queue order; per point |sMeasurementKFs| and
+ * sNeverRetryKFs as two 64-bit words (bit k = keyframe k); mbBundleConverged_Recent / _Full */
+int orc_sys_get_failure_queue(void* sys, int* kf_pt, int cap);
+int orc_sys_get_point_mapmaker_data(void* sys, int* n_meas_kfs, unsigned long long* never_retry2, int cap);
+void orc_sys_get_converged(void* sys, int out[2]);
+void orc_sys_set_point_flags(void* sys, int pt, int bad, int n_in, int n_out);   /* bBad, nMEstimatorInlierCount / OutlierCount: no upload sets them */
+double orc_sys_keyframe_linear_dist(void* sys, int a, int b);                   /* MapMaker::KeyFrameLinearDist, jni/MapMaker.cc:705-712 */
+/* the last problem BundleAdjust built, in map indices.  info = {BundleAdjust calls so far, cameras, adjusted cameras, points, measurements, outliers,
+ * Compute's return value, points an outlier entry made bad after an earlier entry of the list had erased a measurement of theirs}; cam_kf: camera id ->
+ * keyframe (the adjusted ones first), point_id: point id -> map point, outlier_kf_pt: (keyframe, point) in list order.  Arrays may be null. */
+void orc_sys_get_last_problem(void* sys, int info[8], int* cam_kf, int cam_cap, int* point_id, int point_cap, int* outlier_kf_pt, int outlier_cap);
 
 /* ---- SmallBlurryImage rotation prior (jni/SmallBlurryImage.cc, jni/Tracker.cc:885-893); third-party arithmetic restated, see sbi.cpp */
 /* MakeFromKF on a level-3 image: small image (w3/2 x h3/2) and the zero-mean blurred template; returns w | h << 16 */

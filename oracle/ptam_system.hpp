@@ -184,6 +184,14 @@ struct System {
   struct PendingBA { Bundle b; std::vector<int> id_view, id_point; bool recent = true; int accepted = 0; int countdown = -1; };
   PendingBA* pending = nullptr;
   void ApplyBundle(PendingBA& pb);
+  // the last problem BundleAdjust built and what ApplyBundle did with it, in map indices (what the map-maker's edge tests assert on)
+  struct LastProblem {
+    int n_runs = 0;                                  // BundleAdjust calls so far
+    int n_adj = 0, n_meas = 0, accepted = 0;
+    std::vector<int> id_view, id_point;              // camera id -> keyframe (the first n_adj adjusted, the rest the fixed set), point id -> map point
+    std::vector<std::pair<int,int>> outliers;        // (keyframe, map point) in the bundle's list order
+    int n_bad_mid_walk = 0;                          // points an outlier entry made bad after an earlier entry of this list had erased a measurement of theirs
+  } last_problem;
   bool defer_ba = false;
   bool abort_flag = false;
   // map bootstrap (bootstrap.cpp): Tracker::TrackForInitialMap and the trails (jni/Tracker.cc:247-346), MapMaker::InitFromStereo (jni/MapMaker.cc:204-376)

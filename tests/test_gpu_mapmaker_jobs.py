@@ -1,7 +1,9 @@
 """The two combinations of map-maker jobs that no other test reaches, as a characterisation of the map-maker's host driver
 (csrc/ba.hip): a host-driven AddKeyFrame beside the asynchronous map-maker, and a BundleAdjustAll that first has to collect an
 adjustment still in flight.  In both, a system with ba_delay_frames = 3 must leave the same bits as one with ba_delay_frames = 0:
-the kernels read the same map, only the stream they run on and the moment of the write-back differ."""
+the kernels read the same map, only the stream they run on and the moment of the write-back differ.
+The driver's kernels themselves (k_ba_select, k_ba_assemble, k_ba_writeback) are held to the oracle where they branch by
+tests/test_gpu_mapmaker_edges.py, on the hand-built maps of tests/mapmaker_cases.py."""
 import numpy as np
 import pytest
 

@@ -490,7 +490,8 @@ __global__ __launch_bounds__(64) void k_ba_select(MapDev m, TrackParams tp, BaPo
   } else if (want && all) {                                           // BundleAdjustAll :776-798
     int c = 0;
     for (int k = 0; k < nk; k++) if (!kff[k]) { view_of_kf[k] = c; v.cam_fixed[c] = 0; v.cam_pose[c] = kfp[k]; pool.id_view[(size_t)s * pool.max_cams + c] = k; c++; }
-    nadj_out = c; go = c > 0 && c <= 64;                            // the slot layout holds the adjustable cameras of a point in one 64-bit set
+    nadj_out = c; go = c <= 64;                                     // the slot layout holds the adjustable cameras of a point in one 64-bit set
+                                                                    // (c == 0, every keyframe fixed: the reference still adjusts the points, and so does k_ba_compute)
     if (c > 64) st->ba_accepted = -3;
   }
   // The pool record of a stream whose adjustment is pending belongs to that adjustment: its k_ba_assemble runs on a map-maker
