@@ -146,6 +146,14 @@ int vslam_eval_transcendental(int fn, int n, const double* x, double* y, int on_
  *   pose12_out = exp(update6) * pose12. */
 int vslam_eval_select(int form, int n, const double* v, int k, double* out);
 int vslam_eval_pose_tail(const double* sums27, const double* pose12, double* update6, double* pose12_out);
+/* Self-test hook: the ATAN camera's arithmetic on its own (jni/ATANCamera.cc:31-91, 133-164, 198-231), as every projecting kernel reads
+ * it, for the calibration cam5 (as vslam_params.cam) of a width x height image.  xy: n image-plane points (x, y).  out17 receives
+ * 17 doubles per point: Project (im[2], r, factor, invalid as 0 / 1), GetProjectionDerivs [4] (row-major as stored: d00 d01 d10 d11),
+ * UnProject(im) [2], and the bootstrap's UnProject + GetProjectionDerivs at im (position [2], derivatives [4]).  derived5 receives
+ * what SetImageSize / RefreshParams / OnePixelDist derive: two_tan, winv, largest_radius, max_r, one_pixel_dist.  The points are
+ * evaluated by one 64-lane workgroup on the device or (on_host != 0) by the same functions compiled for the host; both must return
+ * the same bits. */
+int vslam_eval_camera(const double* cam5, int width, int height, int quirks, int n, const double* xy, double* out17, double* derived5, int on_host);
 
 /* ---- frame front-end ------------------------------------------------------------------- */
 

@@ -521,6 +521,20 @@ def cam_unproject(cam5, w, h, ix, iy):
     return out
 
 
+CAM_EVAL_FIELDS = {"im": slice(0, 2), "r": 2, "factor": 3, "invalid": 4, "derivs": slice(5, 9), "unproject": slice(9, 11), "boot_out": slice(11, 13), "boot_jac": slice(13, 17)}
+CAM_DERIVED = ("two_tan", "winv", "largest_radius", "max_r", "one_pixel_dist")
+
+
+def cam_eval(cam5, w, h, xy, quirks=0):
+    """The camera arithmetic over (n, 2) image-plane points in vslam_eval_camera's layout: ((n, 17) array, see CAM_EVAL_FIELDS;
+    the 5 derived values, see CAM_DERIVED)"""
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    out, der = np.zeros((len(xy), 17)), np.zeros(5)
+    L = lib(); L.orc_cam_eval.restype = None
+    L.orc_cam_eval(_p(_d(cam5)), int(w), int(h), int(quirks), len(xy), _p(xy), _p(out), _p(der))
+    return out, der
+
+
 def find_sigma_squared(est, v):
     L = lib(); L.orc_find_sigma_squared.restype = C.c_double
     v = _d(v)

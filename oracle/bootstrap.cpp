@@ -247,6 +247,23 @@ extern "C" void orc_boot_matches(const double cam5[5], int w, int h, const int* 
   }
 }
 
+// The camera arithmetic on its own, in the layout of vslam_eval_camera (include/vslam_c.h): per image-plane point 17 doubles
+// (Project: im[2], r, factor, invalid; GetProjectionDerivs [4]; UnProject(im) [2]; unproject_with_derivs(im): out[2], jac[4]) and what
+// RefreshParams / OnePixelDist derive (two_tan, winv, largest_radius, max_r, one_pixel_dist)
+namespace orc { double one_pixel_dist(const Camera& cam); }
+extern "C" void orc_cam_eval(const double cam5[5], int w, int h, int quirks, int n, const double* xy, double* out17, double derived5[5]) {
+  orc::Camera c; c.init(cam5, w, h, (quirks & ORC_Q_CAM_INT_RADIUS) != 0);
+  for (int i = 0; i < n; i++) {
+    double* o = out17 + 17 * i;
+    const orc::Camera::Proj p = c.project(xy[2 * i], xy[2 * i + 1]);
+    o[0] = p.im[0]; o[1] = p.im[1]; o[2] = p.r; o[3] = p.factor; o[4] = p.invalid ? 1.0 : 0.0;
+    c.derivs(p, o + 5);
+    c.unproject(p.im[0], p.im[1], o + 9);
+    orc::unproject_with_derivs(c, p.im[0], p.im[1], o + 11, o + 13);
+  }
+  derived5[0] = c.two_tan; derived5[1] = c.winv; derived5[2] = c.largest_radius; derived5[3] = c.max_r; derived5[4] = orc::one_pixel_dist(c);
+}
+
 extern "C" int orc_calc_plane_aligner_stages(const double* pos3, int n, unsigned seed, double out12[12], double best_mean[3], double best_normal[3]) {
   std::vector<orc::V3> pos((size_t)n);
   for (int i = 0; i < n; i++) pos[i] = orc::v3(pos3[3 * i], pos3[3 * i + 1], pos3[3 * i + 2]);

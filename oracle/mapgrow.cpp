@@ -82,7 +82,7 @@ V3 reproject_point(const SE3& AfromB, const double v2A[2], const double v2B[2]) 
 }
 
 // ATANCamera::OnePixelDist, jni/ATANCamera.cc:86-91
-static double one_pixel_dist(const Camera& cam) {
+double one_pixel_dist(const Camera& cam) {
   double a[2], b[2];
   cam.unproject(cam.size[0] / 2, cam.size[1] / 2, a);
   cam.unproject(cam.size[0] / 2 + 1, cam.size[1] / 2 + 1, b);

@@ -211,6 +211,8 @@ void orc_se3_exp(const double mu[6], double pose12[12]);
 void orc_se3_ln(const double pose12[12], double mu[6]);
 void orc_cam_project(const double cam5[5], int w, int h, int quirks, double cx, double cy, double im[2], double derivs[4], int* invalid, double* largest_radius);
 void orc_cam_unproject(const double cam5[5], int w, int h, double ix, double iy, double out[2]);
+/* the camera arithmetic per image-plane point and the derived values, laid out as vslam_eval_camera's (include/vslam_c.h) */
+void orc_cam_eval(const double cam5[5], int w, int h, int quirks, int n, const double* xy, double* out17, double derived5[5]);
 double orc_find_sigma_squared(int est, const double* v, int n);
 double orc_weight(int est, double e2, double s2);
 double orc_sqrt_weight(int est, double e2, double s2);

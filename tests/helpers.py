@@ -14,15 +14,17 @@ def oracle_corner_fn(thr=(10, 15, 15, 10), barrier=10):
     return fn
 
 
-def make_scene(w=640, h=480, seed=1234, n_frames=30, n_keyframes=8, noise=2, rects=None, **map_kw):
+def make_scene(w=640, h=480, seed=1234, n_frames=30, n_keyframes=8, noise=2, rects=None, cam=None, **map_kw):
     """rects: rectangles of the feeder's texture (VSLAM_FEEDER_NRECT; default 1000 ~ 1100 FAST corners at level 0 of 640x480,
-    1500 ~ 2000 at 1280x720 = BASELINE configs[3])"""
+    1500 ~ 2000 at 1280x720 = BASELINE configs[3]); cam: the calibration the scene is rendered and mapped at (default: the reference's)"""
     import os
     old = os.environ.get("VSLAM_FEEDER_NRECT")
     if rects:
         os.environ["VSLAM_FEEDER_NRECT"] = str(rects)
+    if cam is not None:
+        map_kw["cam"] = tuple(cam)
     try:
-        f = feeder.Feeder(w, h, seed=seed, noise=noise)
+        f = feeder.Feeder(w, h, seed=seed, noise=noise, **({} if cam is None else {"cam": tuple(cam)}))
     finally:
         if rects:
             if old is None:

@@ -12,19 +12,20 @@ def _rot(w):
     return np.eye(3) + np.sin(th) / th * K + (1 - np.cos(th)) / th ** 2 * K @ K
 
 
-def project(pose12, X, w=640, h=480):
+def project(pose12, X, w=640, h=480, cam=CAM):
     R, t = pose12[:9].reshape(3, 3), pose12[9:]
     c = R @ X + t
     x, y = c[0] / c[2], c[1] / c[2]
     r = np.hypot(x, y)
-    ww = CAM[4]
-    fac = 1.0 if r < 0.001 else np.arctan(r * 2 * np.tan(ww / 2)) / ww / r
-    return np.array([w * CAM[2] - 0.5 + w * CAM[0] * x * fac, h * CAM[3] - 0.5 + h * CAM[1] * y * fac]), c[2]
+    ww = cam[4]
+    fac = 1.0 if r < 0.001 or ww == 0.0 else np.arctan(r * 2 * np.tan(ww / 2)) / ww / r
+    return np.array([w * cam[2] - 0.5 + w * cam[0] * x * fac, h * cam[3] - 0.5 + h * cam[1] * y * fac]), c[2]
 
 
 def ba_scene(n_cams=5, n_pts=300, pixel_noise=0.5, outlier_frac=0.05, visibility=1.0, seed=0,
-             init_noise=(0.01, 0.5 * np.pi / 180, 0.02), n_fixed=1):
-    """n_cams cameras (camera 0 fixed) looking at n_pts points in a 2 x 2 x 0.5 box; init = truth + noise."""
+             init_noise=(0.01, 0.5 * np.pi / 180, 0.02), n_fixed=1, cam=CAM):
+    """n_cams cameras (camera 0 fixed) looking at n_pts points in a 2 x 2 x 0.5 box; init = truth + noise.  cam: the calibration the
+    measurements are projected with (640 x 480)."""
     rng = np.random.default_rng(seed)
     pts = np.stack([rng.uniform(-0.6, 0.6, n_pts), rng.uniform(-0.45, 0.45, n_pts), rng.uniform(-0.25, 0.25, n_pts)], 1)
     cams = []
@@ -38,7 +39,7 @@ def ba_scene(n_cams=5, n_pts=300, pixel_noise=0.5, outlier_frac=0.05, visibility
         for i in range(n_pts):
             if rng.uniform() > visibility:
                 continue
-            xy, z = project(cams[j], pts[i])
+            xy, z = project(cams[j], pts[i], cam=cam)
             if z <= 0.1 or not (5 < xy[0] < 635 and 5 < xy[1] < 475):
                 continue
             level = int(rng.integers(0, 4))

@@ -95,6 +95,7 @@ SYMBOLS = {
     "vslam_eval_transcendental": (_i, [_i, _i, _vp, _vp, _i]),
     "vslam_eval_select": (_i, [_i, _i, _vp, _i, _vp]),
     "vslam_eval_pose_tail": (_i, [_vp, _vp, _vp, _vp]),
+    "vslam_eval_camera": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
     "vslam_make_keyframe_lite": (_i, [_sys, _vp, _sz, _sz, _i]),
     "vslam_fast_nonmax": (_i, [_sys]),
     "vslam_read_level_image": (_i, [_sys, _i, _i, _vp, _sz]),
@@ -304,6 +305,19 @@ def eval_pose_tail(sums27, pose12):
     up, out = np.zeros(6), np.zeros(12)
     _check(load_library().vslam_eval_pose_tail(s.ctypes.data, p.ctypes.data, up.ctypes.data, out.ctypes.data))
     return up, out
+
+
+CAM_EVAL_FIELDS = {"im": slice(0, 2), "r": 2, "factor": 3, "invalid": 4, "derivs": slice(5, 9), "unproject": slice(9, 11), "boot_out": slice(11, 13), "boot_jac": slice(13, 17)}
+CAM_DERIVED = ("two_tan", "winv", "largest_radius", "max_r", "one_pixel_dist")
+
+
+def eval_camera(cam5, width, height, xy, quirks=0, on_host=False):
+    """The camera arithmetic (csrc/dev_math.h cam_project, cam_derivs, cam_unproject, unproject_with_derivs) over (n, 2) image-plane
+    points, on the device or as compiled for the host -> ((n, 17) array, columns as CAM_EVAL_FIELDS; the 5 derived values, CAM_DERIVED)."""
+    cam, xy = _f64(cam5).reshape(5), _f64(xy).reshape(-1, 2)
+    out, der = np.zeros((len(xy), 17)), np.zeros(5)
+    _check(load_library().vslam_eval_camera(cam.ctypes.data, int(width), int(height), int(quirks), len(xy), xy.ctypes.data, out.ctypes.data, der.ctypes.data, int(on_host)))
+    return out, der
 
 
 def pvs_permutation(seed, frame, lst, n, keys=None, on_host=False):

@@ -227,25 +227,6 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_trail_advance(MapDev m, BootAr
   }
 }
 
-// ATANCamera::UnProject followed by GetProjectionDerivs (jni/ATANCamera.cc:149-164, 198-231)
-DEVFN void unproject_with_derivs(const CamModel& c, double ix, double iy, double out[2], double jac[4]) {
-  const double dx = (ix - c.center[0]) * (1.0 / c.focal[0]), dy = (iy - c.center[1]) * (1.0 / c.focal[1]);
-  const double dist_r = sqrt(dx * dx + dy * dy);
-  const double rr = c.w == 0.0 ? dist_r : vlm::vtan(dist_r * c.w) * (1.0 / c.two_tan);
-  const double f = dist_r > 0.01 ? rr / dist_r : 1.0;
-  const double last_factor = 1.0 / f;
-  out[0] = dx * f; out[1] = dy * f;
-  double fx, fy;
-  const double k = c.two_tan, x = out[0], y = out[1], r = rr * c.distortion_enabled;
-  if (r < 0.01) { fx = 0.0; fy = 0.0; }
-  else {
-    fx = c.winv * (k * x) / (r * r * (1 + k * k * r * r)) - x * last_factor / (r * r);
-    fy = c.winv * (k * y) / (r * r * (1 + k * k * r * r)) - y * last_factor / (r * r);
-  }
-  jac[0] = c.focal[0] * (fx * x + last_factor); jac[2] = c.focal[1] * (fx * y);
-  jac[1] = c.focal[0] * (fy * x); jac[3] = c.focal[1] * (fy * y + last_factor);
-}
-
 // A stream's slices of InitFromStereo's work arrays
 DEVFN bm::Match* boot_matches(const MapDev& m, int s) { return (bm::Match*)(m.boot_match + (size_t)s * BOOT_MAX_TRAILS * 8); }
 DEVFN int* boot_inliers(const MapDev& m, int s) { return m.boot_inl + (size_t)s * BOOT_MAX_TRAILS; }

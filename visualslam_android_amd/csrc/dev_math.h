@@ -201,6 +201,25 @@ HDFN void cam_unproject(const CamModel& c, double ix, double iy, double out[2]) 
   out[0] = dx * f; out[1] = dy * f;
 }
 
+// ATANCamera::UnProject followed by GetProjectionDerivs (jni/ATANCamera.cc:149-164, 198-231): the bootstrap's matches (boot.hip)
+HDFN void unproject_with_derivs(const CamModel& c, double ix, double iy, double out[2], double jac[4]) {
+  const double dx = (ix - c.center[0]) * (1.0 / c.focal[0]), dy = (iy - c.center[1]) * (1.0 / c.focal[1]);
+  const double dist_r = sqrt(dx * dx + dy * dy);
+  const double rr = c.w == 0.0 ? dist_r : vlm::vtan(dist_r * c.w) * (1.0 / c.two_tan);
+  const double f = dist_r > 0.01 ? rr / dist_r : 1.0;
+  const double last_factor = 1.0 / f;
+  out[0] = dx * f; out[1] = dy * f;
+  double fx, fy;
+  const double k = c.two_tan, x = out[0], y = out[1], r = rr * c.distortion_enabled;
+  if (r < 0.01) { fx = 0.0; fy = 0.0; }
+  else {
+    fx = c.winv * (k * x) / (r * r * (1 + k * k * r * r)) - x * last_factor / (r * r);
+    fy = c.winv * (k * y) / (r * r * (1 + k * k * r * r)) - y * last_factor / (r * r);
+  }
+  jac[0] = c.focal[0] * (fx * x + last_factor); jac[2] = c.focal[1] * (fx * y);
+  jac[1] = c.focal[0] * (fy * x); jac[3] = c.focal[1] * (fy * y + last_factor);
+}
+
 // ---- Tukey (jni/MEstimator.h:42-77) --------------------------------------------------------------------------
 HDFN double tukey_sqrt_weight(double e2, double s2) { return e2 > s2 ? 0.0 : 1.0 - (e2 / s2); }
 HDFN double tukey_weight(double e2, double s2) { const double d = tukey_sqrt_weight(e2, s2); return d * d; }

@@ -345,6 +345,59 @@ extern "C" int vslam_eval_transcendental(int fn, int n, const double* x, double*
   return VSLAM_OK;
 }
 
+// ---- self-test hook: the camera arithmetic every projecting kernel reads through CamModel ---------------------------------
+// Per image-plane point 17 doubles: cam_project (im[2], r, factor, invalid), cam_derivs [4], cam_unproject(im) [2],
+// unproject_with_derivs(im) (out[2], jac[4]).  One function for both sides.
+#define CAM_EVAL_DOUBLES 17
+HDFN void cam_eval_point(const CamModel& c, double x, double y, double* o) {
+  const CamProj p = cam_project(c, x, y);
+  o[0] = p.im[0]; o[1] = p.im[1]; o[2] = p.r; o[3] = p.factor; o[4] = p.invalid ? 1.0 : 0.0;
+  double d[4], u[2], bo[2], bj[4];
+  cam_derivs(c, p, d);
+  cam_unproject(c, p.im[0], p.im[1], u);
+  unproject_with_derivs(c, p.im[0], p.im[1], bo, bj);
+  o[5] = d[0]; o[6] = d[1]; o[7] = d[2]; o[8] = d[3];
+  o[9] = u[0]; o[10] = u[1]; o[11] = bo[0]; o[12] = bo[1];
+  o[13] = bj[0]; o[14] = bj[1]; o[15] = bj[2]; o[16] = bj[3];
+}
+
+__global__ __launch_bounds__(64) void k_eval_camera(CamModel cam, int n, const double* xy, double* out) {
+  for (int i = threadIdx.x; i < n; i += 64) {
+    double o[CAM_EVAL_DOUBLES];
+    cam_eval_point(cam, xy[2 * i], xy[2 * i + 1], o);
+#pragma unroll
+    for (int k = 0; k < CAM_EVAL_DOUBLES; k++) out[(size_t)CAM_EVAL_DOUBLES * i + k] = o[k];
+  }
+}
+
+extern "C" int vslam_eval_camera(const double* cam5, int width, int height, int quirks, int n, const double* xy, double* out17, double* derived5,
+                                 int on_host) {
+  if (!cam5 || width < 1 || height < 1 || n < 0 || (n > 0 && (!xy || !out17)) || !derived5) { vslam_set_error("eval_camera: bad argument"); return VSLAM_E_INVALID; }
+  vslam_params p;
+  memset(&p, 0, sizeof(p));
+  p.width = width; p.height = height; p.quirks = quirks;
+  for (int k = 0; k < 5; k++) p.cam[k] = cam5[k];
+  TrackParams tp;
+  trk_fill_params(p, tp);                               // cam_fill and OnePixelDist as every handle takes them
+  derived5[0] = tp.cam.two_tan; derived5[1] = tp.cam.winv; derived5[2] = tp.cam.largest_radius; derived5[3] = tp.cam.max_r; derived5[4] = tp.one_pixel_dist;
+  if (on_host) {                                        // the same functions compiled for the host
+    for (int i = 0; i < n; i++) cam_eval_point(tp.cam, xy[2 * i], xy[2 * i + 1], out17 + (size_t)CAM_EVAL_DOUBLES * i);
+    return VSLAM_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { vslam_set_error("eval_camera: no HIP device visible"); return VSLAM_E_HIP; }
+  if (n == 0) return VSLAM_OK;
+  DevTemp<double> d_xy, d_out;
+  HIPCHK(d_xy.get((size_t)2 * n));
+  HIPCHK(d_out.get((size_t)CAM_EVAL_DOUBLES * n));
+  HostCopy c(nullptr);                                  // no handle: the null stream from start to end, through the copy primitive
+  VCHK(c.put(d_xy.p, xy, (size_t)2 * n));
+  hipLaunchKernelGGL(k_eval_camera, dim3(1), dim3(64), 0, 0, tp.cam, n, (const double*)d_xy.p, d_out.p);
+  HIPCHK(hipGetLastError());
+  VCHK(c.get(out17, (const double*)d_out.p, (size_t)CAM_EVAL_DOUBLES * n));
+  return c.wait();
+}
+
 // ---- self-test hooks: the median's select and the tail of a pose iteration, each in one workgroup of its kernel's size ----
 // The values are handed over as their producers do: the range of what can be selected is gathered while they are read (+inf
 // marks an entry outside the median, as in the bundle adjustment's scratch) and published before the barrier in front of the select.

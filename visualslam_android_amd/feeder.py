@@ -138,7 +138,7 @@ def _project_np(cam, w, h, x, y):
     """ATANCamera::Project (jni/ATANCamera.cc:133-145) vectorised."""
     fx, fy, cx, cy, ww = w * cam[0], h * cam[1], w * cam[2] - 0.5, h * cam[3] - 0.5, cam[4]
     r = np.hypot(x, y)
-    fac = np.where((r < 0.001) | (ww == 0.0), 1.0, np.arctan(r * 2.0 * np.tan(ww / 2.0)) / ww / np.maximum(r, 1e-300))
+    fac = np.where((r < 0.001) | (ww == 0.0), 1.0, np.arctan(r * 2.0 * np.tan(ww / 2.0)) / (ww if ww != 0.0 else 1.0) / np.maximum(r, 1e-300))
     return cx + fx * x * fac, cy + fy * y * fac
 
 
