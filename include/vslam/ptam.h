@@ -120,6 +120,18 @@ class MapMaker {
   // not in the reference (its map grows on the heap): one keyframe leaves the map, with the points it is the patch source of and every bad
   // point (vslam_retire_keyframes); nKeyFrame < 0: the keyframe farthest from the tracker's pose
   void RetireKeyFrame(int nKeyFrame = -1) { const int s = 0; vslam_detail::check(vslam_retire_keyframes(mMap.sys, &s, &nKeyFrame, 1)); }
+  // :440-449 and :452-464, on the device and in place (vslam_transform_maps): keyframe poses, map points and their pixel vectors, and with
+  // them the tracker's poses, velocity, scene depths and the relocaliser's pose, which the reference's tracker picks up by itself
+  void ApplyGlobalTransformationToMap(mySE3 se3NewFromOld) {
+    const int s = 0; double q[12];
+    for (int i = 0; i < 9; i++) q[i] = se3NewFromOld.R[i];
+    for (int i = 0; i < 3; i++) q[9 + i] = se3NewFromOld.t[i];
+    vslam_detail::check(vslam_transform_maps(mMap.sys, &s, 1, q, nullptr));
+  }
+  void ApplyGlobalScaleToMap(double dScale) {
+    const int s = 0; const double q[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    vslam_detail::check(vslam_transform_maps(mMap.sys, &s, 1, q, &dScale));
+  }
   bool NeedNewKeyFrame(KeyFrame&) { int v = 0; vslam_detail::check(vslam_need_new_keyframe(mMap.sys, 0, &v)); return v != 0; }              // :761-773 (the tracker's current frame)
   bool IsDistanceToNearestKeyFrameExcessive(KeyFrame&) { int v = 0; vslam_detail::check(vslam_distance_to_nearest_keyframe_excessive(mMap.sys, 0, &v)); return v != 0; }   // :1098-1101
   // :204-376, the reference's signature (ImageRef = a pair of ints): the two keyframes' images (KeyFrame::im0, kept by MakeKeyFrame_Lite)

@@ -304,6 +304,45 @@ int vslam_get_retire_info(vslam_system* sys, int stream, int out[6]);
  * VSLAM_E_STATE before the first such call. */
 int vslam_get_retire_timing(vslam_system* sys, double* ms);
 
+/* ---- similarity transform of a map (re-anchor and rescale) -------------------------------------
+ * MapMaker::ApplyGlobalScaleToMap + ApplyGlobalTransformationToMap (jni/MapMaker.cc:440-464) for n streams of a live batch, on the
+ * device and in place: a monocular map has no gauge of its own, and this puts it into the caller's -- a site frame, a metric scale.
+ * x' = R (s x) + t, with new_from_old12 = (R, t) (pose12: R row-major, then t) mapping the old world frame to the new one and s > 0
+ * (scale == NULL: all 1).  Transform i belongs to streams[i]; streams == NULL: every stream, transform s for stream s (n > 0 is then not
+ * read further).  n == 0 succeeds and does nothing.  What changes, and in which order of operations, is stated once in
+ * csrc/similarity_dev.h: the map points and their pixel vectors, the keyframe poses and scene depths, the tracker's poses, the
+ * translational half of its velocity, its scene depth, the camera-frame positions of its per-point data, and the relocaliser's pose;
+ * everything else keeps every bit.  The pixel vectors are rotated and scaled, not remade (a map uploaded with the caller's own vectors
+ * keeps them), and the depths are multiplied, not recomputed: with s == 1 a rigid move leaves velocity and depths bitwise alone.  The
+ * tracker's next frame continues in the new gauge.  Two things read vslam_params.wiggle_scale as an absolute length
+ * (IsDistanceToNearestKeyFrameExcessive, jni/MapMaker.cc:1098-1101, and the start depth of AddPointEpipolar) and do not follow a rescale,
+ * and ba_convergence_limit and wls_prior are absolute in the same way (csrc/similarity_dev.h): that is the reference's behaviour,
+ * nothing compensates for it.
+ * Between frames or between subset steps; a stream held in the last step is not special.  The call waits once for the device to read the
+ * listed streams' states; everything is decided before anything changes, and a refused call changes nothing for any stream.  All listed
+ * streams go in one launch on the system's stream; nothing is allocated per call.
+ * VSLAM_E_INVALID: NULL system, n < 0 or n > n_streams, an index outside the batch, a duplicate stream, NULL transforms with n > 0, a
+ * non-finite entry, s <= 0, R not a rotation (max |R^T R - I| > 1e-9, or det R < 0).
+ * VSLAM_E_STATE: a stage-wise frame is open; a listed stream has no good map, its trails running, or an adjustment of the asynchronous
+ * map-maker pending (its result would land in the old gauge; the call succeeds once it has landed). */
+int vslam_transform_maps(vslam_system* sys, const int* streams, int n, const double* new_from_old12 /* n x pose12 */, const double* scale /* n, or NULL: all 1 */);
+/* out_i[0..1] = transforms of the stream since its creation, reset or restore, and mnFrame (jni/Tracker.h:116) at the last one;
+ * out_d[0..12] = the accumulated similarity from the original gauge to the current one, pose12 then scale (a transform (R, t, s) applied
+ * after (R_acc, t_acc, s_acc) gives R R_acc, s R t_acc + t, s s_acc).  Kept on the host: no wait.  vslam_reset_streams and
+ * vslam_restore_stream put it back to zero and the identity; a snapshot does not carry it. */
+int vslam_get_transform_info(vslam_system* sys, int stream, int out_i[2], double out_d[13]);
+/* HIP-event milliseconds around the last vslam_transform_maps's launch on the system's stream.  Waits for it.  VSLAM_E_STATE before the
+ * first call that transformed. */
+int vslam_get_transform_timing(vslam_system* sys, double* ms);
+/* Least-squares similarity to3 ~ s R from3 + t over n >= 3 correspondences (weights NULL = 1), Horn / Umeyama closed form; host only, no
+ * GPU and no system.  fix_scale != 0: s = 1, only R and t are fitted.  The result goes straight into vslam_transform_maps: read the
+ * keyframe centres with vslam_get_keyframe_pose, fit them to their known positions, apply.  R is always a proper rotation (det > 0), for
+ * mirrored data too.  scale and rms (the weighted root mean square residual) may be NULL.
+ * VSLAM_E_INVALID: n < 3, a non-finite entry, a negative weight, or points (from3, or to3) that are collinear or coincident within 1e-12
+ * of their extent -- the rotation is then not determined. */
+int vslam_fit_similarity(int n, const double* from3, const double* to3, const double* weights, int fix_scale,
+                         double new_from_old12[12], double* scale, double* rms);
+
 /* ---- overlay: the tracker's points and trails drawn into RGBA (vslam_params.overlay) -------------
  * What Tracker::TrackFrame draws on imageColor (jni/Tracker.cc:580-588 the patches TrackMap found, as discs coloured by pyramid level, the
  * `if(mbDraw)` guard commented out; :322-336 the bootstrap trails, as lines) and native_update hands back to the Java view

@@ -130,6 +130,10 @@ SYMBOLS = {
     "vslam_retire_keyframes": (_i, [_sys, _vp, _vp, _i]),
     "vslam_get_retire_info": (_i, [_sys, _i, _vp]),
     "vslam_get_retire_timing": (_i, [_sys, C.POINTER(_d)]),
+    "vslam_transform_maps": (_i, [_sys, _vp, _i, _vp, _vp]),
+    "vslam_get_transform_info": (_i, [_sys, _i, _vp, _vp]),
+    "vslam_get_transform_timing": (_i, [_sys, C.POINTER(_d)]),
+    "vslam_fit_similarity": (_i, [_i, _vp, _vp, _vp, _i, _vp, C.POINTER(_d), C.POINTER(_d)]),
     "vslam_render_overlay": (_i, [_sys, _vp, _i, _vp, _sz, _sz, _i, _i]),
     "vslam_get_overlay_info": (_i, [_sys, _i, _vp]),
     "vslam_get_render_timing": (_i, [_sys, C.POINTER(_d)]),
@@ -260,6 +264,19 @@ def snapshot_info(blob):
     out = SnapshotInfo()
     _check(load_library().vslam_snapshot_info(a.ctypes.data if a.size else None, a.size, C.byref(out)))
     return out
+
+
+def fit_similarity(from3, to3, weights=None, fix_scale=False):
+    """vslam_fit_similarity: the least-squares similarity to3 ~ s R from3 + t over n >= 3 correspondences (Horn / Umeyama closed form;
+    host code only) -> (pose12, scale, rms).  pose12 and scale go straight into System.transform_maps."""
+    a, b = np.ascontiguousarray(from3, np.float64).reshape(-1, 3), np.ascontiguousarray(to3, np.float64).reshape(-1, 3)
+    assert len(a) == len(b)
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+    assert w is None or len(w) == len(a)
+    q, s, rms = np.zeros(12), C.c_double(0.0), C.c_double(0.0)
+    _check(load_library().vslam_fit_similarity(len(a), a.ctypes.data, b.ctypes.data, None if w is None else w.ctypes.data, int(bool(fix_scale)),
+                                               q.ctypes.data, C.byref(s), C.byref(rms)))
+    return q, s.value, rms.value
 
 
 def default_params(width, height, n_streams=1, **overrides):
@@ -575,6 +592,28 @@ class System:
         """-> HIP-event ms of the last retire_keyframes on the system's stream (vslam_get_retire_timing)"""
         ms = C.c_double(0.0)
         _check(self.lib.vslam_get_retire_timing(self.h, C.byref(ms)))
+        return ms.value
+
+    def transform_maps(self, streams, poses, scales=None):
+        """The maps of the listed streams (None: every stream) move into a new gauge, x' = R (s x) + t (vslam_transform_maps): poses
+        [n, 12] new-from-old as pose12, scales [n] (None: all 1); transform i belongs to streams[i]"""
+        a = None if streams is None else np.ascontiguousarray(np.atleast_1d(streams), np.int32)
+        n = self.S if a is None else len(a)
+        q = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        sc = None if scales is None else np.ascontiguousarray(np.atleast_1d(scales), np.float64)
+        assert len(q) == n and (sc is None or len(sc) == n)
+        _check(self.lib.vslam_transform_maps(self.h, None if a is None else a.ctypes.data, n, q.ctypes.data, None if sc is None else sc.ctypes.data))
+
+    def transform_info(self, stream):
+        """-> {"transforms", "frame", "pose" (accumulated new-from-original pose12), "scale"} (vslam_get_transform_info)"""
+        oi, od = np.zeros(2, np.int32), np.zeros(13)
+        _check(self.lib.vslam_get_transform_info(self.h, stream, oi.ctypes.data, od.ctypes.data))
+        return {"transforms": int(oi[0]), "frame": int(oi[1]), "pose": od[:12].copy(), "scale": float(od[12])}
+
+    def transform_timing(self):
+        """-> HIP-event ms of the last transform_maps on the system's stream (vslam_get_transform_timing)"""
+        ms = C.c_double(0.0)
+        _check(self.lib.vslam_get_transform_timing(self.h, C.byref(ms)))
         return ms.value
 
     # ---- stream snapshots --------------------------------------------------------------------

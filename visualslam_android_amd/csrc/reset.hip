@@ -15,6 +15,7 @@
 //   the pool record               ba.hip, ba_reset_streams
 //   the retire record             vslam_get_retire_info (retire.hip), where the system holds one
 //   the overlay's record          -1, TrackMap has not run (overlay.hip), where the system holds one
+//   the transform record          vslam_get_transform_info (transform.hip), kept on the host: no transforms, the identity
 // Not cleared, because every reader is bounded by a count that is now zero and the writer that raises the count fills what it exposes:
 // MapPointDev (n_points; append_point / vslam_map_add_points), the failure queue (fq_n), keyframe images, corner lists and
 // SmallBlurryImages (n_kf; k_add_keyframe, k_copy_kf_corners, k_kf_sbi and their upload forms), the relocaliser's scores and frame
@@ -118,6 +119,7 @@ extern "C" int vslam_reset_streams(vslam_system* sys, const int* streams, int n)
   HIPCHK(hipStreamWaitEvent(sys->fe_stream, sys->ev_reset, 0));
   for (hipStream_t st : sys->ba_streams) HIPCHK(hipStreamWaitEvent(st, sys->ev_reset, 0));
   if (sys->p.use_sbi) sys->sbi_restart_pending = true;
+  for (int s = 0; s < sys->S; s++) if (f[s]) transform_forget(sys, s);   // the transform record is the host's: a new system's
   return VSLAM_OK;
 }
 

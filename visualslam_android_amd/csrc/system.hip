@@ -146,6 +146,7 @@ static int sys_acquire(vslam_system* sys) {
   VCHK(snapshot_alloc(sys));
   if (p->keyframe_retire) VCHK(retire_alloc(sys));
   VCHK(overlay_alloc(sys));
+  VCHK(transform_alloc(sys));
   VCHK(map_init_states(sys));            // (on q, behind the zeroing of the states)
   HIPCHK(hipStreamSynchronize(q));       // the zeroing contract (DevOwner::alloc): from here on the memory is zero for every stream
   return VSLAM_OK;

@@ -322,6 +322,10 @@ template <class T> static inline int host_put(hipStream_t q, T* dev, const T* ho
 
 struct BaSystemWs;             // bundle-adjustment workspace (ba.hip)
 
+// vslam_get_transform_info: the transforms a stream has seen since its creation, reset or restore, mnFrame at the last one, and the
+// accumulated similarity from the original gauge to the current one (similarity_dev.h, sim_compose).  Kept on the host.
+struct TransformRecord { int count, frame; Pose T; double s; };
+
 struct vslam_system {
   vslam_params p;
   int S;
@@ -388,6 +392,13 @@ struct vslam_system {
   int* retire_req_stage = nullptr;           // [S] pinned host copy of the request
   hipEvent_t ev_retire_t[2] = {nullptr, nullptr};   // around the last explicit call's launches (vslam_get_retire_timing)
   long retire_calls = 0;
+  // vslam_transform_maps (transform.hip): the call's argument array, sized for every stream at creation
+  void* transform_args = nullptr;            // [S] device: stream, T, T^-1 and s per ordinal of the call in flight
+  void* transform_stage = nullptr;           // [S] pinned host copy of them
+  std::vector<TrackerState> transform_states;   // [S] host: the listed streams' states, read once per call
+  std::vector<TransformRecord> transform_rec;   // [S] host: vslam_get_transform_info
+  hipEvent_t ev_transform_t[2] = {nullptr, nullptr};   // around the last call's launch (vslam_get_transform_timing)
+  long transform_calls = 0;
   // the overlay renderer (overlay.hip; vslam_params.overlay): null with overlay = 0
   int* overlay_ran = nullptr;                // [S] device: mnFrame at which TrackMap last ran for the stream, -1 never (or forgotten by a reset)
   int* overlay_info = nullptr;               // [S][3] device: discs, lines, marks of the stream's last render
@@ -520,6 +531,9 @@ int snapshot_alloc(vslam_system* sys);
 int overlay_alloc(vslam_system* sys);
 int overlay_note_track_map(vslam_system* sys);   // overlay = 1: records the frame for the streams whose TrackMap runs; the launch in front of k_motion
 int overlay_forget_listed(vslam_system* sys, const int* d_req, int not_listed);   // ... back to -1 for the streams a retirement lists
+// transform.hip
+int transform_alloc(vslam_system* sys);
+void transform_forget(vslam_system* sys, int s);   // a reset or restored stream: no transforms, the identity
 // retire.hip
 int retire_alloc(vslam_system* sys);          // the scratch of keyframe retirement, if the system does not hold it yet
 int retire_on_keyframe(vslam_system* sys);    // keyframe_retire: one keyframe by policy for the full streams with kf_pending, before k_add_keyframe
