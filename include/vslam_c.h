@@ -343,6 +343,38 @@ int vslam_get_transform_timing(vslam_system* sys, double* ms);
 int vslam_fit_similarity(int n, const double* from3, const double* to3, const double* weights, int fix_scale,
                          double new_from_old12[12], double* scale, double* rms);
 
+/* ---- map merge: append one live stream's map to another's ---------------------------------------
+ * Pair i appends the map of stream src[i] to the map of stream dst[i], both in this system, on the device and in place; afterwards the
+ * destination's tracker and map-maker work on the union.  A map from another system comes in through vslam_restore_stream into a spare
+ * slot first.  The reference has no such operation (its Map is a single heap object, jni/Map.h:21-34): like retirement this is the
+ * build's own, and a system that never calls it allocates nothing for it and launches nothing.
+ * With nk_d keyframes and np_d points in the destination: the source's keyframe k becomes keyframe nk_d + k, its point p becomes point
+ * np_d + p, order kept; measurements, templates and their source images, the tracker's per-point data, never-retry sets and the failure
+ * queue come along renumbered (csrc/merge_dev.h states the index rules, csrc/merge.hip what every array holds afterwards).  The
+ * appended keyframes are not fixed (the destination keeps its one gauge), the appended points carry none of the source's per-frame
+ * flags, and both "bundle adjustment has converged" flags of the destination are cleared.  The source is read only and keeps every bit:
+ * the caller resets it or lets it run on.  Nothing of the destination below its old counts changes.
+ * No point fusion: points that both maps hold of the same surface feature stay two points.  No registration: bringing both maps into one
+ * frame and scale first is the caller's job (vslam_fit_similarity + vslam_transform_maps); nothing in this call can check it.  The parts
+ * become one adjustable map as keyframes added afterwards measure points of both, and, with idle_iterations, as ReFindNewlyMade looks for
+ * the appended points in the destination's keyframes: they all count as newly made (mqNewQueue keeps its head).
+ * Between frames only.  The call waits once for the device to read the 2n states; everything is decided before anything changes, and a
+ * refused call changes nothing for any stream.  All pairs go in one set of two launches; n == 0 succeeds and does nothing.
+ * VSLAM_E_INVALID: NULL system, n < 0, NULL lists with n > 0, an index outside the batch, dst[i] == src[i], a stream that appears twice
+ * among the 2n entries in either role (so the pairs of one call are independent).
+ * VSLAM_E_STATE: a stage-wise frame is open; a stream of a pair has no good map, its trails running, or an adjustment of the
+ * asynchronous map-maker pending.
+ * VSLAM_E_CAPACITY: the keyframes of a pair exceed max_keyframes or its points max_points; the message names the pair, the counts and
+ * the capacity.  vslam_retire_keyframes makes room. */
+int vslam_merge_maps(vslam_system* sys, const int* dst, const int* src, int n);
+/* out[0] = merges into this stream so far; of the last one: out[1] the source stream's index, out[2] keyframes appended, out[3] points
+ * appended, out[4] failure-queue entries appended, out[5] the destination's mnFrame (jni/Tracker.h:116) at that time.  All zeros for a
+ * stream that was never a destination.  vslam_reset_streams and vslam_restore_stream zero the record. */
+int vslam_get_merge_info(vslam_system* sys, int stream, int out[6]);
+/* HIP-event milliseconds around the last vslam_merge_maps's launches on the system's stream.  Waits for them.  VSLAM_E_STATE before the
+ * first call that merged. */
+int vslam_get_merge_timing(vslam_system* sys, double* ms);
+
 /* ---- overlay: the tracker's points and trails drawn into RGBA (vslam_params.overlay) -------------
  * What Tracker::TrackFrame draws on imageColor (jni/Tracker.cc:580-588 the patches TrackMap found, as discs coloured by pyramid level, the
  * `if(mbDraw)` guard commented out; :322-336 the bootstrap trails, as lines) and native_update hands back to the Java view

@@ -133,6 +133,9 @@ SYMBOLS = {
     "vslam_transform_maps": (_i, [_sys, _vp, _i, _vp, _vp]),
     "vslam_get_transform_info": (_i, [_sys, _i, _vp, _vp]),
     "vslam_get_transform_timing": (_i, [_sys, C.POINTER(_d)]),
+    "vslam_merge_maps": (_i, [_sys, _vp, _vp, _i]),
+    "vslam_get_merge_info": (_i, [_sys, _i, _vp]),
+    "vslam_get_merge_timing": (_i, [_sys, C.POINTER(_d)]),
     "vslam_fit_similarity": (_i, [_i, _vp, _vp, _vp, _i, _vp, C.POINTER(_d), C.POINTER(_d)]),
     "vslam_render_overlay": (_i, [_sys, _vp, _i, _vp, _sz, _sz, _i, _i]),
     "vslam_get_overlay_info": (_i, [_sys, _i, _vp]),
@@ -614,6 +617,24 @@ class System:
         """-> HIP-event ms of the last transform_maps on the system's stream (vslam_get_transform_timing)"""
         ms = C.c_double(0.0)
         _check(self.lib.vslam_get_transform_timing(self.h, C.byref(ms)))
+        return ms.value
+
+    def merge_maps(self, dst, src):
+        """The map of stream src[i] is appended to the map of stream dst[i] (vslam_merge_maps); the sources keep every bit"""
+        a, b = np.ascontiguousarray(np.atleast_1d(dst), np.int32), np.ascontiguousarray(np.atleast_1d(src), np.int32)
+        assert len(a) == len(b)
+        _check(self.lib.vslam_merge_maps(self.h, a.ctypes.data, b.ctypes.data, len(a)))
+
+    def merge_info(self, stream):
+        """-> {"merged", "source", "keyframes", "points", "queue", "frame"} of the stream as a destination (vslam_get_merge_info)"""
+        o = np.zeros(6, np.int32)
+        _check(self.lib.vslam_get_merge_info(self.h, stream, o.ctypes.data))
+        return dict(zip(("merged", "source", "keyframes", "points", "queue", "frame"), (int(x) for x in o)))
+
+    def merge_timing(self):
+        """-> HIP-event ms of the last merge_maps on the system's stream (vslam_get_merge_timing)"""
+        ms = C.c_double(0.0)
+        _check(self.lib.vslam_get_merge_timing(self.h, C.byref(ms)))
         return ms.value
 
     # ---- stream snapshots --------------------------------------------------------------------

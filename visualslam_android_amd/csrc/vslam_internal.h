@@ -399,6 +399,12 @@ struct vslam_system {
   std::vector<TransformRecord> transform_rec;   // [S] host: vslam_get_transform_info
   hipEvent_t ev_transform_t[2] = {nullptr, nullptr};   // around the last call's launch (vslam_get_transform_timing)
   long transform_calls = 0;
+  // vslam_merge_maps (merge.hip): allocated by the first call, else null
+  int* merge_plan = nullptr;                 // [S][MERGE_PLAN_N] device: the plan record of each pair of the call in flight
+  int* merge_info = nullptr;                 // [S][6] device: vslam_get_merge_info
+  int* merge_plan_stage = nullptr;           // pinned host copy of the request the plan starts from
+  hipEvent_t ev_merge_t[2] = {nullptr, nullptr};   // around the last call's launches (vslam_get_merge_timing)
+  long merge_calls = 0;
   // the overlay renderer (overlay.hip; vslam_params.overlay): null with overlay = 0
   int* overlay_ran = nullptr;                // [S] device: mnFrame at which TrackMap last ran for the stream, -1 never (or forgotten by a reset)
   int* overlay_info = nullptr;               // [S][3] device: discs, lines, marks of the stream's last render
