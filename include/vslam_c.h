@@ -154,6 +154,20 @@ int vslam_eval_pose_tail(const double* sums27, const double* pose12, double* upd
  * evaluated by one 64-lane workgroup on the device or (on_host != 0) by the same functions compiled for the host; both must return
  * the same bits. */
 int vslam_eval_camera(const double* cam5, int width, int height, int quirks, int n, const double* xy, double* out17, double* derived5, int on_host);
+/* Self-test hook: the line geometry of MapMaker::AddPointEpipolar (jni/MapMaker.cc:544-591) and the triangulation of
+ * MapMaker::ReprojectPoint (:174-200) on their own, by the device functions the map-growth kernel runs, with the handle's camera
+ * (vslam_params.cam, width, height, quirks) and on the handle's queue; one launch, one lane per case.
+ * lines30: n_lines cases of 30 doubles -- the source keyframe's pose [12] (R row-major, then t), the target keyframe's [12], the
+ *   candidate's level position x, y, its level (0..3), the source keyframe's scene depth mean and sigma, wiggle_scale.
+ *   line_flags2 receives per case (why, clipped): why = 0 the line stands, 1 the ray ends before it starts or behind the target, 2 a
+ *   segment shorter than 1e-4, 3 the line passes outside largest_radius; clipped = 1 if the start of the ray was moved in front of
+ *   the target's image plane.  line_out12 receives root [2], along [2], normal [2], dNormDist, dMinLen, dMaxLen, and what the first
+ *   three tests compare: the depth of the ray's start in the target before the clip, of its end, the squared length of the segment; a
+ *   field an exit does not reach is 0 (along is the un-normalised difference at why = 2).
+ * tri16: n_tri cases of 16 doubles -- AfromB [12], v2A [2], v2B [2].  tri_out7 receives the homogeneous vector of the smallest
+ *   singular value [4] as the SVD returns it, and the point [3].
+ * The oracle states both for the host (orc_eval_epipolar, orc_eval_triangulation); the two must return the same bits. */
+int vslam_eval_epipolar(vslam_system* sys, int n_lines, const double* lines30, int* line_flags2, double* line_out12, int n_tri, const double* tri16, double* tri_out7);
 
 /* ---- frame front-end ------------------------------------------------------------------- */
 

@@ -316,17 +316,23 @@ class OracleSystem:
     def grow_detail(self, cap=65536):
         """one row per row of grow_log: survivors of the line filter, the most of them in one aligned block of 64 entries of the target's
         corner list, blocks that hold one, the minimum had an equal-ZMSSD rival later in the list, the ray start was clipped, the rank of the
-        minimum among the survivors of its block"""
-        out = np.zeros((cap, 6), np.int32)
+        minimum among the survivors of its block; and (orc_sys_get_grow_rival) the rank of the last equal rival among the survivors of its
+        block and 1 if that block is the minimum's"""
+        out, riv = np.zeros((cap, 6), np.int32), np.zeros((cap, 2), np.int32)
         n = self.L.orc_sys_get_grow_detail(self.h, _p(out), cap)
-        return {k: out[:n, i].copy() for i, k in enumerate(("survivors", "block_max", "blocks", "tie", "clipped", "best_rank"))}
+        assert self.L.orc_sys_get_grow_rival(self.h, _p(riv), cap) == n
+        d = {k: out[:n, i].copy() for i, k in enumerate(("survivors", "block_max", "blocks", "tie", "clipped", "best_rank"))}
+        d.update(rival_rank=riv[:n, 0].copy(), rival_same_block=riv[:n, 1].copy())
+        return d
 
     REFIND_JOBS = ("single keyframe", "newly made", "failure queue")
-    REFIND_OUTCOMES = ("measured", "template bad", "window outside", "not found")
+    REFIND_OUTCOMES = ("measured", "template bad", "window outside", "not found", "behind", "outside radius", "invalid projection", "outside image")
+    REFIND_EARLY = 4                 # outcomes from here on returned before the template (jni/MapMaker.cc:979-996)
 
     def refind_log(self, cap=262144):
-        """every ReFind_Common call that reached the template: job (index of REFIND_JOBS), keyframe, point, cache hit, search level, list span of
-        the search window, outcome (index of REFIND_OUTCOMES), run number of the job"""
+        """every ReFind_Common call past the measured / never-retry test: job (index of REFIND_JOBS), keyframe, point, cache hit, search level,
+        list span of the search window, outcome (index of REFIND_OUTCOMES), run number of the job; an early return (outcome >= REFIND_EARLY)
+        has no template: hit 0, level -1, span -1"""
         out = np.zeros((cap, 8), np.int32)
         n = self.L.orc_sys_get_refind_log(self.h, _p(out), cap)
         assert n <= cap
@@ -533,6 +539,33 @@ def cam_eval(cam5, w, h, xy, quirks=0):
     L = lib(); L.orc_cam_eval.restype = None
     L.orc_cam_eval(_p(_d(cam5)), int(w), int(h), int(quirks), len(xy), _p(xy), _p(out), _p(der))
     return out, der
+
+
+def find_coarse_span(gray, level, im_x, im_y, search_range=4):
+    """one FindPatchCoarse call (flat 8x8 template at `level`) on the keyframe made of `gray`, at the level-0 position (im_x, im_y) -> the list
+    span of its search window, -1 when the window lies outside the level's rows"""
+    g = np.ascontiguousarray(gray, np.uint8)
+    return int(lib().orc_find_coarse_span(_p(g), g.shape[1], g.shape[0], int(level), C.c_double(im_x), C.c_double(im_y), int(search_range)))
+
+
+def eval_epipolar(cam5, w, h, lines, quirks=0):
+    """epipolar_line (the geometry of AddPointEpipolar, as the oracle's product path runs it) over (n, 30) cases in vslam_eval_epipolar's
+    layout -> (flags (n, 2) int32: why, clipped; (n, 12): root, along, normal, dNormDist, dMinLen, dMaxLen, the depths of the ray's start (before the clip) and end in the target, the
+    segment's squared length)"""
+    a = np.ascontiguousarray(lines, np.float64).reshape(-1, 30)
+    flags, out = np.zeros((len(a), 2), np.int32), np.zeros((len(a), 12))
+    L = lib(); L.orc_eval_epipolar.restype = None
+    L.orc_eval_epipolar(_p(_d(cam5)), int(w), int(h), int(quirks), len(a), _p(a), _p(flags), _p(out))
+    return flags, out
+
+
+def eval_triangulation(tri):
+    """reproject_vector and reproject_point over (n, 16) cases (AfromB [12], v2A, v2B) -> (n, 7): the homogeneous vector [4], the point [3]"""
+    a = np.ascontiguousarray(tri, np.float64).reshape(-1, 16)
+    out = np.zeros((len(a), 7))
+    L = lib(); L.orc_eval_triangulation.restype = None
+    L.orc_eval_triangulation(len(a), _p(a), _p(out))
+    return out
 
 
 def find_sigma_squared(est, v):

@@ -69,14 +69,18 @@ void svd4_smallest_right_vector(const double Ain[16], double out[4]) {
   for (int k = 0; k < 4; k++) out[k] = V[k * 4 + best];
 }
 
-// MapMaker::ReprojectPoint, jni/MapMaker.cc:174-200
-V3 reproject_point(const SE3& AfromB, const double v2A[2], const double v2B[2]) {
+// MapMaker::ReprojectPoint, jni/MapMaker.cc:174-200: the homogeneous vector as the SVD hands it over (:176-192) ...
+void reproject_vector(const SE3& AfromB, const double v2A[2], const double v2B[2], double v[4]) {
   double PD[12];                                                // 3x4 [R | t]
   for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) PD[r * 4 + c] = AfromB.R[r * 3 + c]; PD[r * 4 + 3] = AfromB.t[r]; }
   double A[16] = {-1.0, 0.0, v2B[0], 0.0, 0.0, -1.0, v2B[1], 0.0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int c = 0; c < 4; c++) { A[8 + c] = v2A[0] * PD[8 + c] - PD[0 + c]; A[12 + c] = v2A[1] * PD[8 + c] - PD[4 + c]; }
-  double v[4];
   svd4_smallest_right_vector(A, v);                            // svd.matrixV().block(0, 3, 4, 1)
+}
+// ... and the point (:194-199)
+V3 reproject_point(const SE3& AfromB, const double v2A[2], const double v2B[2]) {
+  double v[4];
+  reproject_vector(AfromB, v2A, v2B, v);
   if (v[3] == 0.0) v[3] = 0.00001;
   return v3(v[0] / v[3], v[1] / v[3], v[2] / v[3]);
 }
@@ -140,6 +144,46 @@ V3 unit_ray(const Camera& cam, double ix, double iy) {
   return v3(u[0] / n, u[1] / n, 1.0 / n);                      // myUnproject + normalize()
 }
 
+// The geometry of the search line, jni/MapMaker.cc:544-591 (csrc/grow_dev.h epipolar_line states it for the device, statement for
+// statement; the fields and exits are described there).  AddPointEpipolar below and orc_eval_epipolar run this.
+EpiLine epipolar_line(const Camera& camera, const SE3& src, const SE3& tgt, double irx, double iry, int nLevel, double dMean, double dSigma, double wiggle_scale) {
+  EpiLine e;
+  e.why = 0; e.clipped = 0; e.along[0] = 0; e.along[1] = 0; e.normal[0] = 0; e.normal[1] = 0; e.dNormDist = 0; e.dMinLen = 0; e.dMaxLen = 0; e.alongSq = 0;
+  e.root[0] = level_zero_pos(irx, nLevel); e.root[1] = level_zero_pos(iry, nLevel);
+  const V3 v3Ray_SC = unit_ray(camera, e.root[0], e.root[1]);
+  const V3 v3LineDirn_TC = rot(tgt, rot_inv(src, v3Ray_SC));
+  const double dStartDepth = std::max(wiggle_scale, dMean - dSigma);
+  const double dEndDepth = std::min(40 * wiggle_scale, dMean + dSigma);
+  const SE3 srcInv = inverse(src);
+  const V3 v3CamCenter_TC = xform(tgt, v3(srcInv.t[0], srcInv.t[1], srcInv.t[2]));
+  V3 v3RayStart_TC, v3RayEnd_TC;
+  for (int i = 0; i < 3; i++) { v3RayStart_TC[i] = v3CamCenter_TC[i] + dStartDepth * v3LineDirn_TC[i]; v3RayEnd_TC[i] = v3CamCenter_TC[i] + dEndDepth * v3LineDirn_TC[i]; }
+  e.startZ = v3RayStart_TC[2]; e.endZ = v3RayEnd_TC[2];
+  if (v3RayEnd_TC[2] <= v3RayStart_TC[2]) { e.why = 1; return e; }
+  if (v3RayEnd_TC[2] <= 0.0) { e.why = 1; return e; }
+  if (v3RayStart_TC[2] <= 0.0) {
+    e.clipped = 1;
+    const double f = 0.001 - v3RayStart_TC[2] / v3LineDirn_TC[2];
+    for (int i = 0; i < 3; i++) v3RayStart_TC[i] += v3LineDirn_TC[i] * f;
+  }
+  const double v2A[2] = {v3RayStart_TC[0] / v3RayStart_TC[2], v3RayStart_TC[1] / v3RayStart_TC[2]};
+  const double v2B[2] = {v3RayEnd_TC[0] / v3RayEnd_TC[2], v3RayEnd_TC[1] / v3RayEnd_TC[2]};
+  e.along[0] = v2A[0] - v2B[0]; e.along[1] = v2A[1] - v2B[1];
+  e.alongSq = e.along[0] * e.along[0] + e.along[1] * e.along[1];
+  if (e.along[0] * e.along[0] + e.along[1] * e.along[1] < 0.00000001) { e.why = 2; return e; }
+  { const double n = sqrt(e.along[0] * e.along[0] + e.along[1] * e.along[1]); e.along[0] /= n; e.along[1] /= n; }
+  e.normal[0] = e.along[1]; e.normal[1] = -e.along[0];
+  e.dNormDist = v2A[0] * e.normal[0] + v2A[1] * e.normal[1];
+  if (fabs(e.dNormDist) > camera.largest_radius) { e.why = 3; return e; }
+  e.dMinLen = std::min(e.along[0] * v2A[0] + e.along[1] * v2A[1], e.along[0] * v2B[0] + e.along[1] * v2B[1]) - 0.05;
+  e.dMaxLen = std::max(e.along[0] * v2A[0] + e.along[1] * v2A[1], e.along[0] * v2B[0] + e.along[1] * v2B[1]) + 0.05;
+  if (e.dMinLen < -2.0) e.dMinLen = -2.0;
+  if (e.dMaxLen < -2.0) e.dMaxLen = -2.0;
+  if (e.dMinLen > 2.0) e.dMinLen = 2.0;
+  if (e.dMaxLen > 2.0) e.dMaxLen = 2.0;
+  return e;
+}
+
 bool System::AddPointEpipolar(int ksrc, int ktgt, int nLevel, int nCandidate) {
   // :525-703
   KeyFrame& kSrc = *kfs[ksrc]; KeyFrame& kTarget = *kfs[ktgt];
@@ -147,40 +191,16 @@ bool System::AddPointEpipolar(int ksrc, int ktgt, int nLevel, int nCandidate) {
   int& why = grow_log.back();
   grow_detail.insert(grow_detail.end(), 6, 0);
   int* detail = &grow_detail[grow_detail.size() - 6];
+  grow_rival.insert(grow_rival.end(), 2, 0);
+  int* rival = &grow_rival[grow_rival.size() - 2];
   const int nLevelScale = level_scale(nLevel);
   const uint32_t cpos = kSrc.cand[nLevel][nCandidate];
   const double irLevelPos[2] = {(double)(cpos & 0xFFFF), (double)(cpos >> 16)};
-  const double v2RootPos[2] = {level_zero_pos(irLevelPos[0], nLevel), level_zero_pos(irLevelPos[1], nLevel)};
-  const V3 v3Ray_SC = unit_ray(camera, v2RootPos[0], v2RootPos[1]);
-  const V3 v3LineDirn_TC = rot(kTarget.pose, rot_inv(kSrc.pose, v3Ray_SC));
-  const double dMean = kSrc.depth_mean, dSigma = kSrc.depth_sigma;
-  const double dStartDepth = std::max(p.wiggle_scale, dMean - dSigma);
-  const double dEndDepth = std::min(40 * p.wiggle_scale, dMean + dSigma);
-  const SE3 srcInv = inverse(kSrc.pose);
-  const V3 v3CamCenter_TC = xform(kTarget.pose, v3(srcInv.t[0], srcInv.t[1], srcInv.t[2]));
-  V3 v3RayStart_TC, v3RayEnd_TC;
-  for (int i = 0; i < 3; i++) { v3RayStart_TC[i] = v3CamCenter_TC[i] + dStartDepth * v3LineDirn_TC[i]; v3RayEnd_TC[i] = v3CamCenter_TC[i] + dEndDepth * v3LineDirn_TC[i]; }
-  if (v3RayEnd_TC[2] <= v3RayStart_TC[2]) { why = 1; return false; }
-  if (v3RayEnd_TC[2] <= 0.0) { why = 1; return false; }
-  if (v3RayStart_TC[2] <= 0.0) {
-    detail[4] = 1;
-    const double f = 0.001 - v3RayStart_TC[2] / v3LineDirn_TC[2];
-    for (int i = 0; i < 3; i++) v3RayStart_TC[i] += v3LineDirn_TC[i] * f;
-  }
-  const double v2A[2] = {v3RayStart_TC[0] / v3RayStart_TC[2], v3RayStart_TC[1] / v3RayStart_TC[2]};
-  const double v2B[2] = {v3RayEnd_TC[0] / v3RayEnd_TC[2], v3RayEnd_TC[1] / v3RayEnd_TC[2]};
-  double along[2] = {v2A[0] - v2B[0], v2A[1] - v2B[1]};
-  if (along[0] * along[0] + along[1] * along[1] < 0.00000001) { why = 2; return false; }
-  { const double n = sqrt(along[0] * along[0] + along[1] * along[1]); along[0] /= n; along[1] /= n; }
-  const double normal[2] = {along[1], -along[0]};
-  const double dNormDist = v2A[0] * normal[0] + v2A[1] * normal[1];
-  if (fabs(dNormDist) > camera.largest_radius) { why = 3; return false; }
-  double dMinLen = std::min(along[0] * v2A[0] + along[1] * v2A[1], along[0] * v2B[0] + along[1] * v2B[1]) - 0.05;
-  double dMaxLen = std::max(along[0] * v2A[0] + along[1] * v2A[1], along[0] * v2B[0] + along[1] * v2B[1]) + 0.05;
-  if (dMinLen < -2.0) dMinLen = -2.0;
-  if (dMaxLen < -2.0) dMaxLen = -2.0;
-  if (dMinLen > 2.0) dMinLen = 2.0;
-  if (dMaxLen > 2.0) dMaxLen = 2.0;
+  const EpiLine line = epipolar_line(camera, kSrc.pose, kTarget.pose, irLevelPos[0], irLevelPos[1], nLevel, kSrc.depth_mean, kSrc.depth_sigma, p.wiggle_scale);   // :544-591
+  detail[4] = line.clipped;
+  if (line.why) { why = line.why; return false; }
+  const double v2RootPos[2] = {line.root[0], line.root[1]}, along[2] = {line.along[0], line.along[1]}, normal[2] = {line.normal[0], line.normal[1]};
+  const double dNormDist = line.dNormDist, dMinLen = line.dMinLen, dMaxLen = line.dMaxLen;
 
   Finder f;
   f.P = p.patch_size; f.max_ssd = 500 * p.patch_size * p.patch_size;   // jni/PatchFinder.cc:19-20
@@ -213,7 +233,7 @@ bool System::AddPointEpipolar(int ksrc, int ktgt, int nLevel, int nCandidate) {
     if (nInBlock > detail[1]) detail[1] = nInBlock;
     const int nZMSSD = finder_zmssd(f, kTarget.im[nLevel].data(), kTarget.w[nLevel], kTarget.h[nLevel], kTarget.w[nLevel], cx, cy);
     if (nZMSSD < nBestZMSSD) { nBest = (int)i; nBestZMSSD = nZMSSD; detail[3] = 0; detail[5] = nInBlock - 1; }
-    else if (nBest != -1 && nZMSSD == nBestZMSSD) detail[3] = 1;
+    else if (nBest != -1 && nZMSSD == nBestZMSSD) { detail[3] = 1; rival[0] = nInBlock - 1; rival[1] = (int)i / 64 == nBest / 64; }
   }
   if (nBest == -1) { why = 5; return false; }
 
@@ -255,13 +275,20 @@ bool System::ReFind_Common(int kidx, int pi) {
   KeyFrame& k = *kfs[kidx];
   MapPoint& pt = *pts[pi];
   if (pt.meas_kfs.count(kidx) || pt.never_retry.count(kidx)) return false;                       // :971-973
+  // an early return before the template (:979-996) is logged as an outcome of its own: 4 behind, 5 outside radius, 6 invalid projection, 7 outside image
+  auto early = [&](int outcome) {
+    const int rec[8] = {refind_job, kidx, pi, 0, -1, -1, outcome, refind_run};
+    refind_log.insert(refind_log.end(), rec, rec + 8);
+    pt.never_retry.insert(kidx);
+    return false;
+  };
   const V3 v3Cam = xform(k.pose, pt.pos);
-  if (v3Cam[2] < 0.001) { pt.never_retry.insert(kidx); return false; }                            // :979-982
+  if (v3Cam[2] < 0.001) return early(4);                                                          // :979-982
   const double ip0 = v3Cam[0] / v3Cam[2], ip1 = v3Cam[1] / v3Cam[2];
-  if (ip0 * ip0 + ip1 * ip1 > camera.largest_radius * camera.largest_radius) { pt.never_retry.insert(kidx); return false; }
+  if (ip0 * ip0 + ip1 * ip1 > camera.largest_radius * camera.largest_radius) return early(5);     // :985-988
   const Camera::Proj pr = camera.project(ip0, ip1);
-  if (pr.invalid) { pt.never_retry.insert(kidx); return false; }
-  if (pr.im[0] < 0 || pr.im[1] < 0 || pr.im[0] > k.w[0] || pr.im[1] > k.h[0]) { pt.never_retry.insert(kidx); return false; }
+  if (pr.invalid) return early(6);                                                                // :991-994
+  if (pr.im[0] < 0 || pr.im[1] < 0 || pr.im[0] > k.w[0] || pr.im[1] > k.h[0]) return early(7);    // :996-999
   double d[4];
   camera.derivs(pr, d);
   Finder& f = refinder;
@@ -352,12 +379,41 @@ extern "C" void orc_reproject_point(const double AfromB12[12], const double v2A[
   for (int i = 0; i < 3; i++) out3[i] = r[i];
 }
 
+// the twins of vslam_eval_epipolar (include/vslam_c.h), in its layouts
+extern "C" void orc_eval_epipolar(const double cam5[5], int w, int h, int quirks, int n, const double* lines30, int* flags2, double* out12) {
+  orc::Camera c; c.init(cam5, w, h, (quirks & ORC_Q_CAM_INT_RADIUS) != 0);
+  for (int i = 0; i < n; i++) {
+    const double* in = lines30 + 30 * (size_t)i;
+    orc::SE3 src, tgt;
+    for (int k = 0; k < 9; k++) { src.R[k] = in[k]; tgt.R[k] = in[12 + k]; }
+    for (int k = 0; k < 3; k++) { src.t[k] = in[9 + k]; tgt.t[k] = in[21 + k]; }
+    const orc::EpiLine e = orc::epipolar_line(c, src, tgt, in[24], in[25], (int)in[26], in[27], in[28], in[29]);
+    flags2[2 * i] = e.why; flags2[2 * i + 1] = e.clipped;
+    double* o = out12 + 12 * (size_t)i;
+    o[0] = e.root[0]; o[1] = e.root[1]; o[2] = e.along[0]; o[3] = e.along[1]; o[4] = e.normal[0]; o[5] = e.normal[1];
+    o[6] = e.dNormDist; o[7] = e.dMinLen; o[8] = e.dMaxLen; o[9] = e.startZ; o[10] = e.endZ; o[11] = e.alongSq;
+  }
+}
+
+extern "C" void orc_eval_triangulation(int n, const double* tri16, double* out7) {
+  for (int i = 0; i < n; i++) {
+    const double* in = tri16 + 16 * (size_t)i;
+    orc::SE3 T;
+    for (int k = 0; k < 9; k++) T.R[k] = in[k];
+    for (int k = 0; k < 3; k++) T.t[k] = in[9 + k];
+    orc::reproject_vector(T, in + 12, in + 14, out7 + 7 * (size_t)i);
+    const orc::V3 r = orc::reproject_point(T, in + 12, in + 14);
+    for (int k = 0; k < 3; k++) out7[7 * (size_t)i + 4 + k] = r[k];
+  }
+}
+
 static int copy_records(const std::vector<int>& v, int width, int* out, int cap) {
   const int n = (int)v.size() / width;
   for (int i = 0; i < n && i < cap; i++) for (int k = 0; k < width; k++) out[width * i + k] = v[(size_t)width * i + k];
   return n;
 }
 extern "C" int orc_sys_get_grow_detail(void* sys, int* out6, int cap) { return copy_records(((orc::System*)sys)->grow_detail, 6, out6, cap); }
+extern "C" int orc_sys_get_grow_rival(void* sys, int* out2, int cap) { return copy_records(((orc::System*)sys)->grow_rival, 2, out2, cap); }
 extern "C" int orc_sys_get_refind_log(void* sys, int* out8, int cap) { return copy_records(((orc::System*)sys)->refind_log, 8, out8, cap); }
 
 extern "C" int orc_sys_get_grow_log(void* sys, int* out3, int cap) {

@@ -209,3 +209,18 @@ bool finder_iterate_subpix_to_convergence(Finder& f, const KeyFrame& kf, int nMa
 }
 
 }  // namespace orc
+
+// FindPatchCoarse's window on its own (tests/test_grow_cases.py: the window of a projection that :996 of ReFind_Common lets through never lies
+// outside its level): the image's keyframe, a flat 8x8 template at `level`, one finder_find_coarse call at the level-0 position (im_x, im_y)
+// -> the list span of the window, -1 when the window lies outside the level's rows
+extern "C" int orc_find_coarse_span(const uint8_t* gray, int w, int h, int level, double im_x, double im_y, int range) {
+  orc::KeyFrame k;
+  const int thr[4] = {10, 15, 15, 10};
+  orc::make_keyframe_lite(k, gray, w, h, w, thr);
+  orc::Finder f;
+  f.P = 8; f.max_ssd = 500 * 64; f.level = level;
+  f.tmpl.assign(64, 128); f.tsum = 64 * 128; f.tsumsq = 64 * 128 * 128;
+  const double pos[2] = {im_x, im_y};
+  orc::finder_find_coarse(f, pos, k, (unsigned)range);
+  return f.span;
+}

@@ -164,9 +164,17 @@ int orc_sys_get_grow_log(void* sys, int* out3, int cap);
  * 1 if the start of the ray was clipped to the image plane (:565-568), the rank of the minimum among the survivors of its block (0 = the first).
  * Zeros for what a call did not reach. */
 int orc_sys_get_grow_detail(void* sys, int* out6, int cap);
+/* and one record of 2 per call about the last equal rival of the minimum: its rank among the survivors of its block of 64 list entries, 1 if that
+ * block is the minimum's.  Zeros without a rival. */
+int orc_sys_get_grow_rival(void* sys, int* out2, int cap);
+/* PatchFinder::FindPatchCoarse (jni/PatchFinder.cc:170-235) once, on the keyframe made of the w x h image, with a flat 8x8 template at `level`, at the
+ * level-0 position (im_x, im_y): the list span of its search window, or -1 when the window lies outside the level's rows */
+int orc_find_coarse_span(const uint8_t* gray, int w, int h, int level, double im_x, double im_y, int range);
 /* every ReFind_Common call that reached the template (jni/MapMaker.cc:1000), 8 per record: job (0 ReFindInSingleKeyFrame, 1 ReFindNewlyMade,
  * 2 ReFindFromFailureQueue), keyframe, point, 1 if MakeTemplateCoarseCont kept the previous template, search level, list span of the FindPatchCoarse
- * window (-1: none), outcome (0 measured, 1 template bad, 2 window outside the level's rows, 3 no corner scored below the limit), run number of the job */
+ * window (-1: none), outcome (0 measured, 1 template bad, 2 window outside the level's rows, 3 no corner scored below the limit), run number of the job.
+ * Also every call that passed the sMeasurementKFs / sNeverRetryKFs test and returned before the template (:979-996), with kept 0, level -1, span -1 and
+ * outcome 4 behind the keyframe, 5 outside largest_radius, 6 invalid projection, 7 outside the image */
 int orc_sys_get_refind_log(void* sys, int* out8, int cap);
 int orc_sys_bundle_adjust_recent(void* sys);   /* MapMaker::BundleAdjustRecent, jni/MapMaker.cc:801-851 */
 int orc_sys_bundle_adjust_all(void* sys);      /* MapMaker::BundleAdjustAll,    jni/MapMaker.cc:776-798 */
@@ -191,6 +199,10 @@ void orc_sbi_rotation(const uint8_t* cur_l3, const uint8_t* last_l3, int w3, int
 
 /* MapMaker::ReprojectPoint (jni/MapMaker.cc:174-200): point in frame B from its z = 1 projections in A and B; AfromB 12 doubles */
 void orc_reproject_point(const double AfromB12[12], const double v2A[2], const double v2B[2], double out3[3]);
+/* the line geometry of AddPointEpipolar (jni/MapMaker.cc:544-591) and the triangulation on their own, laid out as vslam_eval_epipolar's
+ * (include/vslam_c.h): 30 doubles in, (why, clipped) and 12 doubles out per line case; 16 doubles in, 7 out per triangulation */
+void orc_eval_epipolar(const double cam5[5], int w, int h, int quirks, int n, const double* lines30, int* flags2, double* out12);
+void orc_eval_triangulation(int n, const double* tri16, double* out7);
 
 /* ---- stand-alone Bundle (jni/Bundle.h:111-121) --------------------------------------------------- */
 void* orc_ba_create(const double cam5[5], int width, int height, int quirks, int max_iterations, double convergence_limit, double min_sigma);

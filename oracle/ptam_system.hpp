@@ -174,9 +174,12 @@ struct System {
   // entries, the blocks that hold one, the strict minimum had an equal-ZMSSD rival later in the list, the ray start was clipped (:565-568),
   // the rank of the minimum among the survivors of its block
   std::vector<int> grow_detail;
+  std::vector<int> grow_rival;   // per call, of the last equal rival of the minimum: its rank among the survivors of its block, 1 if that block is the minimum's
   // per ReFind_Common call that reaches the template: job (0 ReFindInSingleKeyFrame, 1 ReFindNewlyMade, 2 ReFindFromFailureQueue), keyframe,
   // point, MakeTemplateCoarseCont kept the previous template, search level, list span of the FindPatchCoarse window (-1: outside the rows),
-  // outcome (0 measured, 1 template bad :1004, 2 window outside the level :1009, 3 no corner scored below the limit :1009), the job's run number
+  // outcome (0 measured, 1 template bad :1004, 2 window outside the level :1009, 3 no corner scored below the limit :1009), the job's run number.
+  // A call that passes the sMeasurementKFs / sNeverRetryKFs test and returns before the template is a record too, with no template, level -1 and
+  // no window: outcome 4 behind (:979), 5 outside largest_radius (:985), 6 invalid projection (:991), 7 outside the image (:996)
   std::vector<int> refind_log;
   int refind_job = 0, refind_run = 0;
   int BundleAdjust(const std::vector<int>& adj, const std::vector<int>& fixed, const std::vector<int>& points, bool recent);
@@ -219,7 +222,11 @@ void make_keyframe_lite(KeyFrame& k, const uint8_t* gray, int w, int h, int stri
 void make_keyframe_rest_nonmax(KeyFrame& k, int barrier, bool quirk);
 void make_keyframe_rest_candidates(KeyFrame& k, double min_score);
 V3 reproject_point(const SE3& AfromB, const double v2A[2], const double v2B[2]);
+void reproject_vector(const SE3& AfromB, const double v2A[2], const double v2B[2], double v[4]);   // the homogeneous vector reproject_point divides
 void svd4_smallest_right_vector(const double A[16], double out[4]);
+// the search line of AddPointEpipolar (jni/MapMaker.cc:544-591); fields and exits as csrc/grow_dev.h EpiLine
+struct EpiLine { int why, clipped; double root[2], along[2], normal[2], dNormDist, dMinLen, dMaxLen, startZ, endZ, alongSq; };
+EpiLine epipolar_line(const Camera& camera, const SE3& src, const SE3& tgt, double irx, double iry, int nLevel, double dMean, double dSigma, double wiggle_scale);
 
 // PatchFinder pieces exposed for unit tests
 int transform_image(const uint8_t* in, int iw, int ih, int istride, uint8_t* out, int P, const double M[4],

@@ -96,6 +96,26 @@ int main() {
     std::printf("stand-alone bundle: %d accepted, %ld trials, %zu outlier measurements\n", acc, b.n_trials, b.outlier_meas.size());
     if (acc < 0) return 4;
   }
+  // the epipolar line at every exit and the triangulation's degenerate inputs (tests/epipolar_cases.py holds the full set)
+  {
+    SE3 I{}; I.R[0] = I.R[4] = I.R[8] = 1.0;
+    int exits[4] = {0, 0, 0, 0}, clipped = 0;
+    for (int i = 0; i < 64; i++) {
+      SE3 tgt = I;
+      const double a = 0.4 * (i % 8) - 1.4;                                     // the target turned about its vertical axis, moved about
+      tgt.R[0] = cos(a); tgt.R[2] = sin(a); tgt.R[6] = -sin(a); tgt.R[8] = cos(a);
+      tgt.t[0] = 0.3 * ((i / 8) % 3) - 0.3; tgt.t[1] = 0.05 * (i % 3); tgt.t[2] = (i / 24) * -1.0;
+      const EpiLine e = epipolar_line(sys.camera, I, tgt, 20.0 + 30 * (i % 5), 15.0 + 20 * (i % 4), i % 4 ? 0 : 1, 2.0, 0.5, i % 7 ? 0.1 : 0.02);
+      exits[e.why]++; clipped += e.clipped;
+    }
+    const double zero[2] = {0.0, 0.0}, ray[2] = {0.3, -0.2};
+    double v[4];
+    SE3 Z{};                                                                    // not a motion: a zero matrix below the two fixed rows
+    const V3 p0 = reproject_point(I, zero, zero), p1 = reproject_point(I, ray, ray), p2 = reproject_point(Z, zero, ray);
+    reproject_vector(I, zero, zero, v);
+    std::printf("epipolar exits %d %d %d %d, %d clipped; degenerate triangulations %g %g %g, v[3] %g\n", exits[0], exits[1], exits[2], exits[3], clipped, p0[2], p1[2], p2[2], v[3]);
+    if (!exits[0] || !exits[1] || !exits[2] || !exits[3] || !clipped || v[3] != 0.0) { std::fprintf(stderr, "selftest: the epipolar cases miss their exits\n"); vslam_feeder_destroy(f); return 5; }
+  }
   vslam_feeder_destroy(f);
   return 0;
 }

@@ -13,10 +13,31 @@ A Case is a scene key, a sub-map, parameters, a start pose, an optional own fram
 streams of one System.  Every case runs one tracked frame that becomes a keyframe, the four idle jobs in order, and a second tracked
 frame (record()).  Everything is derived from the oracle, nothing from the device.
 
-What stays unreached in every case (test_grow_cases.py asserts the counts are zero, so that a change that reaches one is noticed):
-stage 3 (the line outside largest_radius), stage 4 (candidates keep a border of 10 pixels, the template needs P / 2 + 1), an equal-ZMSSD
-tie at the strict minimum of the epipolar search, the start-depth clip (v3RayStart_TC[2] <= 0), a stored corner list cut at
-16384 / 8192 / 4096 / 2048 entries, and a failure queue beyond its 8192 entries.  No scene is built for any of these."""
+Group e reaches what a to d leave out.  Stage 3 (the line outside largest_radius): the target keyframe is a map keyframe placed 0.03
+from the camera of frame 0 and turned 20 or 30 degrees about its vertical axis, so that the lines of the candidates on the far side pass
+outside the radius while those on the near side are searched and accepted in the same levels.  ReFind_Common's early return "behind"
+(v3Cam[2] < 0.001): map points moved behind the new keyframe.  Its early returns "outside radius" and "outside image" are reached by
+group b already (the oracle's re-find log names them since it records the calls that return before the template).  An equal-ZMSSD tie at
+the strict minimum of the epipolar search, on an accepted call: a block of texture repeated inside the target keyframe's image along a
+candidate's line (TIES); the first of the two in list order must win, which the new point and its measurement show.  The start-depth
+clip (v3RayStart_TC[2] <= 0): the source camera must stand behind the target's image plane by more than dStartDepth dirn[2] and less than
+dEndDepth dirn[2].  Zooming out alone (0.4 to 0.8 of the scene's distance, sub-map and full map) never reaches it, nor does a tilt of 15
+to 35 degrees alone: the scene depth's sigma is 0.01 when the camera faces the plane, so the window between the two depths is too narrow.
+Zoomed out to 0.7 and tilted -35 degrees (also 0.5 with +-35) the sigma is wide enough and hundreds of lines are clipped, seven of them
+accepted; a target turned 80 degrees and placed 0.04 ahead of a camera tilted 25 degrees clips a few lines whose dirn[2] is a few hundredths.
+
+What stays unreached in every case (test_grow_cases.py asserts the counts are zero, so that a change that reaches one is noticed), and why:
+- stage 4.  Candidates keep a border of 10 level pixels (orc_candidates(..., 10, ...), jni/KeyFrame.cc:66-95); MakeTemplateCoarseNoWarp
+  needs P / 2 + 1 <= 6 for P = 8 and 11.  No candidate can fail it.
+- "window outside" in ReFind_Common.  FindPatchCoarse's range at level l is ceil(4 / 2^l) >= 1, and :996 has bounded the projection by the
+  image: 0 <= im_y <= h_0, so 0 <= iry = im_y / 2^l <= h_0 / 2^l.  Then top = int(iry - range) <= floor(h_0 / 2^l - 1) =
+  (h_0 >> l) - 1 < rows (a negative top is clamped to 0 < rows), and bottom_plus_one = int(iry + range + 1) >= 2 > 0.
+  test_grow_cases.py checks both at 320x240 and at the odd size 131x77 of search_trip_cases.py, where h_0 / 2^l is no integer.
+- "invalid projection" in ReFind_Common (:991).  invalid means r > 1.5 largest_radius, and :985 has already turned away every point with
+  x^2 + y^2 > largest_radius^2: with largest_radius >= 0, r = sqrt(x^2 + y^2) <= largest_radius (1 + 2^-52) < 1.5 largest_radius, or
+  r = 0 = largest_radius with quirks = 1.  Only an out-of-model calibration (largest_radius < 0, cam_cases.OUT_OF_MODEL), with which
+  nothing is ever searched, can take it.
+- a stored corner list cut at 16384 / 8192 / 4096 / 2048 entries, and a failure queue beyond its 8192 entries."""
 import functools
 
 import numpy as np
@@ -47,14 +68,67 @@ def _levels(rects=None):
     return np.array([q["level"] for q in scene(rects)[1]["points"]])
 
 
+def with_turned_keyframe(m, f, degrees, offset, pose12=None):
+    """the map with one more keyframe at the end: the camera of frame 0 turned by `degrees` about its own vertical axis and moved by
+    `offset` along it, its image rendered there by the feeder.  ClosestKeyFrame looks at camera centres only (jni/MapMaker.cc:737-758), so
+    this keyframe is the target of the epipolar search; the vertical baseline makes every epipolar line vertical in its image plane, at
+    the horizontal position of the candidate's ray: tan(angle of the ray + degrees), outside largest_radius for the candidates on the far side."""
+    p = np.asarray(f.pose(0) if pose12 is None else pose12, np.float64)      # (pose12: the camera of a case that renders its own frames)
+    a = np.deg2rad(degrees)
+    Ry = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+    R, t = Ry @ p[:9].reshape(3, 3), Ry @ p[9:] + (np.array([0.0, offset, 0.0]) if np.isscalar(offset) else np.asarray(offset, np.float64))
+    pose = np.r_[R.ravel(), t]
+    kf = {"pose": pose, "fixed": False, "image": f.render_pose(pose, key=2000), "depth_mean": m["keyframes"][-1]["depth_mean"],
+          "depth_sigma": m["keyframes"][-1]["depth_sigma"]}
+    return {"keyframes": list(m["keyframes"]) + [kf], "points": m["points"], "meas": m["meas"]}
+
+
+def closest_keyframe(m, pose12):
+    """ClosestKeyFrame by camera centres (jni/MapMaker.cc:737-758) among the map's keyframes, for a camera at pose12"""
+    def centre(p):
+        p = np.asarray(p, np.float64)
+        return -p[:9].reshape(3, 3).T @ p[9:]
+    return int(np.argmin([np.linalg.norm(centre(kf["pose"]) - centre(pose12)) for kf in m["keyframes"]]))
+
+
+def with_repeated_block(m, pose12, cx, cy, half, dx, dy):
+    """the map with a block of texture repeated inside the image of the keyframe nearest to the camera at pose12, as search_trip_cases.py
+    repeats one inside a frame: the (2 half + 1)^2 pixels around (cx, cy) are copied to (cx + dx, cy + dy).  |dx| or |dy| exceeds the
+    block's side, so the source stays whole.  A corner at (cx, cy) then has a twin with the same neighbourhood: the same FAST verdict and
+    the same ZMSSD against any template, so a candidate whose epipolar line holds both meets an equal minimum."""
+    assert max(abs(dx), abs(dy)) > 2 * half
+    k = closest_keyframe(m, pose12)
+    kfs = [dict(kf) for kf in m["keyframes"]]
+    img = np.array(kfs[k]["image"], np.uint8, copy=True)
+    img[cy + dy - half:cy + dy + half + 1, cx + dx - half:cx + dx + half + 1] = img[cy - half:cy + half + 1, cx - half:cx + half + 1]
+    kfs[k]["image"] = img
+    return {"keyframes": kfs, "points": m["points"], "meas": m["meas"]}
+
+
+def with_points_behind(m, pose12, n):
+    """the map with its last n points moved behind the camera at pose12 (1.5 behind its centre, spread sideways) and without measurements:
+    ReFindInSingleKeyFrame meets them in the new keyframe and leaves at v3Cam[2] < 0.001 (jni/MapMaker.cc:979)"""
+    R, t = np.asarray(pose12[:9], np.float64).reshape(3, 3), np.asarray(pose12[9:], np.float64)
+    pts = [dict(q) for q in m["points"]]
+    moved = set(range(len(pts) - n, len(pts)))
+    for j, i in enumerate(sorted(moved)):
+        pts[i]["pos"] = R.T @ (np.array([0.2 * j - 0.1, 0.1 * j, -1.5]) - t)
+    return {"keyframes": m["keyframes"], "points": pts, "meas": [x for x in m["meas"] if x[1] not in moved]}
+
+
 class Case:
     """keep: None = the full map, "no map" = nothing loaded, else the indices of the sub-map.  at_kf: the start pose is that map
     keyframe's and both frames are rendered there.  zoom: the start pose is the scene's moved along the optical axis to 1 / zoom of its
     distance from the plane, frames rendered there.  kf_request = False: the tracker has just dropped a keyframe, so it asks for none."""
 
-    def __init__(self, name, keep=None, pkw=BASE, rects=None, at_kf=None, zoom=None, kf_request=True, target=None):
+    def __init__(self, name, keep=None, pkw=BASE, rects=None, at_kf=None, zoom=None, kf_request=True, target=None, turned_kf=None, behind=0, repeat=None, oblique=None):
+        """turned_kf = (degrees, offset): one more map keyframe, without measurements, at the pose of frame 0 turned about the camera's
+        vertical axis and moved along it by offset (group e).  behind: that many points of the sub-map, its last, are moved behind
+        the camera of frame 0 and lose their measurements (group e)."""
         self.name, self.pkw, self.rects, self.at_kf, self.zoom, self.kf_request, self.target = name, tuple(pkw), rects, at_kf, zoom, kf_request, dict(target or {})
         self.keep = keep if keep is None or isinstance(keep, str) else np.asarray(keep, np.int64)
+        self.oblique = oblique          # degrees: the start pose (after zoom) turned in place about the camera's horizontal axis, frames rendered there
+        self.turned_kf, self.behind, self.repeat = turned_kf, behind, repeat           # repeat = (cx, cy, half, dx, dy): with_repeated_block
         self._map, self._frames = None, {}
 
     @property
@@ -69,16 +143,31 @@ class Case:
         if self._map is None:
             m = scene(self.rects)[1]
             self._map = m if self.keep is None else sub_map(m, self.keep)
+            if self.turned_kf is not None:
+                self._map = with_turned_keyframe(self._map, scene(self.rects)[0], *self.turned_kf, pose12=self.start_pose() if self.own_frames else None)
+            if self.behind:
+                self._map = with_points_behind(self._map, scene(self.rects)[0].pose(0), self.behind)
+            if self.repeat is not None:
+                self._map = with_repeated_block(self._map, scene(self.rects)[0].pose(0), *self.repeat)
         return self._map
+
+    @property
+    def own_frames(self):
+        return not (self.at_kf is None and self.zoom is None and self.oblique is None)
 
     def start_pose(self):
         f, m, _frames = scene(self.rects)
-        if self.zoom is not None:
-            return _zoomed(f.pose(-1), self.zoom)
+        if self.zoom is not None or self.oblique is not None:
+            p = np.asarray(f.pose(-1), np.float64) if self.zoom is None else _zoomed(f.pose(-1), self.zoom)
+            if self.oblique is not None:
+                a = np.deg2rad(self.oblique)
+                Rx = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(a), -np.sin(a)], [0.0, np.sin(a), np.cos(a)]])
+                p = np.r_[(Rx @ p[:9].reshape(3, 3)).ravel(), Rx @ p[9:]]
+            return p
         return f.pose(-1) if self.at_kf is None else np.asarray(m["keyframes"][self.at_kf]["pose"], np.float64)
 
     def frame(self, t):
-        if self.at_kf is None and self.zoom is None:
+        if not self.own_frames:
             return scene(self.rects)[2][t]
         if t not in self._frames:
             self._frames[t] = scene(self.rects)[0].render_pose(self.start_pose(), key=t)
@@ -251,9 +340,55 @@ def group_d(patch):
             _fills_during(patch, "first 200 points", np.arange(200), 0), exact_fit_case(patch), mid_chunk_case(patch)]
 
 
-GROUP_NAMES = ("a: epipolar counts", "b: re-find", "c: stage 1", "c: stage 2", "d: map capacity")
+# ---- group E: epipolar exits and the re-find's early returns ---------------------------------------------------------------------------
+E_PKW = _with(BASE, max_kf_dist_wiggle_mult=0.0)           # the keyframe request passes although a map keyframe stands 0.03 from the camera
+TURNED_OFFSET = 0.03                                       # nearer than any keyframe of the scene (at 0.06 one of those is the target again)
+BEHIND = 3
+
+
+@functools.lru_cache(maxsize=None)
+def group_e():
+    """Two streams whose target keyframe is the camera of frame 0 turned about its vertical axis (with_turned_keyframe): the candidates
+    on the far side leave at stage 3, those on the near side are searched in the turned image and some are accepted, at levels 0 to 2.
+    Turned the other way the far side is the other half of the image.  The third stream holds BEHIND points behind the new keyframe
+    (with_points_behind), which ReFindInSingleKeyFrame turns away at its first early return.  Five streams with a repeated block in the
+    target keyframe's image (TIES): an equal minimum on an accepted call.  Two streams that reach the start-depth clip."""
+    n = len(_levels())
+    keep = np.arange(0, n, 8)
+    return [Case("target turned 20 degrees", keep, E_PKW, turned_kf=(20.0, TURNED_OFFSET), target=dict(stage3_levels=(0, 1, 2))),
+            Case("target turned -30 degrees", keep, E_PKW, turned_kf=(-30.0, TURNED_OFFSET), target=dict(stage3_levels=(0, 1, 2))),
+            Case("%d points behind the new keyframe" % BEHIND, keep, E_PKW, behind=BEHIND, target=dict(behind=BEHIND))] + [
+            Case("tie: block at (%d, %d) repeated at (%+d, %+d)" % (cx, cy, dx, dy), keep, E_PKW, repeat=(cx, cy, half, dx, dy), target=dict(tie=want))
+            for (cx, cy, half, dx, dy), want in TIES] + [
+            # the clip.  Zoomed out to 0.7 and tilted 35 degrees the camera stands behind the image planes of the map's keyframes, and the
+            # tilt spreads the scene depth enough for the ray to start behind the target's plane and end in front of it: hundreds of
+            # clipped lines, a few of them matched and accepted.  Tilted 25 degrees the other way, with a target turned 80 degrees and
+            # 0.04 ahead of the camera: dirn[2] is a few hundredths, the clipped lines leave at stage 5 (at 8x8 some at stage 3).
+            # (Without the clip those few calls would leave at stage 5 as well: only the first case tells a missing clip apart; the
+            # arithmetic with a small dirn[2] is compared bit for bit by tests/epipolar_cases.py.)
+            Case("clip: zoomed out to 0.7, tilted -35 degrees", keep, E_PKW, zoom=0.7, oblique=-35.0, target=dict(clip_stages=(0, 5))),
+            Case("clip: tilted 25 degrees, target turned 80 degrees and 0.04 ahead", keep, E_PKW, oblique=25.0, turned_kf=(80.0, (0.0, 0.02, -0.04)),
+                 target=dict(clip_stages=(5,)))]
+
+
+# The ties.  An accepted level-0 candidate of the every-8th sub-map is matched, in the target keyframe (the map's last), at the FAST corner
+# (cx, cy); the epipolar lines there run along (0.96, -0.27) and the search window reaches 13 pixels beyond the segment's ends.  The block
+# around the corner is repeated 13 pixels along the line (with_repeated_block), so the corner and its twin both pass the line filter and score
+# the same ZMSSD, the minimum.  want = per patch size (rank of the first of the two among the survivors of its block of 64 list entries,
+# rank of the second, the two share a block), found on the oracle (test_grow_cases.py asserts them): with 8 patches scored per step at 8x8 and
+# 4 at 11x11 the first case has both rivals in one step at 8x8 and in neighbouring steps at 11x11, the second in two steps at both sizes, the
+# third in two blocks of 64, that is in two ballots, the fourth in the first step at both sizes (ranks 0 and 3), the fifth in the first
+# step at 8x8 and in the second at 11x11 (ranks 5 and 7).
+TIES = (((237, 13, 6, 13, -4), {8: (1, 4, 1), 11: (1, 4, 1)}),
+        ((162, 13, 6, 13, -4), {8: (5, 8, 1), 11: (5, 8, 1)}),
+        ((237, 13, 5, -11, 3), {8: (1, 1, 0), 11: (1, 1, 0)}),
+        ((256, 46, 5, 11, -3), {8: (0, 3, 1), 11: (0, 3, 1)}),
+        ((114, 17, 5, -11, 2), {8: (5, 7, 1), 11: (5, 7, 1)}))
+
+
+GROUP_NAMES = ("a: epipolar counts", "b: re-find", "c: stage 1", "c: stage 2", "d: map capacity", "e: epipolar exits")
 
 
 def groups(patch):
     return {"a: epipolar counts": group_a(), "b: re-find": group_b(), "c: stage 1": group_c("stage 1"), "c: stage 2": group_c("stage 2"),
-            "d: map capacity": group_d(patch)}
+            "d: map capacity": group_d(patch), "e: epipolar exits": group_e()}

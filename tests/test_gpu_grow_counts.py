@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import grow_cases as gc
+import retire_ref as rr
 from helpers import assert_map_exact, assert_tracker_exact
 from visualslam_android_amd import capi
 
@@ -38,7 +39,19 @@ def assert_candidates_exact(o, g, s, tag, vouched):
         assert np.array_equal(stage, rows[:, 2]), (tag, l, [(int(i), int(a), int(b)) for i, (a, b) in enumerate(zip(stage, rows[:, 2])) if a != b][:8])
 
 
-def run_group(cases, patch):
+def assert_never_retry_exact(o, g, s, tag):
+    """sNeverRetryKFs of every point: the oracle's sets against the device's 128-bit words, read from a snapshot of the stream.  The
+    measurement tables alone show a wrong bit only if a later job happens to retry the pair."""
+    _h, secs = rr.sections(g.snapshot(s))
+    dev = secs[rr.NEVER_RETRY].view(np.uint64).reshape(-1, 2)
+    want = o.point_mapmaker_data()["never_retry"]
+    assert dev.shape == want.shape and np.array_equal(dev, want), (tag, dev.shape, want.shape, np.flatnonzero((dev != want).any(1))[:8].tolist() if dev.shape == want.shape else None)
+    return int(np.sum([bin(int(v)).count("1") for v in want.ravel()]))
+
+
+def run_group(cases, patch, never_retry=False):
+    """never_retry: also compare the never-retry sets after the keyframe and after each idle job -> the bits set at the end, per stream"""
+    bits = {}
     S = len(cases)
     assert all(c.pkw == cases[0].pkw for c in cases)                                      # the parameters are system-wide
     g = capi.System(cases[0].params(S, patch))
@@ -69,6 +82,8 @@ def run_group(cases, patch):
         assert_tables_exact(o, g, s, tag)
         assert_map_exact(o, g, s, tag)
         assert_tracker_exact(o, g, s, tag)
+        if never_retry:
+            assert_never_retry_exact(o, g, s, tag)
     for job in range(4):
         g.mapmaker_idle_job(job)
         for s, c, o, tag in tags("idle job %d" % job):
@@ -80,6 +95,8 @@ def run_group(cases, patch):
             assert g.idle_stats(s) == o.idle_stats(), (tag, g.idle_stats(s), o.idle_stats())
             assert_tables_exact(o, g, s, tag)
             assert_map_exact(o, g, s, tag)
+            if never_retry:
+                bits[s] = assert_never_retry_exact(o, g, s, tag)
     g.track_frame(np.stack([c.frame(1) for c in cases]))
     for s, c, o, tag in tags("frame 1"):
         if o is None:
@@ -92,6 +109,7 @@ def run_group(cases, patch):
         assert_map_exact(o, g, s, tag)
         o.close()
     g.close()
+    return bits
 
 
 @pytest.mark.parametrize("patch", [8, 11])
@@ -111,8 +129,11 @@ def test_refind_at_every_level_and_window_length(patch):
     hundreds of points at levels 0 to 2 and a few at level 3 (the sub-pixel iterations whose result nobody checks), in windows of up to 161
     list entries (three passes of refind_common's loop) found through the row table, and ReFindNewlyMade in windows of up to 130 found by
     the binary search.  The fourth stream sees every 8th point from twice as close: its new level-0 points have a bad scale in the map's
-    keyframes, so the kept template of ReFindNewlyMade answers bad (RefindCache's bad_scale ? true : prev_bad) dozens of times."""
-    run_group(gc.groups(patch)["b: re-find"], patch)
+    keyframes, so the kept template of ReFindNewlyMade answers bad (RefindCache's bad_scale ? true : prev_bad) dozens of times.  The
+    never-retry sets are compared after the keyframe and after every idle job: the returns of refind_common before the template (outside
+    largest_radius, outside the image) set a bit and nothing else, so only the sets show them."""
+    bits = run_group(gc.groups(patch)["b: re-find"], patch, never_retry=True)
+    assert len(bits) == 4 and min(bits.values()) >= 100, bits                            # the sets compared are not empty
 
 
 @pytest.mark.parametrize("patch", [8, 11])
@@ -133,3 +154,21 @@ def test_map_that_fills_during_growth(patch):
     cases = gc.groups(patch)["d: map capacity"]
     assert cases[0].params(1, patch).max_points == gc.MAX_POINTS
     run_group(cases, patch)
+
+
+@pytest.mark.parametrize("patch", [8, 11])
+def test_epipolar_exits_and_refind_behind(patch):
+    """Group e, ten streams.  Two whose target keyframe is the camera of frame 0 turned 20 and -30 degrees about its vertical axis:
+    dozens of candidates at levels 0 to 2 leave at stage 3 (the line passes outside largest_radius; with +20 degrees dNormDist has one sign,
+    with -30 the other) beside accepted candidates in the same chunks, and the codes, the new points and the tables == the oracle's.  One
+    with three map points behind the new keyframe: refind_common's first early return, which writes a never-retry bit and nothing else.
+    Five with a block of texture repeated in the target keyframe's image, so that an accepted candidate meets two corners of equal ZMSSD at
+    its minimum -- in one step of k_epipolar's ballot (the first step at both patch sizes, the second at 11x11), in two steps, in two
+    ballots: the first in list order must win, and the new point's position and its measurement in the target keyframe (compared bit for
+    bit) are the twin's otherwise.  Two that reach the start-depth clip inside k_epipolar: a camera zoomed out and tilted 35 degrees, with
+    hundreds of clipped lines of which a few are matched and accepted, and a tilted camera whose target is turned 80 degrees and stands
+    0.04 ahead of it (dirn[2] of a few hundredths in the re-start's division).
+    The never-retry sets are compared after the keyframe and after every idle job."""
+    cases = gc.groups(patch)["e: epipolar exits"]
+    bits = run_group(cases, patch, never_retry=True)
+    assert len(bits) == len(cases) == 5 + len(gc.TIES) and min(bits.values()) >= gc.BEHIND, bits

@@ -8,11 +8,19 @@ one step of k_epipolar scores, up to four steps (the winner in the second step a
 keyframe measured at every level; search windows longer than 64 and 128 list entries; hundreds of kept templates in ReFindNewlyMade, some
 with a bad verdict.
 
+Group e: stage 3 beside accepted calls at levels 0 to 2 (a target keyframe turned about its vertical axis, both ways); an equal-ZMSSD tie
+at the minimum of an accepted call, the two rivals in one step of the ballot (the first step at both patch sizes, a later one at 11x11),
+in two steps and in two ballots (a block of texture repeated inside the target keyframe's image); the start-depth clip, on hundreds of
+calls of which a few are accepted (a camera zoomed out and tilted) and with a small dirn[2] (a tilted camera, the target turned 80
+degrees and ahead of it); ReFind_Common's return "behind".  Its returns "outside radius" and "outside image" are reached by group b, in the new keyframe and in the
+map's keyframes (the oracle's re-find log records the calls that return before the template as outcomes of their own).
+
 Not reached: at 8x8 a winner scored in the third or fourth step of its ballot (test_group_a prints the steps).  Not reached, and asserted to be
-absent so that a change that reaches one is noticed: stage 3, stage 4, an equal-ZMSSD tie at the
-minimum, the start-depth clip (module docstring of grow_cases.py); of ReFind_Common's early returns, a search window outside the rows of
-its level (the projection has been tested against the image before, jni/MapMaker.cc:996); a kept template in ReFindFromFailureQueue (the
-queue is sorted by keyframe first, neighbours are different points) and one kept across two jobs."""
+absent so that a change that reaches one is noticed: stage 3, an equal-ZMSSD tie at the minimum and the start-depth clip outside group e,
+stage 4; of ReFind_Common's returns, the invalid projection and a search window outside the rows of its level (the module docstring of
+grow_cases.py gives the reason for each; test_refind_window_never_lies_outside_its_level runs the oracle's FindPatchCoarse at the
+image's edges for the last one); a kept template
+in ReFindFromFailureQueue (the queue is sorted by keyframe first, neighbours are different points) and one kept across two jobs."""
 import numpy as np
 import pytest
 
@@ -21,6 +29,13 @@ import oracle.binding as orc
 
 OUTCOME = {name: i for i, name in enumerate(orc.OracleSystem.REFIND_OUTCOMES)}
 JOB = {name: i for i, name in enumerate(orc.OracleSystem.REFIND_JOBS)}
+EARLY = orc.OracleSystem.REFIND_EARLY                            # outcomes from here on returned before the template
+
+
+def template_calls(rf):
+    """the records of the calls that reached the template"""
+    m = rf["outcome"] < EARLY
+    return {k: v[m] for k, v in rf.items()}
 
 
 def describe(case, r, patch):
@@ -33,9 +48,12 @@ def describe(case, r, patch):
     for job, name in enumerate(orc.OracleSystem.REFIND_JOBS):
         jm = rf["job"] == job
         if jm.any():
+            line += "\n      %s: early returns %s" % (name, {k: int((jm & (rf["outcome"] == v)).sum()) for k, v in OUTCOME.items() if v >= EARLY})
+        jm = jm & (rf["outcome"] < EARLY)
+        if jm.any():
             line += "\n      %s: %d template calls, measured per level %s, outcomes %s, kept templates %d (bad %d), longest window %d" % (
                 name, int(jm.sum()), [int((jm & (rf["outcome"] == 0) & (rf["level"] == l)).sum()) for l in range(4)],
-                {k: int((jm & (rf["outcome"] == v)).sum()) for k, v in OUTCOME.items()}, int((jm & (rf["hit"] == 1)).sum()),
+                {k: int((jm & (rf["outcome"] == v)).sum()) for k, v in OUTCOME.items() if v < EARLY}, int((jm & (rf["hit"] == 1)).sum()),
                 int((jm & (rf["hit"] == 1) & (rf["outcome"] == OUTCOME["template bad"])).sum()), int(rf["span"][jm].max()))
     return line + "\n      idle: %s; second frame: quality %d, found %s" % (r.idle, r.quality1, r.found1)
 
@@ -52,10 +70,13 @@ def records(group, patch, verbose=True):
         assert (r.kf_added, r.kf_added1, r.n_keyframes - r.kf0) == (int(c.grows), 0, int(c.grows)), c.name
         assert r.quality0 == r.quality1 == 2 and r.n_points1 == r.n_points, c.name
         assert r.idle["new_queue"] == 0 and r.idle["failure_queue"] <= 8192, (c.name, r.idle)
-        for k in (3, 4):                                         # the unreached stages stay unreached
-            assert r.stages().get(k, 0) == 0, (c.name, r.stages())
-        assert r.detail["tie"].sum() == 0 and r.detail["clipped"].sum() == 0, c.name
-        assert (r.refind["outcome"] != OUTCOME["window outside"]).all(), c.name
+        for k in (3, 4):                                         # the unreached stages stay unreached (stage 3: outside group e's turned targets)
+            if not (k == 3 and c.turned_kf is not None):
+                assert r.stages().get(k, 0) == 0, (c.name, r.stages())
+        assert (r.detail["tie"].sum() == 0 or c.repeat is not None) and (r.detail["clipped"].sum() == 0 or "clip_stages" in c.target), c.name
+        assert (r.refind["outcome"] != OUTCOME["window outside"]).all() and (r.refind["outcome"] != OUTCOME["invalid projection"]).all(), c.name
+        if not c.behind:
+            assert (r.refind["outcome"] != OUTCOME["behind"]).all(), c.name
     return out
 
 
@@ -96,6 +117,7 @@ def _cat(recs, key):
 
 def cross_job_hits(rf):
     """kept templates whose previous template call belonged to another run of a job"""
+    rf = template_calls(rf)
     h = np.flatnonzero(rf["hit"] == 1)
     assert (h > 0).all() and (rf["pt"][h] == rf["pt"][h - 1]).all()              # a kept template follows a call for the same point
     return int((rf["run"][h] != rf["run"][h - 1]).sum())
@@ -112,6 +134,12 @@ def test_group_b_reaches_the_refind_counts(patch):
     assert (new_kf & (span > 128)).sum() >= 1 and ((job == JOB["newly made"]) & (span > 128)).sum() >= 1     # by the row table and by the binary search
     for name in ("measured", "template bad", "not found"):                         # every early return the scene reaches ("window outside": none)
         assert (outcome == OUTCOME[name]).sum() >= 1, name
+    # the returns before the template: the radius and the image border in the new keyframe and in the map's keyframes; no point lies behind a
+    # keyframe (group e), and the radius test leaves nothing for the invalid projection (module docstring of grow_cases.py)
+    for name in ("outside radius", "outside image"):
+        assert (new_kf & (outcome == OUTCOME[name])).sum() >= 10 and ((job == JOB["newly made"]) & (outcome == OUTCOME[name])).sum() >= 1, name
+    assert (outcome == OUTCOME["behind"]).sum() == 0 and (outcome == OUTCOME["invalid projection"]).sum() == 0
+    assert ((level == -1) == (outcome >= EARLY)).all() and (hit[outcome >= EARLY] == 0).all() and (span[outcome >= EARLY] == -1).all()
     both = recs + records("a: epipolar counts", patch, verbose=False)
     job, outcome, hit = (_cat(both, k) for k in ("job", "outcome", "hit"))
     newly = job == JOB["newly made"]
@@ -155,3 +183,60 @@ def test_group_d_fills_the_map(patch):
         if c.target.get("mid_chunk"):
             assert ff[1] % gc.GROW_WAVES != 0, (c.name, ff)
         print("      the map fills during level %d; first call on a full map: level %d, candidate %d of the level (wavefront %d of its chunk); levels with stage 7: %s" % (fill, ff[0], ff[1], ff[1] % gc.GROW_WAVES, sorted(set(r.log[st == 7, 0].tolist()))))
+
+
+@pytest.mark.parametrize("patch", [8, 11])
+def test_group_e_reaches_stage_3_and_the_early_return_behind(patch):
+    recs = records("e: epipolar exits", patch)
+    steps = []
+    for c, r in recs:
+        print("      %s: stages per level %s, ties %d, clips %d" % (c.name, {l: r.stages(l) for l in range(4)}, int(r.detail["tie"].sum()), int(r.detail["clipped"].sum())))
+        outcome = r.refind["outcome"]
+        if "stage3_levels" in c.target:
+            for l in c.target["stage3_levels"]:                                    # stage 3 and an accepted call in the same level
+                st = r.stages(l)
+                assert st.get(3, 0) >= 1 and st.get(0, 0) >= 1, (c.name, l, st)
+            assert r.stages().get(3, 0) >= 10 and r.n_points > r.n0, (c.name, r.stages())
+            # the far side is one half of the image: stage 3 on one side of the candidates' mean x, accepted calls on the other
+            x = (r.log[:, 1] & 0xFFFF) * (1 << r.log[:, 0])
+            far, near = x[r.log[:, 2] == 3], x[r.log[:, 2] == 0]
+            assert (far.mean() - near.mean()) * c.turned_kf[0] > 0, (c.name, far.mean(), near.mean())
+        elif c.turned_kf is None:
+            assert r.stages().get(3, 0) == 0, (c.name, r.stages())
+        if c.repeat is not None:                                                   # an equal minimum on an accepted call, the rivals where TIES says
+            t = np.flatnonzero((r.detail["tie"] == 1) & (r.log[:, 2] == 0))
+            assert len(t) == 1 and int(r.detail["tie"].sum()) == 1, (c.name, t)
+            got = tuple(int(r.detail[k][t[0]]) for k in ("best_rank", "rival_rank", "rival_same_block"))
+            assert got == c.target["tie"][patch], (c.name, got)
+            steps.append((got[0] // gc.PATCHES_PER_STEP[patch], got[1] // gc.PATCHES_PER_STEP[patch], got[2]))
+            base = gc.record(gc.group_e()[2], patch)                                # without the block the call has no rival (the behind stream: same sub-map and parameters)
+            i = np.flatnonzero((base.log[:, :2] == r.log[t[0], :2]).all(1))
+            assert len(i) == 1 and base.log[i[0], 2] == 0 and base.detail["tie"][i[0]] == 0, c.name
+        if "clip_stages" in c.target:                                              # clipped lines, and what became of them
+            cl = r.detail["clipped"] == 1
+            for st in c.target["clip_stages"]:
+                assert (cl & (r.log[:, 2] == st)).sum() >= 1, (c.name, st, np.bincount(r.log[cl, 2]).tolist())
+            assert (~cl & (r.log[:, 2] != 1)).sum() >= 1 or c.zoom is not None, c.name
+        if c.behind:
+            m = outcome == OUTCOME["behind"]
+            assert m.sum() == c.target["behind"] and (r.refind["job"][m] == JOB["single keyframe"]).all(), (c.name, int(m.sum()))
+            assert sorted(r.refind["pt"][m].tolist()) == list(range(r.n0 - c.behind, r.n0)), c.name
+    assert sum("stage3_levels" in c.target for c, _r in recs) == 2 and sum("clip_stages" in c.target for c, _r in recs) == 2 and sum(c.behind > 0 for c, _r in recs) == 1
+    # the rivals of a tie: in two steps of one ballot, in two ballots, and (8x8) in one step
+    assert any(a != b and same for a, b, same in steps) and any(not same for _a, _b, same in steps), steps
+    assert any(a == b == 0 and same for a, b, same in steps) and (patch == 8 or any(a == b == 1 and same for a, b, same in steps)), steps   # one step: the first, and (11x11) a later one
+
+
+def test_refind_window_never_lies_outside_its_level():
+    """the argument of grow_cases' docstring, on the code that runs: once :996 has bounded the projection by the image, the oracle's
+    FindPatchCoarse (range 4, as ReFind_Common calls it) finds its window inside the level at every level -- a span, never -1 -- at
+    320x240 and at the odd size of search_trip_cases.py; one step outside the image in y the window does leave the small levels, so the
+    -1 is not out of this call's reach"""
+    rng = np.random.RandomState(3)
+    for w0, h0 in ((gc.W, gc.H), (131, 77)):
+        img = rng.randint(0, 256, (h0, w0)).astype(np.uint8)
+        for l in range(4):
+            for im_y in (0.0, 0.5, h0 / 2.0, np.nextafter(float(h0), 0.0), float(h0)):     # :996 lets 0 <= im_y <= h0 through
+                for im_x in (0.0, w0 / 2.0, float(w0)):
+                    assert orc.find_coarse_span(img, l, im_x, im_y) >= 0, (w0, h0, l, im_x, im_y)
+        assert orc.find_coarse_span(img, 3, w0 / 2.0, h0 + 16.0) == -1 and orc.find_coarse_span(img, 0, w0 / 2.0, h0 + 5.0) == -1

@@ -96,6 +96,7 @@ SYMBOLS = {
     "vslam_eval_select": (_i, [_i, _i, _vp, _i, _vp]),
     "vslam_eval_pose_tail": (_i, [_vp, _vp, _vp, _vp]),
     "vslam_eval_camera": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i]),
+    "vslam_eval_epipolar": (_i, [_sys, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "vslam_make_keyframe_lite": (_i, [_sys, _vp, _sz, _sz, _i]),
     "vslam_fast_nonmax": (_i, [_sys]),
     "vslam_read_level_image": (_i, [_sys, _i, _i, _vp, _sz]),
@@ -338,6 +339,11 @@ def eval_camera(cam5, width, height, xy, quirks=0, on_host=False):
     out, der = np.zeros((len(xy), 17)), np.zeros(5)
     _check(load_library().vslam_eval_camera(cam.ctypes.data, int(width), int(height), int(quirks), len(xy), xy.ctypes.data, out.ctypes.data, der.ctypes.data, int(on_host)))
     return out, der
+
+
+EPI_LINE_IN = {"src": slice(0, 12), "tgt": slice(12, 24), "pos": slice(24, 26), "level": 26, "depth_mean": 27, "depth_sigma": 28, "wiggle_scale": 29}
+EPI_LINE_OUT = {"root": slice(0, 2), "along": slice(2, 4), "normal": slice(4, 6), "norm_dist": 6, "min_len": 7, "max_len": 8, "start_z": 9, "end_z": 10, "along_sq": 11}
+EPI_LINE_DOUBLES = 12
 
 
 def pvs_permutation(seed, frame, lst, n, keys=None, on_host=False):
@@ -893,6 +899,17 @@ class System:
         out = PlaneProbe()
         _check(self.lib.vslam_probe_plane_aligner(self.h, stream, len(a), a.ctypes.data, seed, C.addressof(out)))
         return out
+
+    def eval_epipolar(self, lines=None, tri=None):
+        """vslam_eval_epipolar: epipolar_line over (n, 30) cases (EPI_LINE_IN) and reproject_vector / reproject_point over (m, 16) cases
+        (AfromB [12], v2A, v2B) with this handle's camera, one launch -> (flags (n, 2) int32: why, clipped; (n, 12) as EPI_LINE_OUT;
+        (m, 7): the homogeneous vector [4], the point [3])"""
+        a = _f64(np.zeros((0, 30)) if lines is None else lines).reshape(-1, 30)
+        b = _f64(np.zeros((0, 16)) if tri is None else tri).reshape(-1, 16)
+        flags, out, tout = np.zeros((len(a), 2), np.int32), np.zeros((len(a), EPI_LINE_DOUBLES)), np.zeros((len(b), 7))
+        _check(self.lib.vslam_eval_epipolar(self.h, len(a), a.ctypes.data if len(a) else None, flags.ctypes.data if len(a) else None,
+                                            out.ctypes.data if len(a) else None, len(b), b.ctypes.data if len(b) else None, tout.ctypes.data if len(b) else None))
+        return flags, out, tout
 
     def idle_stats(self, stream):
         o = np.zeros(6, np.int32)

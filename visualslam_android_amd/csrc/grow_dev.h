@@ -114,14 +114,18 @@ DEVFN void svd4_smallest_right_vector(const double Ain[16], double out[4]) {
   }
 }
 
-// MapMaker::ReprojectPoint, jni/MapMaker.cc:174-200
-DEVFN void reproject_point(const Pose& AfromB, const double v2A[2], const double v2B[2], double out[3]) {
+// MapMaker::ReprojectPoint, jni/MapMaker.cc:174-200: the homogeneous vector as the SVD hands it over (:176-192) ...
+DEVFN void reproject_vector(const Pose& AfromB, const double v2A[2], const double v2B[2], double v[4]) {
   double PD[12];
   for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) PD[r * 4 + c] = AfromB.R[r * 3 + c]; PD[r * 4 + 3] = AfromB.t[r]; }
   double A[16] = {-1.0, 0.0, v2B[0], 0.0, 0.0, -1.0, v2B[1], 0.0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int c = 0; c < 4; c++) { A[8 + c] = v2A[0] * PD[8 + c] - PD[0 + c]; A[12 + c] = v2A[1] * PD[8 + c] - PD[4 + c]; }
-  double v[4];
   svd4_smallest_right_vector(A, v);
+}
+// ... and the point (:194-199)
+DEVFN void reproject_point(const Pose& AfromB, const double v2A[2], const double v2B[2], double out[3]) {
+  double v[4];
+  reproject_vector(AfromB, v2A, v2B, v);
   if (v[3] == 0.0) v[3] = 0.00001;
   out[0] = v[0] / v[3]; out[1] = v[1] / v[3]; out[2] = v[2] / v[3];
 }
@@ -136,5 +140,54 @@ DEVFN void rot_inv(const Pose& T, const double p[3], double o[3]) {             
   o[0] = T.R[0] * p[0] + T.R[3] * p[1] + T.R[6] * p[2];
   o[1] = T.R[1] * p[0] + T.R[4] * p[1] + T.R[7] * p[2];
   o[2] = T.R[2] * p[0] + T.R[5] * p[1] + T.R[8] * p[2];
+}
+
+// The geometry of AddPointEpipolar's search line, jni/MapMaker.cc:544-591: the candidate at level position (irx, iry) of level
+// nLevel in the source keyframe, its ray between the depths the scene allows, seen in the target keyframe's z = 1 plane.
+// why: 0 the line stands, 1 the ray ends before it starts or behind the target (:559-563), 2 a segment shorter than 1e-4
+// (:575-576), 3 the line passes outside largest_radius (:582-583).  clipped: the start of the ray lay behind the target's image
+// plane and was moved to 0.001 in front of it (:565-568).  startZ, endZ, alongSq: what the first three tests look at
+// (v3RayStart_TC[2] before the clip, v3RayEnd_TC[2], the squared length), for the probe; k_epipolar reads none of
+// them.  A field an exit does not reach stays 0 (along holds the
+// un-normalised difference at exit 2).  k_epipolar and vslam_eval_epipolar run this; oracle/mapgrow.cpp epipolar_line states
+// it for the host, statement for statement.
+struct EpiLine { int why, clipped; double root[2], along[2], normal[2], dNormDist, dMinLen, dMaxLen, startZ, endZ, alongSq; };
+
+DEVFN EpiLine epipolar_line(const Pose& Tsrc, const Pose& Ttgt, const CamModel& cam, double irx, double iry, int nLevel, double dMean, double dSigma,
+                            double wiggle_scale) {
+  EpiLine e;
+  e.why = 0; e.clipped = 0; e.along[0] = 0; e.along[1] = 0; e.normal[0] = 0; e.normal[1] = 0; e.dNormDist = 0; e.dMinLen = 0; e.dMaxLen = 0; e.alongSq = 0;
+  e.root[0] = level_zero_pos(irx, nLevel); e.root[1] = level_zero_pos(iry, nLevel);
+  double ray[3], tmp[3], dirn[3];
+  unit_ray(cam, e.root[0], e.root[1], ray);
+  rot_inv(Tsrc, ray, tmp);
+  pose_rot(Ttgt, tmp, dirn);
+  const double dStartDepth = wiggle_scale > dMean - dSigma ? wiggle_scale : dMean - dSigma;
+  const double dEndDepth = 40 * wiggle_scale < dMean + dSigma ? 40 * wiggle_scale : dMean + dSigma;
+  const Pose srcInv = pose_inverse(Tsrc);
+  double centre[3];
+  pose_xform(Ttgt, srcInv.t, centre);
+  double rs[3], re[3];
+  for (int i = 0; i < 3; i++) { rs[i] = centre[i] + dStartDepth * dirn[i]; re[i] = centre[i] + dEndDepth * dirn[i]; }
+  e.startZ = rs[2]; e.endZ = re[2];
+  if (re[2] <= rs[2]) { e.why = 1; return e; }
+  if (re[2] <= 0.0) { e.why = 1; return e; }
+  if (rs[2] <= 0.0) { e.clipped = 1; const double f = 0.001 - rs[2] / dirn[2]; for (int i = 0; i < 3; i++) rs[i] += dirn[i] * f; }
+  const double v2A[2] = {rs[0] / rs[2], rs[1] / rs[2]}, v2B[2] = {re[0] / re[2], re[1] / re[2]};
+  e.along[0] = v2A[0] - v2B[0]; e.along[1] = v2A[1] - v2B[1];
+  e.alongSq = e.along[0] * e.along[0] + e.along[1] * e.along[1];
+  if (e.along[0] * e.along[0] + e.along[1] * e.along[1] < 0.00000001) { e.why = 2; return e; }
+  const double n = sqrt(e.along[0] * e.along[0] + e.along[1] * e.along[1]);
+  e.along[0] /= n; e.along[1] /= n;
+  e.normal[0] = e.along[1]; e.normal[1] = -e.along[0];
+  e.dNormDist = v2A[0] * e.normal[0] + v2A[1] * e.normal[1];
+  if (fabs(e.dNormDist) > cam.largest_radius) { e.why = 3; return e; }
+  const double la = e.along[0] * v2A[0] + e.along[1] * v2A[1], lb = e.along[0] * v2B[0] + e.along[1] * v2B[1];
+  e.dMinLen = (la < lb ? la : lb) - 0.05; e.dMaxLen = (la > lb ? la : lb) + 0.05;
+  if (e.dMinLen < -2.0) e.dMinLen = -2.0;
+  if (e.dMaxLen < -2.0) e.dMaxLen = -2.0;
+  if (e.dMinLen > 2.0) e.dMinLen = 2.0;
+  if (e.dMaxLen > 2.0) e.dMaxLen = 2.0;
+  return e;
 }
 

@@ -136,39 +136,10 @@ __global__ __launch_bounds__(GROW_THREADS) __attribute__((amdgpu_waves_per_eu(2,
     if (alive) {                                                   // ---- geometry of the epipolar line, :544-591 (every lane alike)
       const uint32_t cpos = cand[ci];
       irx = (double)(cpos & 0xFFFF); iry = (double)(cpos >> 16);
-      root0 = level_zero_pos(irx, nLevel); root1 = level_zero_pos(iry, nLevel);
-      double ray[3], tmp[3], dirn[3];
-      unit_ray(tp.cam, root0, root1, ray);
-      rot_inv(Tsrc, ray, tmp);
-      pose_rot(Ttgt, tmp, dirn);
-      const double dStartDepth = tp.wiggle_scale > dMean - dSigma ? tp.wiggle_scale : dMean - dSigma;
-      const double dEndDepth = 40 * tp.wiggle_scale < dMean + dSigma ? 40 * tp.wiggle_scale : dMean + dSigma;
-      const Pose srcInv = pose_inverse(Tsrc);
-      double centre[3];
-      pose_xform(Ttgt, srcInv.t, centre);
-      double rs[3], re[3];
-      for (int i = 0; i < 3; i++) { rs[i] = centre[i] + dStartDepth * dirn[i]; re[i] = centre[i] + dEndDepth * dirn[i]; }
-      if (re[2] <= rs[2]) { alive = false; why = 1; }
-      if (re[2] <= 0.0) { alive = false; why = 1; }
-      if (alive) {
-        if (rs[2] <= 0.0) { const double f = 0.001 - rs[2] / dirn[2]; for (int i = 0; i < 3; i++) rs[i] += dirn[i] * f; }
-        const double v2A[2] = {rs[0] / rs[2], rs[1] / rs[2]}, v2B[2] = {re[0] / re[2], re[1] / re[2]};
-        along0 = v2A[0] - v2B[0]; along1 = v2A[1] - v2B[1];
-        if (along0 * along0 + along1 * along1 < 0.00000001) { alive = false; why = 2; }
-        else {
-          const double n = sqrt(along0 * along0 + along1 * along1);
-          along0 /= n; along1 /= n;
-          normal0 = along1; normal1 = -along0;
-          dNormDist = v2A[0] * normal0 + v2A[1] * normal1;
-          if (fabs(dNormDist) > tp.cam.largest_radius) { alive = false; why = 3; }
-          const double la = along0 * v2A[0] + along1 * v2A[1], lb = along0 * v2B[0] + along1 * v2B[1];
-          dMinLen = (la < lb ? la : lb) - 0.05; dMaxLen = (la > lb ? la : lb) + 0.05;
-          if (dMinLen < -2.0) dMinLen = -2.0;
-          if (dMaxLen < -2.0) dMaxLen = -2.0;
-          if (dMinLen > 2.0) dMinLen = 2.0;
-          if (dMaxLen > 2.0) dMaxLen = 2.0;
-        }
-      }
+      const EpiLine el = epipolar_line(Tsrc, Ttgt, tp.cam, irx, iry, nLevel, dMean, dSigma, tp.wiggle_scale);
+      root0 = el.root[0]; root1 = el.root[1]; along0 = el.along[0]; along1 = el.along[1]; normal0 = el.normal[0]; normal1 = el.normal[1];
+      dNormDist = el.dNormDist; dMinLen = el.dMinLen; dMaxLen = el.dMaxLen;
+      why = el.why; alive = why == 0;
       ca = (int)irx; cb = (int)iry;
     }
     GROW_STAMP(0);   // geometry

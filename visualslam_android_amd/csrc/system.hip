@@ -1,5 +1,6 @@
 // vslam_system lifetime, parameters and read-back entry points of the C ABI (include/vslam_c.h).
 #include "vslam_internal.h"
+#include "grow_dev.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -396,6 +397,70 @@ extern "C" int vslam_eval_camera(const double* cam5, int width, int height, int 
   hipLaunchKernelGGL(k_eval_camera, dim3(1), dim3(64), 0, 0, tp.cam, n, (const double*)d_xy.p, d_out.p);
   HIPCHK(hipGetLastError());
   VCHK(c.get(out17, (const double*)d_out.p, (size_t)CAM_EVAL_DOUBLES * n));
+  return c.wait();
+}
+
+// ---- self-test hook: the line geometry of AddPointEpipolar and the triangulation, as k_epipolar runs them (grow_dev.h) ------
+// One launch, one lane per case: first the n_lines epipolar_line cases, then the n_tri reproject_vector / reproject_point cases.
+#define EPI_IN_DOUBLES 30
+#define EPI_OUT_DOUBLES 12
+#define TRI_IN_DOUBLES 16
+#define TRI_OUT_DOUBLES 7
+static DEVFN Pose pose_from12(const double* a) {
+  Pose T;
+  for (int i = 0; i < 9; i++) T.R[i] = a[i];
+  for (int i = 0; i < 3; i++) T.t[i] = a[9 + i];
+  return T;
+}
+
+__global__ __launch_bounds__(64) void k_eval_epipolar(CamModel cam, int n_lines, const double* lines, int* line_flags, double* line_out, int n_tri,
+                                                       const double* tri, double* tri_out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i < n_lines) {
+    const double* in = lines + (size_t)EPI_IN_DOUBLES * i;
+    const EpiLine e = epipolar_line(pose_from12(in), pose_from12(in + 12), cam, in[24], in[25], (int)in[26], in[27], in[28], in[29]);
+    line_flags[2 * i] = e.why; line_flags[2 * i + 1] = e.clipped;
+    double* o = line_out + (size_t)EPI_OUT_DOUBLES * i;
+    o[0] = e.root[0]; o[1] = e.root[1]; o[2] = e.along[0]; o[3] = e.along[1]; o[4] = e.normal[0]; o[5] = e.normal[1];
+    o[6] = e.dNormDist; o[7] = e.dMinLen; o[8] = e.dMaxLen; o[9] = e.startZ; o[10] = e.endZ; o[11] = e.alongSq;
+  } else if (i - n_lines < n_tri) {
+    const int j = i - n_lines;
+    const double* in = tri + (size_t)TRI_IN_DOUBLES * j;
+    const Pose T = pose_from12(in);
+    double* o = tri_out + (size_t)TRI_OUT_DOUBLES * j;
+    double v[4], p[3];
+    reproject_vector(T, in + 12, in + 14, v);
+    reproject_point(T, in + 12, in + 14, p);
+    for (int k = 0; k < 4; k++) o[k] = v[k];
+    for (int k = 0; k < 3; k++) o[4 + k] = p[k];
+  }
+}
+
+extern "C" int vslam_eval_epipolar(vslam_system* sys, int n_lines, const double* lines30, int* line_flags2, double* line_out12, int n_tri,
+                                   const double* tri16, double* tri_out7) {
+  if (!sys || n_lines < 0 || n_tri < 0 || (n_lines > 0 && (!lines30 || !line_flags2 || !line_out12)) || (n_tri > 0 && (!tri16 || !tri_out7))) { vslam_set_error("eval_epipolar: bad argument"); return VSLAM_E_INVALID; }
+  if (n_lines > 65536 || n_tri > 65536) { vslam_set_error("eval_epipolar: at most 65536 cases of a kind"); return VSLAM_E_CAPACITY; }
+  for (int i = 0; i < n_lines; i++) {
+    const double l = lines30[(size_t)EPI_IN_DOUBLES * i + 26];
+    if (!(l == 0.0 || l == 1.0 || l == 2.0 || l == 3.0)) { vslam_set_error("eval_epipolar: case %d: level outside 0..%d", i, NLEV - 1); return VSLAM_E_INVALID; }
+  }
+  if (n_lines + n_tri == 0) return VSLAM_OK;
+  DevTemp<double> d_in, d_out;
+  DevTemp<int> d_flags;
+  const size_t nin = (size_t)EPI_IN_DOUBLES * n_lines + (size_t)TRI_IN_DOUBLES * n_tri, nout = (size_t)EPI_OUT_DOUBLES * n_lines + (size_t)TRI_OUT_DOUBLES * n_tri;
+  HIPCHK(d_in.get(nin));
+  HIPCHK(d_out.get(nout));
+  HIPCHK(d_flags.get((size_t)2 * (n_lines > 0 ? n_lines : 1)));
+  hipStream_t q = sys->stream;
+  HostCopy c(q);                                        // (behind the buffers: it waits before they are freed)
+  VCHK(c.put(d_in.p, lines30, (size_t)EPI_IN_DOUBLES * n_lines));
+  VCHK(c.put(d_in.p + (size_t)EPI_IN_DOUBLES * n_lines, tri16, (size_t)TRI_IN_DOUBLES * n_tri));
+  hipLaunchKernelGGL(k_eval_epipolar, dim3((n_lines + n_tri + 63) / 64), dim3(64), 0, q, sys->tp.cam, n_lines, (const double*)d_in.p, d_flags.p, d_out.p, n_tri,
+                     (const double*)(d_in.p + (size_t)EPI_IN_DOUBLES * n_lines), d_out.p + (size_t)EPI_OUT_DOUBLES * n_lines);
+  HIPCHK(hipGetLastError());
+  VCHK(c.get(line_flags2, (const int*)d_flags.p, (size_t)2 * n_lines));
+  VCHK(c.get(line_out12, (const double*)d_out.p, (size_t)EPI_OUT_DOUBLES * n_lines));
+  VCHK(c.get(tri_out7, (const double*)(d_out.p + (size_t)EPI_OUT_DOUBLES * n_lines), (size_t)TRI_OUT_DOUBLES * n_tri));
   return c.wait();
 }
 
