@@ -3,13 +3,13 @@
 window, a survivor that fails the border test in the middle of a trip, two candidates of equal best ZMSSD in one trip and in two (the
 earlier in raster order wins), and one wavefront whose patches mix the extremes.  The cases come from tests/search_trip_cases.py;
 tests/test_search_trip_cases.py asserts on the CPU that the oracle reaches every count.  Here every case is a stream of one System
-beside its own oracle (test_gpu_tracker_counts.run_group): searched and found sets, vfound, image, attempted, found and n_zmssd are
+beside its own oracle (stagewise.run_group): searched and found sets, vfound, image, attempted, found and n_zmssd are
 compared with == after each search and pose stage, then the frame through helpers.assert_tracker_exact; two frames per case, the second
 on the cached templates."""
 import pytest
 
 import search_trip_cases as sc
-from test_gpu_tracker_counts import run_group
+from stagewise import run_group
 
 pytestmark = pytest.mark.gpu
 

@@ -2,7 +2,7 @@
 edges, k_searchN's patches per wavefront, xcd_stream_block's groups of eight streams, k_subpixN's strided grid, and k_pose's batches,
 chunks and read-ahead.  The cases come from tests/tracker_cases.py -- sub-maps chosen from the oracle so that each reaches a wanted
 n_points, number of searched patches, per-level count or number of found patches; tests/test_tracker_cases.py asserts on the CPU that
-they do.  Here every case is a stream of one System beside its own oracle, both started from the same bits, and everything is compared
+they do.  Here every case is a stream of one System beside its own oracle (stagewise.run_group), both started from the same bits, and everything is compared
 with ==: after each search and pose stage (so a difference is attributed to one of them), and after the frame through
 helpers.assert_tracker_exact, templates included.  Two frames per case, re-synchronised in between; the second takes the
 cached-template path."""
@@ -10,63 +10,11 @@ import numpy as np
 import pytest
 
 import tracker_cases as tc
-from helpers import assert_tracker_exact, check_and_resync, pose_err, resync
+from helpers import check_and_resync, pose_err
+from stagewise import run_group
 from visualslam_android_amd import capi
 
 pytestmark = pytest.mark.gpu
-
-
-def assert_stage_exact(o, g, s, tag):
-    """after a search or pose stage: counters, searched and found sets, positions and the pose estimate == the oracle's"""
-    so, sg = o.state(), g.state(s)
-    to, tg = o.point_tracks(), g.point_tracks(s)
-    pv = tg["level"] >= 0
-    assert np.array_equal(to["level"] >= 0, pv) and np.array_equal(to["level"][pv], tg["level"][pv]), tag
-    assert np.array_equal(to["searched"], tg["searched"]) and np.array_equal(to["found"][pv], tg["found"][pv]), tag
-    fnd = pv & (tg["found"] == 1)
-    assert np.array_equal(to["vfound"][fnd], tg["vfound"][fnd]) and np.array_equal(to["image"][fnd], tg["image"][fnd]), tag
-    assert list(so.attempted) == list(sg.attempted) and list(so.found) == list(sg.found), (tag, list(so.attempted), list(sg.attempted), list(so.found), list(sg.found))
-    assert so.n_zmssd == sg.n_zmssd and so.did_coarse == sg.did_coarse, (tag, so.n_zmssd, sg.n_zmssd, so.did_coarse, sg.did_coarse)
-    assert np.array_equal(np.array(so.pose[:]), np.array(sg.pose[:])), (tag, pose_err(so.pose, sg.pose))
-
-
-def run_group(cases, patch, after_fine_pose=None):
-    """the cases as the streams of one System, stage by stage against one oracle each"""
-    S = len(cases)
-    g = capi.System(cases[0].params(S, patch))
-    assert all(c.pkw == cases[0].pkw and c.size == cases[0].size for c in cases)          # the parameters are system-wide
-    oracles = []
-    for s, c in enumerate(cases):
-        c.load(g, s)
-        oracles.append(c.oracle(patch))
-    for t in range(tc.N_FRAMES):
-        g.make_keyframe_lite(np.stack([c.frame(t) for c in cases]))
-        for o, c in zip(oracles, cases):
-            o.frame_begin(c.frame(t))
-        for stage in (0, 1):
-            g.patch_search(stage)
-            for s, (o, c) in enumerate(zip(oracles, cases)):
-                o.search_stage(stage)
-                assert_stage_exact(o, g, s, "%s, %dx%d patches, frame %d, search %d" % (c.name, patch, patch, t, stage))
-            g.pose_update(stage)
-            for s, (o, c) in enumerate(zip(oracles, cases)):
-                o.pose_stage(stage)
-                assert_stage_exact(o, g, s, "%s, %dx%d patches, frame %d, pose %d" % (c.name, patch, patch, t, stage))
-        g.finish_frame()
-        for s, (o, c) in enumerate(zip(oracles, cases)):
-            o.frame_end()
-            tag = "%s, %dx%d patches, frame %d" % (c.name, patch, patch, t)
-            assert_tracker_exact(o, g, s, tag)
-            if t == 0:
-                for key in ("n_points", "did_coarse"):                                    # the case is the one the CPU test vouched for
-                    if key in c.target:
-                        assert getattr(g.state(s), key) == c.target[key], (tag, key)
-            if after_fine_pose:
-                after_fine_pose(o, g, s, tag)
-            resync(o, g, s)
-    for o in oracles:
-        o.close()
-    g.close()
 
 
 def outlier_marks_equal(o, g, s, tag):
