@@ -67,8 +67,11 @@ int orc_sys_init_from_stereo(void* sv, const uint8_t* first, const uint8_t* seco
   make_keyframe_lite(kS, second, s->p.width, s->p.height, stride, s->p.thr);
   std::vector<std::array<int, 4>> m((size_t)n);
   for (int i = 0; i < n; i++) m[(size_t)i] = {matches4[4 * i], matches4[4 * i + 1], matches4[4 * i + 2], matches4[4 * i + 3]};
+  s->trails.clear();                                                 // the matches stand where the trails would (init_info's count, as after a second press)
+  for (int i = 0; i < n; i++) { System::Trail t{}; t.init[0] = matches4[4 * i]; t.init[1] = matches4[4 * i + 1]; t.cur[0] = matches4[4 * i + 2]; t.cur[1] = matches4[4 * i + 3]; s->trails.push_back(t); }
+  kS.depth_mean = s->cur.depth_mean; kS.depth_sigma = s->cur.depth_sigma;   // mCurrentKF's scene depth (1.0 since jni/Tracker.cc:52-53) is not the image's
   s->cur = kS;
-  s->frame += 2;                                                     // the two frames the device path spends on it
+  s->frame += 2;                                                    // the two frames the device path spends on it
   s->n_hom_inliers = 0; s->n_init_points = 0;
   s->init_ok = s->InitFromStereo(kF, kS, m);
   s->init_stage = 2;
@@ -78,6 +81,39 @@ int orc_sys_init_from_stereo(void* sv, const uint8_t* first, const uint8_t* seco
 void orc_sys_get_init_info(void* sv, int out[6]) {
   System* s = (System*)sv;
   out[0] = s->init_stage; out[1] = (int)s->trails.size(); out[2] = s->init_ok ? 1 : 0; out[3] = s->n_hom_inliers; out[4] = s->n_init_points; out[5] = s->map_good ? 1 : 0;
+}
+// shared-stage mode (ptam_system.hpp): both functions, or both null for the oracle's own mathematics (the default)
+void orc_sys_set_shared_stages(void* sv, void* homography_pipeline, void* plane_pipeline) {
+  System* s = (System*)sv;
+  s->shared_hom = (System::HomStageFn)homography_pipeline; s->shared_plane = (System::PlaneStageFn)plane_pipeline;
+}
+int orc_sys_get_boot_log(void* sv, int* code_its2, double* sub2, int cap) {
+  System* s = (System*)sv;
+  const int n = (int)s->boot_log.size();
+  for (int i = 0; i < n && i < cap; i++) { code_its2[2 * i] = s->boot_log[i].code; code_its2[2 * i + 1] = s->boot_log[i].its; sub2[2 * i] = s->boot_log[i].sub[0]; sub2[2 * i + 1] = s->boot_log[i].sub[1]; }
+  return n;
+}
+void orc_sys_get_boot_diag(void* sv, int out[4], double* wiggle_depth_norm) {
+  System* s = (System*)sv;
+  out[0] = s->boot_exit; out[1] = s->boot_plane_points; out[2] = s->boot_plane_have; out[3] = s->boot_pixvec_changed;
+  *wiggle_depth_norm = s->wiggle_depth_norm;
+}
+int orc_sys_get_point_sources(void* sv, double* right3, double* down3, int* src4, int cap) {
+  System* s = (System*)sv;
+  const int n = (int)s->pts.size();
+  for (int i = 0; i < n && i < cap; i++) {
+    const MapPoint& p = *s->pts[i];
+    for (int k = 0; k < 3; k++) { right3[3 * i + k] = p.pix_right[k]; down3[3 * i + k] = p.pix_down[k]; }
+    src4[4 * i] = p.src_kf; src4[4 * i + 1] = p.src_level; src4[4 * i + 2] = p.irx; src4[4 * i + 3] = p.iry;
+  }
+  return n;
+}
+void orc_sys_get_keyframe_depth(void* sv, int kf, double out[2]) { const KeyFrame& k = *((System*)sv)->kfs[kf]; out[0] = k.depth_mean; out[1] = k.depth_sigma; }
+int orc_sys_get_keyframe_meas_subpix(void* sv, int kf, int* subpix, int cap) {
+  System* s = (System*)sv;
+  int n = 0;
+  for (auto& it : s->kfs[kf]->meas) { if (n < cap) subpix[n] = it.second.subpix ? 1 : 0; n++; }
+  return n;
 }
 int orc_sys_get_trails(void* sv, int* out4, int cap) {
   System* s = (System*)sv;

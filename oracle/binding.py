@@ -287,6 +287,57 @@ class OracleSystem:
     def set_boot_seed(self, seed):
         self.L.orc_sys_set_boot_seed(self.h, C.c_uint(seed))
 
+    def set_shared_stages(self, on=True):
+        """Shared-stage mode: InitFromStereo and CalcPlaneAligner take the results of their two mathematical stages from the host build of
+        the product's csrc/bootstrap_math.h (bootmath(): bmh_homography_pipeline, bmh_plane_pipeline), handed to the oracle as two function
+        pointers -- the oracle library itself does not link that build.  Off (the default): the oracle's own mathematics."""
+        self.L.orc_sys_set_shared_stages.restype = None
+        self.L.orc_sys_set_shared_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        if on:
+            B = bootmath()
+            self.L.orc_sys_set_shared_stages(self.h, C.cast(B.bmh_homography_pipeline, C.c_void_p), C.cast(B.bmh_plane_pipeline, C.c_void_p))
+        else:
+            self.L.orc_sys_set_shared_stages(self.h, None, None)
+
+    BOOT_CODES = ("point", "template border", "subpix failed", "behind")
+
+    def boot_log(self, cap=1000):
+        """the point loop of the last InitFromStereo, one row per match: code (index of BOOT_CODES), sub-pixel iterations started, the
+        sub-pixel position reached (the match's second position where none ran)"""
+        ci, sub = np.zeros((cap, 2), np.int32), np.zeros((cap, 2))
+        n = self.L.orc_sys_get_boot_log(self.h, _p(ci), _p(sub), cap)
+        assert n <= cap
+        return {"code": ci[:n, 0].copy(), "its": ci[:n, 1].copy(), "sub": sub[:n].copy()}
+
+    BOOT_EXITS = ("went through", "HomographyInit failed", "zero translation", "host pipeline not ok")
+
+    def boot_diag(self):
+        """of the last InitFromStereo: exit (index of BOOT_EXITS), points when CalcPlaneAligner ran (-1: not reached), an aligner was made,
+        points whose pixel vectors ApplyGlobalTransformationToMap changed in some bit, mdWiggleScaleDepthNormalized"""
+        o = np.zeros(4, np.int32); wd = C.c_double(0)
+        self.L.orc_sys_get_boot_diag.restype = None
+        self.L.orc_sys_get_boot_diag(self.h, _p(o), C.byref(wd))
+        return {"exit": int(o[0]), "plane_points": int(o[1]), "plane_have": int(o[2]), "pixvec_changed": int(o[3]), "wiggle_depth_norm": wd.value}
+
+    def point_sources(self):
+        """per map point: v3PixelRight_W, v3PixelDown_W, source keyframe, source level, irLevelPos"""
+        n = self.state().n_points
+        right, down, src = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, 4), np.int32)
+        self.L.orc_sys_get_point_sources(self.h, _p(right), _p(down), _p(src), n)
+        return {"right": right, "down": down, "src_kf": src[:, 0].copy(), "src_level": src[:, 1].copy(), "irx": src[:, 2].copy(), "iry": src[:, 3].copy()}
+
+    def keyframe_depth(self, kf):
+        o = np.zeros(2)
+        self.L.orc_sys_get_keyframe_depth.restype = None
+        self.L.orc_sys_get_keyframe_depth(self.h, int(kf), _p(o))
+        return o
+
+    def keyframe_meas_subpix(self, kf, cap=8192):
+        """bSubPix of the keyframe's measurements, in keyframe_meas's order"""
+        o = np.zeros(cap, np.int32)
+        n = self.L.orc_sys_get_keyframe_meas_subpix(self.h, int(kf), _p(o), cap)
+        return o[:n]
+
     def init_info(self):
         o = np.zeros(6, np.int32)
         self.L.orc_sys_get_init_info(self.h, _p(o))

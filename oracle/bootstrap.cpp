@@ -6,7 +6,9 @@
 // that file's header): PARITY UNPINNED (no fixture of the reference covers it).
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include "ptam_system.hpp"
+#include "../include/vslam_c.h"   // the records the shared-stage functions fill (vslam_homography_probe, vslam_plane_probe): layouts only
 
 namespace orc {
 
@@ -125,10 +127,22 @@ bool System::InitFromStereo(const KeyFrame& kF, const KeyFrame& kS, const std::v
     vm.push_back(m);
   }
   SE3 se3;
-  if (!homography_init_compute(vm, 5.0, boot_seed, se3, &n_hom_inliers)) return false;   // :233-240
-  const double mag = sqrt(se3.t[0] * se3.t[0] + se3.t[1] * se3.t[1] + se3.t[2] * se3.t[2]);
-  if (mag == 0) return false;                                                    // :243-248
-  for (int i = 0; i < 3; i++) se3.t[i] *= p.wiggle_scale / mag;                  // :250
+  boot_log.clear(); boot_exit = 0; boot_plane_points = -1; boot_plane_have = 0; boot_pixvec_changed = 0;
+  if (shared_hom) {                                                              // shared-stage mode: ok, the inlier count, R and the SCALED translation
+    std::vector<double> m8(8 * vm.size() + 8);
+    for (size_t i = 0; i < vm.size(); i++) { for (int k = 0; k < 2; k++) { m8[8 * i + k] = vm[i].first[k]; m8[8 * i + 2 + k] = vm[i].second[k]; } for (int k = 0; k < 4; k++) m8[8 * i + 4 + k] = vm[i].jac[k]; }
+    std::unique_ptr<vslam_homography_probe> rec(new vslam_homography_probe);
+    shared_hom((int)vm.size(), m8.data(), boot_seed, 5.0, p.wiggle_scale, rec.get());
+    if (vm.size() >= 4) n_hom_inliers = rec->n_inliers;
+    if (!rec->ok) { boot_exit = 3; return false; }
+    for (int i = 0; i < 9; i++) se3.R[i] = rec->R[i];
+    for (int i = 0; i < 3; i++) se3.t[i] = rec->t_scaled[i];
+  } else {
+    if (!homography_init_compute(vm, 5.0, boot_seed, se3, &n_hom_inliers)) { boot_exit = 1; return false; }   // :233-240
+    const double mag = sqrt(se3.t[0] * se3.t[0] + se3.t[1] * se3.t[1] + se3.t[2] * se3.t[2]);
+    if (mag == 0) { boot_exit = 2; return false; }                               // :243-248
+    for (int i = 0; i < 3; i++) se3.t[i] *= p.wiggle_scale / mag;                // :250
+  }
   KeyFrame* pkFirst = new KeyFrame(kF); KeyFrame* pkSecond = new KeyFrame(kS);
   pkFirst->fixed = true; pkFirst->pose = SE3(); pkFirst->meas.clear();
   pkSecond->fixed = false; pkSecond->pose = se3; pkSecond->meas.clear();
@@ -139,6 +153,8 @@ bool System::InitFromStereo(const KeyFrame& kF, const KeyFrame& kS, const std::v
     const int cx = trail[i][0], cy = trail[i][1];
     // MakeTemplateCoarseNoWarp (jni/PatchFinder.cc:130-142) at level 0 of the first keyframe
     const int P = f.P, half = P / 2;
+    boot_log.push_back({1, 0, {(double)trail[i][2], (double)trail[i][3]}});
+    BootLogEntry& lg = boot_log.back();
     if (!(cx >= half + 1 && cy >= half + 1 && cx < pkFirst->w[0] - (half + 1) && cy < pkFirst->h[0] - (half + 1))) continue;   // mbTemplateBad -> the sub-pixel steps fail
     f.level = 0; f.bad = false;
     f.tmpl.resize(P * P);
@@ -148,11 +164,15 @@ bool System::InitFromStereo(const KeyFrame& kF, const KeyFrame& kS, const std::v
     f.coarse[0] = 0; f.coarse[1] = 0;
     finder_make_subpix(f);
     f.subpix[0] = trail[i][2]; f.subpix[1] = trail[i][3];                        // SetSubPixPos, :300
-    if (!finder_iterate_subpix_to_convergence(f, *pkSecond, 10)) continue;       // :301-304
+    const bool converged = finder_iterate_subpix_to_convergence(f, *pkSecond, 10);
+    lg.code = 2; lg.its = f.sp_its; lg.sub[0] = f.subpix[0]; lg.sub[1] = f.subpix[1];
+    if (!converged) continue;                                                    // :301-304
     double uB[2];
     camera.unproject(f.subpix[0], f.subpix[1], uB);
     const V3 wp = reproject_point(se3, uB, vm[i].first);                         // :309-311
+    lg.code = 3;
     if (wp[2] < 0.0) continue;
+    lg.code = 0;
     MapPoint* mp = new MapPoint();
     mp->pos = wp; mp->boot = true; mp->src_kf = 0; mp->src_level = 0; mp->irx = cx; mp->iry = cy;
     mp->finder.P = p.patch_size; mp->finder.max_ssd = f.max_ssd;
@@ -189,7 +209,17 @@ SE3 System::CalcPlaneAligner() {
   std::vector<V3> pos;                                                           // every point of the map (bad ones live in the trash there)
   for (auto q : pts) pos.push_back(q->pos);
   SE3 T;
-  calc_plane_aligner(pos, boot_seed + 1u, T);                                    // identity with fewer than ten points (:1107-1110)
+  boot_plane_points = (int)pos.size();
+  if (shared_plane) {                                                            // shared-stage mode: the aligner, or identity where none was made
+    std::vector<double> p3(3 * pos.size() + 3);
+    for (size_t i = 0; i < pos.size(); i++) for (int k = 0; k < 3; k++) p3[3 * i + k] = pos[i][k];
+    vslam_plane_probe rec;
+    shared_plane((int)pos.size(), p3.data(), boot_seed + 1u, &rec);
+    boot_plane_have = rec.have;
+    if (rec.have) { for (int i = 0; i < 9; i++) T.R[i] = rec.R[i]; for (int i = 0; i < 3; i++) T.t[i] = rec.t[i]; }
+    return T;
+  }
+  boot_plane_have = calc_plane_aligner(pos, boot_seed + 1u, T) ? 1 : 0;          // identity with fewer than ten points (:1107-1110)
   return T;
 }
 
@@ -199,11 +229,13 @@ void System::ApplyGlobalTransformationToMap(const SE3& new_from_old) {
   for (auto k : kfs) k->pose = mul(k->pose, inv);
   for (auto q : pts) {
     q->pos = xform(new_from_old, q->pos);
+    const V3 right_before = q->pix_right, down_before = q->pix_down;
     const KeyFrame& k = *kfs[q->src_kf];
     const int s = 1 << q->src_level;
     const double cx = level_zero_pos((double)q->irx, q->src_level), cy = level_zero_pos((double)q->iry, q->src_level);
     if (q->src_kf == 0 && q->boot) refresh_pixel_vectors(*q, k, unit_ray(camera, cx, cy), unit_ray(camera, cx, cy + 1), unit_ray(camera, cx + 1, cy));
     else refresh_pixel_vectors(*q, k, unit_ray(camera, cx, cy), unit_ray(camera, cx + s, cy), unit_ray(camera, cx, cy + s));
+    if (memcmp(&right_before, &q->pix_right, sizeof(V3)) != 0 || memcmp(&down_before, &q->pix_down, sizeof(V3)) != 0) boot_pixvec_changed++;
   }
 }
 

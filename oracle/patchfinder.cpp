@@ -200,8 +200,10 @@ static double finder_iterate_subpix(Finder& f, const KeyFrame& kf) {
 // PatchFinder::IterateSubPixToConvergence, jni/PatchFinder.cc:273-289
 bool finder_iterate_subpix_to_convergence(Finder& f, const KeyFrame& kf, int nMaxIts) {
   const double dConvLimit = 0.03;
+  f.sp_its = 0;
   for (int nIts = 0; nIts < nMaxIts; nIts++) {
     const double d = finder_iterate_subpix(f, kf);
+    f.sp_its = nIts + 1;
     if (d < 0) return false;
     if (d < dConvLimit * dConvLimit) return true;
   }

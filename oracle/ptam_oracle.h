@@ -133,6 +133,21 @@ void orc_sys_set_boot_seed(void* sys, unsigned seed);
 int orc_sys_init_from_stereo(void* sys, const uint8_t* first, const uint8_t* second, int stride, const int* matches4, int n, double pose12[12]);   /* MapMaker::InitFromStereo with the caller's frames and matches */
 void orc_sys_get_init_info(void* sys, int out[6]);   /* stage, trails, InitFromStereo succeeded, homography inliers, points after the stereo pass, map good */
 int orc_sys_get_trails(void* sys, int* out4 /* initial x, y, current x, y */, int cap);
+/* Shared-stage mode: InitFromStereo / CalcPlaneAligner take the results of HomographyInit::Compute (+ the scale) and of the plane aligner from the two
+ * functions given -- bmh_homography_pipeline and bmh_plane_pipeline of oracle/bootmath_host.cpp, the host build of the product's csrc/bootstrap_math.h --
+ * instead of the oracle's own mathematics.  Both null (the default): the oracle's own. */
+void orc_sys_set_shared_stages(void* sys, void* homography_pipeline, void* plane_pipeline);
+/* the point loop of the last InitFromStereo (jni/MapMaker.cc:263-337), per match: (code, sub-pixel iterations started) and the sub-pixel position reached.
+ * code 0 a point was made, 1 the template does not keep the border, 2 sub-pixel did not converge or left the image, 3 wp[2] < 0 */
+int orc_sys_get_boot_log(void* sys, int* code_its2, double* sub2, int cap);
+/* of the last InitFromStereo: {exit (0 went through, 1 HomographyInit failed, 2 zero translation, 3 shared-stage mode: the host pipeline's ok = 0), points
+ * when CalcPlaneAligner ran (-1: not reached), an aligner was made, points whose pixel vectors ApplyGlobalTransformationToMap changed in some bit};
+ * mdWiggleScaleDepthNormalized */
+void orc_sys_get_boot_diag(void* sys, int out[4], double* wiggle_depth_norm);
+/* per map point: v3PixelRight_W, v3PixelDown_W and (source keyframe, source level, irLevelPos x, y) */
+int orc_sys_get_point_sources(void* sys, double* right3, double* down3, int* src4, int cap);
+void orc_sys_get_keyframe_depth(void* sys, int kf, double out[2]);   /* dSceneDepthMean, dSceneDepthSigma */
+int orc_sys_get_keyframe_meas_subpix(void* sys, int kf, int* subpix, int cap);   /* bSubPix, in orc_sys_get_keyframe_meas's order */
 /* HomographyInit::Compute (jni/HomographyInit.cc:43-71) on n matches given as 8 doubles each: first (z = 1 plane), second, d pixel / d plane (2x2 row-major) */
 int orc_homography_init(const double* matches8, int n, double max_pixel_error, unsigned seed, double out12[12], int* n_inliers);
 /* ... with what Compute held on the way: the MLESAC homography, the indices of its inliers (inl: room for n), the refined homography, the branch of

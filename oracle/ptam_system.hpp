@@ -50,6 +50,7 @@ struct Finder {
   long n_win[3] = {0, 0, 0};  // statistics: FindPatchCoarse windows that reach the bottom row / hold no candidate / hold a candidate no patch fits around
   bool kept = false;          // statistics: the last MakeTemplateCoarseCont kept the previous template (a cache hit)
   int span = -1;              // statistics: list entries i_end - i of the last FindPatchCoarse window; -1: the window was outside the level's rows
+  int sp_its = 0;             // statistics: sub-pixel iterations the last IterateSubPixToConvergence started
 };
 
 struct MapPoint {     // jni/MapPoint.h:22-69 + TrackerData (jni/TrackerData.h:36-66)
@@ -208,6 +209,23 @@ struct System {
   bool InitFromStereo(const KeyFrame& kF, const KeyFrame& kS, const std::vector<std::array<int, 4>>& trail_matches);
   void RefreshSceneDepth(KeyFrame& k);
   SE3 CalcPlaneAligner(); void ApplyGlobalTransformationToMap(const SE3& new_from_old);
+  // Shared-stage mode (off while both are null): InitFromStereo and CalcPlaneAligner take the RESULTS of their two mathematical stages from the host
+  // build of the product's csrc/bootstrap_math.h (oracle/bootmath_host.cpp: bmh_homography_pipeline, bmh_plane_pipeline, which fill the records of
+  // include/vslam_c.h) instead of homography.cpp, so that everything around the stages can be compared with the device without a tolerance.  The oracle
+  // library does not link that build: the caller hands the two functions in.
+  typedef void (*HomStageFn)(int n, const double* m8, unsigned seed, double max_pixel_error, double wiggle_scale, void* homography_probe);
+  typedef void (*PlaneStageFn)(int n, const double* pos3, unsigned seed, void* plane_probe);
+  HomStageFn shared_hom = nullptr; PlaneStageFn shared_plane = nullptr;
+  // InitFromStereo's point loop (jni/MapMaker.cc:263-337), per match: code (0 a point was made, 1 the template does not keep the border, 2 the sub-pixel
+  // iterations did not converge or left the image, 3 wp[2] < 0), the iterations started, and the sub-pixel position reached
+  struct BootLogEntry { int code, its; double sub[2]; };
+  std::vector<BootLogEntry> boot_log;
+  // which way the last InitFromStereo left: 0 it went through, 1 HomographyInit::Compute failed (:233-240), 2 the translation has no length (:243-248),
+  // 3 shared-stage mode: the host pipeline's ok = 0 (it covers both)
+  int boot_exit = 0;
+  // CalcPlaneAligner / ApplyGlobalTransformationToMap of the last InitFromStereo: points at that moment, 1 if an aligner was made, points whose pixel
+  // vectors the refresh changed in at least one bit
+  int boot_plane_points = -1, boot_plane_have = 0, boot_pixvec_changed = 0;
 };
 
 // map bootstrap mathematics (homography.cpp): HomographyMatch / HomographyDecomposition of jni/HomographyInit.h, HomographyInit::Compute, CalcPlaneAligner

@@ -6,12 +6,19 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+#include "../include/vslam_c.h"
 #include "../include/vslam_feeder.h"
 #include "ptam_system.hpp"
 
 using namespace orc;
 
 static const double kCam[5] = {0.841906, 1.10893, 0.505171, 0.470265, -0.0133843};
+
+// bootmath_host.cpp's two pipelines behind the signatures System::shared_hom / shared_plane take
+extern "C" void bmh_homography_pipeline(int n, const double* m8, unsigned seed, double max_pixel_error, double wiggle_scale, vslam_homography_probe* out);
+extern "C" void bmh_plane_pipeline(int n, const double* pos3, unsigned seed, vslam_plane_probe* out);
+static void hom_stage(int n, const double* m8, unsigned seed, double e, double w, void* out) { bmh_homography_pipeline(n, m8, seed, e, w, (vslam_homography_probe*)out); }
+static void plane_stage(int n, const double* pos3, unsigned seed, void* out) { bmh_plane_pipeline(n, pos3, seed, (vslam_plane_probe*)out); }
 
 int main() {
   const int W = 320, H = 240, NKF = 8, NFRAMES = 46;
@@ -115,6 +122,26 @@ int main() {
     reproject_vector(I, zero, zero, v);
     std::printf("epipolar exits %d %d %d %d, %d clipped; degenerate triangulations %g %g %g, v[3] %g\n", exits[0], exits[1], exits[2], exits[3], clipped, p0[2], p1[2], p2[2], v[3]);
     if (!exits[0] || !exits[1] || !exits[2] || !exits[3] || !clipped || v[3] != 0.0) { std::fprintf(stderr, "selftest: the epipolar cases miss their exits\n"); vslam_feeder_destroy(f); return 5; }
+  }
+  // the map bootstrap in shared-stage mode: the trails of twelve frames, then InitFromStereo with the two stage results taken from the host build of
+  // csrc/bootstrap_math.h (bootmath_host.cpp, compiled into this program), the point loop's log, the frames that follow
+  {
+    Params pb = p;
+    pb.ba_delay_frames = 0; pb.use_sbi = 0;
+    System boot(pb);
+    boot.shared_hom = hom_stage; boot.shared_plane = plane_stage;
+    boot.boot_seed = 4;
+    for (int t = 0; t < 16; t++) {
+      if (t == 0 || t == 11) boot.spacebar = true;
+      boot.TrackFrame(frames.data() + (size_t)t * W * H, W);
+    }
+    int made = 0;
+    for (auto& e : boot.boot_log) made += e.code == 0;
+    std::printf("shared-stage bootstrap: ok %d, %d inliers, %zu matches logged, %d points made, %zu points, plane over %d points (have %d), quality %d\n", (int)boot.init_ok,
+                boot.n_hom_inliers, boot.boot_log.size(), made, boot.pts.size(), boot.boot_plane_points, boot.boot_plane_have, boot.quality);
+    if (!boot.init_ok || boot.boot_exit != 0 || made != boot.n_init_points || made < 50 || !boot.boot_plane_have || boot.quality != 2) {
+      std::fprintf(stderr, "selftest: the shared-stage bootstrap did not initialise\n"); vslam_feeder_destroy(f); return 6;
+    }
   }
   vslam_feeder_destroy(f);
   return 0;

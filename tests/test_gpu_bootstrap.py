@@ -11,7 +11,8 @@ from rand() and holds no fixture for this.
 What this file sees of HomographyInit and the plane aligner is the map AFTER 55 bundle adjustments, which repair a slightly wrong
 second camera pose.  The two stages themselves are observed in tests/test_gpu_bootstrap_stages.py (every stage of the device functions
 against a host build of csrc/bootstrap_math.h bit for bit, and against the oracle's stages), tied to the product path here by
-test_init_from_stereo_with_host_keyframes_and_matches."""
+test_init_from_stereo_with_host_keyframes_and_matches.  Everything past the homography is compared without a tolerance in
+tests/test_gpu_init_from_stereo.py, against the oracle in its shared-stage mode."""
 import numpy as np
 import pytest
 

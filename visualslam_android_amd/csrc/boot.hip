@@ -315,14 +315,18 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_boot_homography(MapDev m, Trac
                         boot_workspace(m, tp, s), nullptr, &r);
   if (threadIdx.x != 0) return;
   if (n >= 4) st->n_hom_inliers = r.n_inliers;
-  if (!r.ok) { st->boot_run = 0; st->boot_ok = 0; st->init_stage = 2; return; }      // the tracker's stage is COMPLETE either way, jni/Tracker.cc:279
+  // the tracker's stage is COMPLETE either way, jni/Tracker.cc:279; InitFromStereo has returned before it made a keyframe (:236-247), so the
+  // map holds none: slot 0 was the tracker's mFirstKF, as after Reset
+  if (!r.ok) { st->boot_run = 0; st->boot_ok = 0; st->init_stage = 2; st->n_kf = 0; return; }
   Pose se3;
   for (int i = 0; i < 9; i++) se3.R[i] = r.R[i];
   for (int i = 0; i < 3; i++) se3.t[i] = r.t_scaled[i];
   st->boot_ok = 1;
   const size_t K = tp.max_keyframes;
   m.kf_pose[(size_t)s * K + 0] = pose_identity(); m.kf_fixed[(size_t)s * K + 0] = 1;   // pkFirst, :256-257
-  st->pose_final = se3; st->depth_mean = 0; st->depth_sigma = 0;                       // pkSecond's pose for k_add_keyframe (slot n_kf = 1)
+  // pkSecond's pose for k_add_keyframe (slot n_kf = 1).  Its scene depth is the tracker's, *pkSecond = kS (:254), until :349-350 refresh it; the
+  // tracker's own (mCurrentKF.dSceneDepthMean / Sigma, 1.0 since jni/Tracker.cc:52-53) is not InitFromStereo's to write and stays.
+  st->pose_final = se3;
   st->kf_pending = 1;
 }
 
@@ -481,10 +485,15 @@ __global__ __launch_bounds__(BOOT_THREADS) void k_boot_plane(MapDev m, TrackPara
   for (int i = threadIdx.x; i < n; i += BOOT_THREADS) for (int k = 0; k < 3; k++) pos[3 * i + k] = pts[i].pos[k];
   __syncthreads();
   boot_plane_stage(pos, n, st->boot_seed + 1u, nullptr, &r);
-  if (r.have) {                                                      // ApplyGlobalTransformationToMap, :440-449
-    Pose T;
-    for (int i = 0; i < 9; i++) T.R[i] = r.R[i];
-    for (int i = 0; i < 3; i++) T.t[i] = r.t[i];
+  {                                                                  // ApplyGlobalTransformationToMap, :440-449
+    // Without an aligner (fewer than ten points, :1107-1110, or no inlier) the reference applies the identity: the poses and positions go
+    // through the same products, and RefreshPixelVectors re-derives every point's pixel vectors from the ADJUSTED map -- the vectors
+    // k_boot_points and the growth made belong to the map before the adjustments.
+    Pose T = pose_identity();
+    if (r.have) {
+      for (int i = 0; i < 9; i++) T.R[i] = r.R[i];
+      for (int i = 0; i < 3; i++) T.t[i] = r.t[i];
+    }
     const Pose Tinv = pose_inverse(T);
     for (int k = threadIdx.x; k < nk; k += BOOT_THREADS) m.kf_pose[(size_t)s * K + k] = pose_mul(m.kf_pose[(size_t)s * K + k], Tinv);
     __syncthreads();
