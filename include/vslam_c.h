@@ -368,7 +368,8 @@ int vslam_fit_similarity(int n, const double* from3, const double* to3, const do
  * appended keyframes are not fixed (the destination keeps its one gauge), the appended points carry none of the source's per-frame
  * flags, and both "bundle adjustment has converged" flags of the destination are cleared.  The source is read only and keeps every bit:
  * the caller resets it or lets it run on.  Nothing of the destination below its old counts changes.
- * No point fusion: points that both maps hold of the same surface feature stay two points.  No registration: bringing both maps into one
+ * Points that both maps hold of the same surface feature are two points afterwards; vslam_fuse_points (below) makes them one once they
+ * have been measured at the same corners.  No registration: bringing both maps into one
  * frame and scale first is the caller's job (vslam_fit_similarity + vslam_transform_maps); nothing in this call can check it.  The parts
  * become one adjustable map as keyframes added afterwards measure points of both, and, with idle_iterations, as ReFindNewlyMade looks for
  * the appended points in the destination's keyframes: they all count as newly made (mqNewQueue keeps its head).
@@ -388,6 +389,43 @@ int vslam_get_merge_info(vslam_system* sys, int stream, int out[6]);
 /* HIP-event milliseconds around the last vslam_merge_maps's launches on the system's stream.  Waits for them.  VSLAM_E_STATE before the
  * first call that merged. */
 int vslam_get_merge_timing(vslam_system* sys, double* ms);
+
+/* ---- point fusion: coincident measurements make two map points one --------------------------------
+ * After a merge of two maps of overlapping ground every shared surface feature is in the destination twice, and with idle_iterations
+ * ReFindNewlyMade finds the appended twin in the destination's keyframes at the very corner where the destination's own point is
+ * measured.  This call reads that and nothing else: two live (not bad) points q < p of a stream are duplicates if in at least min_views
+ * keyframes both are measured at the same pyramid level with |root_p - root_q| <= radius * 2^level (radius in level pixels), and in no
+ * keyframe both are measured otherwise (csrc/fuse_dev.h states the rule and its order of operations).  Nothing is projected and no
+ * registration is trusted.  The partner of p is the lowest such q; p is dropped into it unless that q has a partner of its own -- one
+ * level per call, all decisions on the state before the call: the tail of a chain stays, is counted, and a later call takes it.
+ * The lower index is kept (after a merge: the destination's own point) with its position, template and tracker data; the next bundle
+ * adjustment moves it.  Of a kept q an empty measurement cell (k, q) whose keyframe is not in q's never-retry set takes the measurement
+ * (k, p) of the lowest p dropped into q that has one, no longer marked as a point's root measurement, and q's measurement-keyframe count
+ * grows by one per cell taken.  A dropped p becomes bad and the valid bytes of its measurements are cleared; nothing else of it changes
+ * (the tracker and the map-maker skip bad points; vslam_retire_keyframes reclaims their slots).  If anything was dropped both "bundle
+ * adjustment has converged" flags are cleared.  Every other byte of the stream keeps its value.
+ * streams == NULL: every stream, whatever n > 0 is (it is only checked against n_streams; n == 0 still does nothing).  Between frames or
+ * between subset steps.  The call waits once for the device to read the listed streams'
+ * states; everything is decided before anything changes, and a refused call changes nothing for any stream.  All listed streams go in one
+ * set of four launches on the system's stream; n == 0 succeeds and does nothing.  The scratch (12 bytes per point of every stream's
+ * capacity) is allocated by the first call.
+ * VSLAM_E_INVALID: NULL system, n < 0 or n > n_streams, an index outside the batch, a duplicate stream, radius not finite or <= 0,
+ * min_views < 1.
+ * VSLAM_E_STATE: a stage-wise frame is open; a listed stream has no good map, its trails running, or an adjustment of the asynchronous
+ * map-maker pending (its result would write outlier bookkeeping for points that no longer exist). */
+int vslam_fuse_points(vslam_system* sys, const int* streams, int n, double radius, int min_views);
+/* out[0] = calls that dropped something for this stream so far; of the last call that listed it: out[1] points dropped, out[2] cells
+ * taken, out[3] valid cells of dropped points that were not taken, out[4] points left because their partner was itself a duplicate,
+ * out[5] mnFrame (jni/Tracker.h:116) at that call.  All zeros before the first call.  vslam_reset_streams and vslam_restore_stream zero
+ * the record. */
+int vslam_get_fuse_info(vslam_system* sys, int stream, int out[6]);
+/* The (dropped, kept) point indices of the last call that listed the stream, ascending by dropped: a caller that holds point indices
+ * (anchors) follows them.  *n = the number of pairs; VSLAM_E_CAPACITY if cap is short (then *n is still the count and nothing is
+ * written).  VSLAM_E_STATE for a stream no call has listed since its creation, reset or restore. */
+int vslam_get_fuse_pairs(vslam_system* sys, int stream, int* dropped, int* kept, int cap, int* n);
+/* HIP-event milliseconds around the last vslam_fuse_points's launches on the system's stream.  Waits for them.  VSLAM_E_STATE before the
+ * first call that launched. */
+int vslam_get_fuse_timing(vslam_system* sys, double* ms);
 
 /* ---- overlay: the tracker's points and trails drawn into RGBA (vslam_params.overlay) -------------
  * What Tracker::TrackFrame draws on imageColor (jni/Tracker.cc:580-588 the patches TrackMap found, as discs coloured by pyramid level, the

@@ -137,6 +137,10 @@ SYMBOLS = {
     "vslam_merge_maps": (_i, [_sys, _vp, _vp, _i]),
     "vslam_get_merge_info": (_i, [_sys, _i, _vp]),
     "vslam_get_merge_timing": (_i, [_sys, C.POINTER(_d)]),
+    "vslam_fuse_points": (_i, [_sys, _vp, _i, _d, _i]),
+    "vslam_get_fuse_info": (_i, [_sys, _i, _vp]),
+    "vslam_get_fuse_pairs": (_i, [_sys, _i, _vp, _vp, _i, _ip]),
+    "vslam_get_fuse_timing": (_i, [_sys, C.POINTER(_d)]),
     "vslam_fit_similarity": (_i, [_i, _vp, _vp, _vp, _i, _vp, C.POINTER(_d), C.POINTER(_d)]),
     "vslam_render_overlay": (_i, [_sys, _vp, _i, _vp, _sz, _sz, _i, _i]),
     "vslam_get_overlay_info": (_i, [_sys, _i, _vp]),
@@ -641,6 +645,35 @@ class System:
         """-> HIP-event ms of the last merge_maps on the system's stream (vslam_get_merge_timing)"""
         ms = C.c_double(0.0)
         _check(self.lib.vslam_get_merge_timing(self.h, C.byref(ms)))
+        return ms.value
+
+    def fuse_points(self, streams=None, radius=1.0, min_views=2):
+        """Live points of the listed streams (None: every stream) that were measured at the same place (within radius level pixels) in at
+        least min_views keyframes and nowhere apart become one, the lower index kept (vslam_fuse_points)"""
+        a = None if streams is None else np.ascontiguousarray(np.atleast_1d(streams), np.int32)
+        _check(self.lib.vslam_fuse_points(self.h, None if a is None else a.ctypes.data, self.S if a is None else len(a), float(radius), int(min_views)))
+
+    def fuse_info(self, stream):
+        """-> {"fused", "dropped", "taken", "not_taken", "chained", "frame"} of the stream (vslam_get_fuse_info)"""
+        o = np.zeros(6, np.int32)
+        _check(self.lib.vslam_get_fuse_info(self.h, stream, o.ctypes.data))
+        return dict(zip(("fused", "dropped", "taken", "not_taken", "chained", "frame"), (int(x) for x in o)))
+
+    def fuse_pairs(self, stream):
+        """-> int32 [n, 2]: (dropped, kept) point indices of the stream's last fuse_points, ascending by dropped (vslam_get_fuse_pairs)"""
+        n = C.c_int(0)
+        rc = self.lib.vslam_get_fuse_pairs(self.h, stream, None, None, 0, C.byref(n))
+        if rc != -3:                                   # VSLAM_E_CAPACITY: there are pairs, n says how many
+            _check(rc)
+            return np.zeros((0, 2), np.int32)
+        d, k = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        _check(self.lib.vslam_get_fuse_pairs(self.h, stream, d.ctypes.data, k.ctypes.data, n.value, C.byref(n)))
+        return np.stack([d, k], axis=1)
+
+    def fuse_timing(self):
+        """-> HIP-event ms of the last fuse_points on the system's stream (vslam_get_fuse_timing)"""
+        ms = C.c_double(0.0)
+        _check(self.lib.vslam_get_fuse_timing(self.h, C.byref(ms)))
         return ms.value
 
     # ---- stream snapshots --------------------------------------------------------------------

@@ -5,7 +5,8 @@
 // build's own, and opt-in by being called: a system that never calls it allocates nothing here and launches nothing.  The C++ mirror
 // (include/vslam/ptam.h) gains nothing: its MapMaker is one stream.
 //
-// What it is not.  No point fusion: points that both maps hold of one surface feature stay two points.  No registration: bringing both
+// What it is not.  Points that both maps hold of one surface feature are two points afterwards; vslam_fuse_points (fuse.hip) makes them
+// one once they have been measured at the same corners.  No registration: bringing both
 // maps into one frame and one scale first is the caller's job (vslam_fit_similarity + vslam_transform_maps), and nothing here can check
 // it.  The two parts become one adjustable map through what exists: keyframes added afterwards measure points of both parts, and
 // TrackerState::newq_head stays where it was, so every appended point is in mqNewQueue and, with idle jobs, ReFindNewlyMade looks for

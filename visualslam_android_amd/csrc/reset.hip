@@ -15,6 +15,7 @@
 //   the pool record               ba.hip, ba_reset_streams
 //   the retire record             vslam_get_retire_info (retire.hip), where the system holds one
 //   the merge record              vslam_get_merge_info (merge.hip), where the system holds one
+//   the fuse record               vslam_get_fuse_info and vslam_get_fuse_pairs (fuse.hip), where the system holds one
 //   the overlay's record          -1, TrackMap has not run (overlay.hip), where the system holds one
 //   the transform record          vslam_get_transform_info (transform.hip), kept on the host: no transforms, the identity
 // Not cleared, because every reader is bounded by a count that is now zero and the writer that raises the count fills what it exposes:
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(RESET_THREADS) void k_reset_clear(MapDev m, TrackPa
 }
 
 // one lane per stream: what the reset dropped, then the state of a new system's stream
-__global__ void k_reset_state(MapDev m, int S, const unsigned char* flags, int* info, int* retire_info, int* merge_info, int* overlay_ran, unsigned char* sbi_restart, unsigned pvs_seed) {
+__global__ void k_reset_state(MapDev m, int S, const unsigned char* flags, int* info, int* retire_info, int* merge_info, int* fuse_info, int* overlay_ran, unsigned char* sbi_restart, unsigned pvs_seed) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= S || !flags[s]) return;
   TrackerState* st = &m.st[s];
@@ -72,6 +73,7 @@ __global__ void k_reset_state(MapDev m, int S, const unsigned char* flags, int* 
   *st = tracker_reset_state(pvs_seed);
   if (retire_info) for (int k = 0; k < 6; k++) retire_info[6 * (size_t)s + k] = 0;   // vslam_get_retire_info: a new system's
   if (merge_info) for (int k = 0; k < 6; k++) merge_info[6 * (size_t)s + k] = 0;     // vslam_get_merge_info: a new system's
+  if (fuse_info) for (int k = 0; k < 8; k++) fuse_info[8 * (size_t)s + k] = 0;       // vslam_get_fuse_info and the pairs: a new system's
   if (overlay_ran) overlay_ran[s] = -1;                                              // no discs until TrackMap has run again
   if (sbi_restart) sbi_restart[s] = 1;
 }
@@ -113,7 +115,7 @@ extern "C" int vslam_reset_streams(vslam_system* sys, const int* streams, int n)
   HIPCHK(hipEventRecord(sys->ev_reset_stage[q], sys->stream));
   int r = ba_reset_streams(sys, sys->reset_flags); if (r) return r;
   hipLaunchKernelGGL(k_reset_clear, dim3(RESET_BLOCKS, sys->S), dim3(RESET_THREADS), 0, sys->stream, sys->map, sys->tp, sys->reset_flags, sys->reloc.info);
-  hipLaunchKernelGGL(k_reset_state, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->S, sys->reset_flags, sys->reset_info, sys->retire_info, sys->merge_info, sys->overlay_ran, sys->sbi_restart, sys->p.pvs_shuffle_seed);
+  hipLaunchKernelGGL(k_reset_state, dim3((sys->S + 63) / 64), dim3(64), 0, sys->stream, sys->map, sys->S, sys->reset_flags, sys->reset_info, sys->retire_info, sys->merge_info, sys->fuse_info, sys->overlay_ran, sys->sbi_restart, sys->p.pvs_shuffle_seed);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(sys->ev_reset_t[1], sys->stream));
   // whatever the other streams of the system launch from now on comes after the reset

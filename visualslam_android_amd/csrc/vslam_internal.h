@@ -405,6 +405,14 @@ struct vslam_system {
   int* merge_plan_stage = nullptr;           // pinned host copy of the request the plan starts from
   hipEvent_t ev_merge_t[2] = {nullptr, nullptr};   // around the last call's launches (vslam_get_merge_timing)
   long merge_calls = 0;
+  // vslam_fuse_points (fuse.hip): allocated by the first call, else null
+  int* fuse_partner = nullptr;               // [S][max_points] device: partner(p) of the call in flight, -1 none
+  int2* fuse_pairs = nullptr;                // [S][max_points] device: the (dropped, kept) pairs of a stream's last call, ascending by dropped
+  int* fuse_info = nullptr;                  // [S][8] device: vslam_get_fuse_info's six, then whether the stream has been listed
+  int* fuse_list = nullptr;                  // [S] device: ordinal -> stream of the call in flight
+  int* fuse_list_stage = nullptr;            // pinned host copy of it
+  hipEvent_t ev_fuse_t[2] = {nullptr, nullptr};   // around the last call's launches (vslam_get_fuse_timing)
+  long fuse_calls = 0;
   // the overlay renderer (overlay.hip; vslam_params.overlay): null with overlay = 0
   int* overlay_ran = nullptr;                // [S] device: mnFrame at which TrackMap last ran for the stream, -1 never (or forgotten by a reset)
   int* overlay_info = nullptr;               // [S][3] device: discs, lines, marks of the stream's last render
