@@ -186,6 +186,13 @@ int orc_sys_get_template(void* sv, int pt, uint8_t* tmpl, int* sum, int* sumsq, 
   return f.have_last;
 }
 
+// mm2WarpInverse of point pt's finder as the last CalcSearchLevelAndWarpMatrix left it, and mm2LastWarpMatrix, the warp its template was
+// last made with (row-major; tests/template_cases.py works out from them how far a pose stands from a threshold)
+void orc_sys_get_warp(void* sv, int pt, double warp_inv[4], double last_warp[4]) {
+  const Finder& f = ((System*)sv)->pts[pt]->finder;
+  for (int i = 0; i < 4; i++) { warp_inv[i] = f.warp_inv[i]; last_warp[i] = f.last_warp[i]; }
+}
+
 int orc_sys_bundle_adjust_recent(void* sv) { System* s = (System*)sv; const int r = s->BundleAdjustRecent(); s->HandleBadPoints(); return r; }
 int orc_sys_bundle_adjust_all(void* sv) { System* s = (System*)sv; const int r = s->BundleAdjustAll(); s->HandleBadPoints(); return r; }
 

@@ -427,6 +427,12 @@ class OracleSystem:
         have = self.L.orc_sys_get_template(self.h, pt, _p(t), C.byref(s), C.byref(sq), C.byref(bad))
         return {"tmpl": t.reshape(P, P), "sum": s.value, "sumsq": sq.value, "bad": bad.value, "have": have}
 
+    def warp(self, pt):
+        """(mm2WarpInverse, mm2LastWarpMatrix) of the point's finder, row-major"""
+        w, last = np.zeros(4), np.zeros(4)
+        self.L.orc_sys_get_warp(self.h, pt, _p(w), _p(last))
+        return w, last
+
     def templates(self, n=None):
         """cached warped templates of the first n map points, like capi.System.templates"""
         n = self.state().n_points if n is None else n

@@ -172,6 +172,8 @@ int orc_sys_get_points(void* sys, double* pos3, int* bad, int* n_in, int* n_out,
 void orc_sys_get_keyframe_pose(void* sys, int kf, double pose12[12]);
 int orc_sys_get_keyframe_meas(void* sys, int kf, int* pt, int* level, double* root, int* source, int cap);
 int orc_sys_get_template(void* sys, int pt, uint8_t* tmpl, int* sum, int* sumsq, int* bad);
+/* the point's mm2WarpInverse as last computed and the mm2LastWarpMatrix its template was made with, row-major */
+void orc_sys_get_warp(void* sys, int pt, double warp_inv[4], double last_warp[4]);
 /* every AddPointEpipolar call so far: (level, packed candidate position, stage at which it gave up; 0 = point added) */
 int orc_sys_get_grow_log(void* sys, int* out3, int cap);
 /* beside it, one record of 6 per call: target corners that passed the line filter (jni/MapMaker.cc:622-628), the most of them inside one aligned block

@@ -26,6 +26,10 @@ to 35 degrees alone: the scene depth's sigma is 0.01 when the camera faces the p
 Zoomed out to 0.7 and tilted -35 degrees (also 0.5 with +-35) the sigma is wide enough and hundreds of lines are clipped, seven of them
 accepted; a target turned 80 degrees and placed 0.04 ahead of a camera tilted 25 degrees clips a few lines whose dirn[2] is a few hundredths.
 
+Group f reaches the template that samples outside its source image (nOutside != 0 in MakeTemplateCoarseCont, jni/PatchFinder.cc:105-117),
+which the 10-pixel border of the other groups' map points keeps away: a map whose points keep half a patch from the borders of their source
+images, and, for the verdict that a kept template carries on from nOutside, map keyframes that see the new keyframe from far to the side.
+
 What stays unreached in every case (test_grow_cases.py asserts the counts are zero, so that a change that reaches one is noticed), and why:
 - stage 4.  Candidates keep a border of 10 level pixels (orc_candidates(..., 10, ...), jni/KeyFrame.cc:66-95); MakeTemplateCoarseNoWarp
   needs P / 2 + 1 <= 6 for P = 8 and 11.  No candidate can fail it.
@@ -60,8 +64,9 @@ def _with(pkw, **kw):
 
 
 @functools.lru_cache(maxsize=None)
-def scene(rects=None):
-    return make_scene(W, H, seed=SEED, n_frames=2, per_level=PER_LEVEL, rects=rects)
+def scene(rects=None, border=None):
+    """border: feeder.build_map's patch_border, the level pixels a map point keeps from the borders of its source image (default 10)"""
+    return make_scene(W, H, seed=SEED, n_frames=2, per_level=PER_LEVEL, rects=rects, **({} if border is None else {"patch_border": border}))
 
 
 def _levels(rects=None):
@@ -81,6 +86,27 @@ def with_turned_keyframe(m, f, degrees, offset, pose12=None):
     kf = {"pose": pose, "fixed": False, "image": f.render_pose(pose, key=2000), "depth_mean": m["keyframes"][-1]["depth_mean"],
           "depth_sigma": m["keyframes"][-1]["depth_sigma"]}
     return {"keyframes": list(m["keyframes"]) + [kf], "points": m["points"], "meas": m["meas"]}
+
+
+def with_oblique_keyframes(m, f, pose12, degrees):
+    """the map with one more keyframe per angle of `degrees` at the end, without measurements: the camera at pose12 swung by that angle
+    about the vertical axis through the point where its optical axis meets the scene's plane z = 0, so that it looks at the same spot
+    from the same distance, obliquely.  Such a keyframe sees a patch of the new keyframe compressed to cos(angle) of its width: the
+    template ReFindNewlyMade warps for it covers 1 / cos(angle) source pixels per pixel, and leaves the source image for new points whose
+    candidates kept only their 10 pixels from its left or right border.  Two angles half a degree apart give the second call the first's
+    template (the warp moves by less than 0.07) and with it the verdict of nOutside."""
+    p = np.asarray(pose12, np.float64)
+    R, t = p[:9].reshape(3, 3), p[9:]
+    C = -R.T @ t
+    x0c = np.array([0.0, 0.0, -C[2] / R[2, 2]])                  # the spot, in the camera's frame
+    kfs = list(m["keyframes"])
+    for j, deg in enumerate(degrees):
+        a = np.deg2rad(deg)
+        Ry = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+        pose = np.r_[(Ry @ R).ravel(), Ry @ (t - x0c) + x0c]
+        kfs.append({"pose": pose, "fixed": False, "image": f.render_pose(pose, key=3000 + j), "depth_mean": m["keyframes"][-1]["depth_mean"],
+                    "depth_sigma": m["keyframes"][-1]["depth_sigma"]})
+    return {"keyframes": kfs, "points": m["points"], "meas": m["meas"]}
 
 
 def closest_keyframe(m, pose12):
@@ -121,12 +147,14 @@ class Case:
     keyframe's and both frames are rendered there.  zoom: the start pose is the scene's moved along the optical axis to 1 / zoom of its
     distance from the plane, frames rendered there.  kf_request = False: the tracker has just dropped a keyframe, so it asks for none."""
 
-    def __init__(self, name, keep=None, pkw=BASE, rects=None, at_kf=None, zoom=None, kf_request=True, target=None, turned_kf=None, behind=0, repeat=None, oblique=None):
+    def __init__(self, name, keep=None, pkw=BASE, rects=None, at_kf=None, zoom=None, kf_request=True, target=None, turned_kf=None, behind=0, repeat=None, oblique=None, border=None, oblique_kfs=None):
         """turned_kf = (degrees, offset): one more map keyframe, without measurements, at the pose of frame 0 turned about the camera's
         vertical axis and moved along it by offset (group e).  behind: that many points of the sub-map, its last, are moved behind
         the camera of frame 0 and lose their measurements (group e)."""
         self.name, self.pkw, self.rects, self.at_kf, self.zoom, self.kf_request, self.target = name, tuple(pkw), rects, at_kf, zoom, kf_request, dict(target or {})
         self.keep = keep if keep is None or isinstance(keep, str) else np.asarray(keep, np.int64)
+        self.border = border            # the map's patch_border (group f), None = build_map's default
+        self.oblique_kfs = oblique_kfs  # angles: with_oblique_keyframes about the spot the start pose looks at (group f)
         self.oblique = oblique          # degrees: the start pose (after zoom) turned in place about the camera's horizontal axis, frames rendered there
         self.turned_kf, self.behind, self.repeat = turned_kf, behind, repeat           # repeat = (cx, cy, half, dx, dy): with_repeated_block
         self._map, self._frames = None, {}
@@ -141,14 +169,16 @@ class Case:
 
     def map(self):
         if self._map is None:
-            m = scene(self.rects)[1]
+            m = scene(self.rects, self.border)[1]
             self._map = m if self.keep is None else sub_map(m, self.keep)
             if self.turned_kf is not None:
-                self._map = with_turned_keyframe(self._map, scene(self.rects)[0], *self.turned_kf, pose12=self.start_pose() if self.own_frames else None)
+                self._map = with_turned_keyframe(self._map, scene(self.rects, self.border)[0], *self.turned_kf, pose12=self.start_pose() if self.own_frames else None)
+            if self.oblique_kfs is not None:
+                self._map = with_oblique_keyframes(self._map, scene(self.rects, self.border)[0], self.start_pose(), self.oblique_kfs)
             if self.behind:
-                self._map = with_points_behind(self._map, scene(self.rects)[0].pose(0), self.behind)
+                self._map = with_points_behind(self._map, scene(self.rects, self.border)[0].pose(0), self.behind)
             if self.repeat is not None:
-                self._map = with_repeated_block(self._map, scene(self.rects)[0].pose(0), *self.repeat)
+                self._map = with_repeated_block(self._map, scene(self.rects, self.border)[0].pose(0), *self.repeat)
         return self._map
 
     @property
@@ -156,7 +186,7 @@ class Case:
         return not (self.at_kf is None and self.zoom is None and self.oblique is None)
 
     def start_pose(self):
-        f, m, _frames = scene(self.rects)
+        f, m, _frames = scene(self.rects, self.border)
         if self.zoom is not None or self.oblique is not None:
             p = np.asarray(f.pose(-1), np.float64) if self.zoom is None else _zoomed(f.pose(-1), self.zoom)
             if self.oblique is not None:
@@ -168,9 +198,9 @@ class Case:
 
     def frame(self, t):
         if not self.own_frames:
-            return scene(self.rects)[2][t]
+            return scene(self.rects, self.border)[2][t]
         if t not in self._frames:
-            self._frames[t] = scene(self.rects)[0].render_pose(self.start_pose(), key=t)
+            self._frames[t] = scene(self.rects, self.border)[0].render_pose(self.start_pose(), key=t)
         return self._frames[t]
 
     def params(self, n_streams, patch):
@@ -262,9 +292,10 @@ BAD_SCALE_ZOOM = 2.0
 @functools.lru_cache(maxsize=None)
 def group_b():
     """The fourth stream is there for the cached verdict.  A template that MakeTemplateCoarseCont regenerates is bad when the warp samples
-    outside the source image, which the 10-pixel border of candidates and map points rules out here; a kept template says what the last
-    generation said unless the scale is bad (determinant of the warp below 0.25, or above 3 at level 3).  So a cache hit is bad only by
-    a bad scale: the new keyframe seen from twice as close, whose new level-0 points the map's keyframes see at less than half the size."""
+    outside the source image, which the 10-pixel border of this group's map points and of the candidates all but rules out (group f
+    reaches it); a kept template says what the last generation said unless the scale is bad (determinant of the warp below 0.25, or above
+    3 at level 3).  So a cache hit here is bad by a bad scale: the new keyframe seen from twice as close, whose new level-0 points the
+    map's keyframes see at less than half the size."""
     n = len(_levels())
     return [Case("full map, 100 patches", None, B_PKW), Case("every 2nd point, 100 patches", np.arange(0, n, 2), B_PKW),
             Case("dense texture, full map, 100 patches", None, B_PKW, rects=DENSE_RECTS),
@@ -386,9 +417,44 @@ TIES = (((237, 13, 6, 13, -4), {8: (1, 4, 1), 11: (1, 4, 1)}),
         ((114, 17, 5, -11, 2), {8: (5, 7, 1), 11: (5, 7, 1)}))
 
 
-GROUP_NAMES = ("a: epipolar counts", "b: re-find", "c: stage 1", "c: stage 2", "d: map capacity", "e: epipolar exits")
+# ---- group F: the border map ----------------------------------------------------------------------------------------------------------
+F_ZOOMS = (1.0, 0.8, 0.6)
+F_OBLIQUE = ((1.0, (78.0, 78.03)), (0.8, (75.0, 75.05)))    # (zoom, angles of with_oblique_keyframes)
+
+
+@functools.lru_cache(maxsize=None)
+def group_f(patch):
+    """The map built with patch_border = patch // 2: its points keep half a patch from the borders of their source images, so the warped
+    template of ReFind_Common samples outside the source for dozens of them (nOutside != 0: the template is bad, the pair is never
+    retried) -- in ReFindInSingleKeyFrame, where every template is made anew.  Two more streams for the verdict a kept template carries
+    when it came from nOutside and not from the scale: every 4th point, and two map keyframes that see the new keyframe's spot from 78
+    (75) degrees to the side, 0.03 (0.05) degrees apart.  A new point's template for the first covers four source pixels per pixel
+    across and leaves the new keyframe's image where the candidate kept just its 10 pixels; the second call keeps that template."""
+    b = patch // 2
+    n = len(scene(None, b)[1]["points"])
+    return [Case("border %d, full map, zoom %.1f, 100 patches" % (b, z), None, B_PKW, zoom=z, border=b) for z in F_ZOOMS] + [
+            Case("border %d, every 4th point, zoom %.1f, keyframes at %s degrees" % (b, z, degs), np.arange(0, n, 4), B_PKW, zoom=z, border=b, oblique_kfs=degs)
+            for z, degs in F_OBLIQUE]
+
+
+def kept_outside_verdicts(rf, bad_outcome=1):
+    """of the re-find log's template calls: those that kept the template of the call before (hit) and with it a bad verdict that the call
+    which made the template (hit == 0, same point) took from nOutside -- a template made anew takes its verdict from nOutside alone"""
+    m = rf["outcome"] < 4
+    pt, hit, out = rf["pt"][m], rf["hit"][m], rf["outcome"][m]
+    n, made_bad = 0, False
+    for i in range(len(pt)):
+        if hit[i] == 0:
+            made_bad = out[i] == bad_outcome
+        elif made_bad and out[i] == bad_outcome:
+            assert pt[i] == pt[i - 1]
+            n += 1
+    return n
+
+
+GROUP_NAMES = ("a: epipolar counts", "b: re-find", "c: stage 1", "c: stage 2", "d: map capacity", "e: epipolar exits", "f: border map")
 
 
 def groups(patch):
     return {"a: epipolar counts": group_a(), "b: re-find": group_b(), "c: stage 1": group_c("stage 1"), "c: stage 2": group_c("stage 2"),
-            "d: map capacity": group_d(patch), "e: epipolar exits": group_e()}
+            "d: map capacity": group_d(patch), "e: epipolar exits": group_e(), "f: border map": group_f(patch)}

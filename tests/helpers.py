@@ -81,6 +81,23 @@ def assert_tracker_exact(o, g, s, tag, templates=True):
         assert np.array_equal(ao["sum"][h], ag["sum"][h]) and np.array_equal(ao["sumsq"][h], ag["sumsq"][h]), tag
 
 
+def assert_templates_exact(o, g, s, tag):
+    """The template state of EVERY point of the map, beside assert_tracker_exact's look at the searched ones: a point whose template is bad
+    is skipped before it is marked searched (jni/Tracker.cc:637-640), and a bad scale keeps a point out of the search list altogether
+    (jni/PatchFinder.cc:63-66).  mbTemplateBad and the have-a-template flag of all points; the bytes (zeros where the warp sampled outside
+    the source) and both sums of every template there is, bad ones included."""
+    n = o.state().n_points
+    assert g.state(s).n_points == n, tag
+    ao, ag = o.templates(n), g.templates(s, n)
+    assert np.array_equal(ao["have"], ag["have"]), (tag, np.flatnonzero(ao["have"] != ag["have"])[:8].tolist())
+    assert np.array_equal(ao["bad"], ag["bad"]), (tag, np.flatnonzero(ao["bad"] != ag["bad"])[:8].tolist())
+    h = ag["have"] == 1
+    diff = (ao["tmpl"][h] != ag["tmpl"][h]).any((1, 2))
+    assert not diff.any(), (tag, np.flatnonzero(h)[diff][:8].tolist(), int((ao["tmpl"][h] != ag["tmpl"][h]).sum()))
+    assert np.array_equal(ao["sum"][h], ag["sum"][h]) and np.array_equal(ao["sumsq"][h], ag["sumsq"][h]), tag
+    return ao
+
+
 def assert_tracker_close(o, g, s, tag, tol=POSE_TOL):
     """Free-running comparison once the maps differ in the last bits (the bundle adjustment's parallel sums are not taken
     in the reference's order): the north_star bar on the pose, the same decisions, nearly the same found set."""

@@ -1,4 +1,4 @@
-"""The stage-wise comparison of tests/test_gpu_tracker_counts.py and tests/test_gpu_frame_tail.py: cases (tracker_cases.Case) as the streams
+"""The stage-wise comparison of tests/test_gpu_tracker_counts.py, tests/test_gpu_frame_tail.py and tests/test_gpu_template_edges.py: cases (tracker_cases.Case) as the streams
 of one System, each beside its own oracle, compared with == after every search and pose stage and after the frame."""
 import numpy as np
 
@@ -21,8 +21,9 @@ def assert_stage_exact(o, g, s, tag):
     assert np.array_equal(np.array(so.pose[:]), np.array(sg.pose[:])), (tag, pose_err(so.pose, sg.pose))
 
 
-def run_group(cases, patch, after_fine_pose=None):
-    """the cases as the streams of one System, stage by stage against one oracle each"""
+def run_group(cases, patch, after_fine_pose=None, n_frames=tc.N_FRAMES, before_frame=None, after_stage=None):
+    """the cases as the streams of one System, stage by stage against one oracle each.  before_frame(o, g, s, case, t) prepares both sides
+    for frame t (a pose of the case's own, say); after_stage(o, g, s, tag) compares more after every search and pose stage."""
     S = len(cases)
     g = capi.System(cases[0].params(S, patch))
     assert all(c.pkw == cases[0].pkw and c.size == cases[0].size for c in cases)          # the parameters are system-wide
@@ -30,7 +31,10 @@ def run_group(cases, patch, after_fine_pose=None):
     for s, c in enumerate(cases):
         c.load(g, s)
         oracles.append(c.oracle(patch))
-    for t in range(tc.N_FRAMES):
+    for t in range(n_frames):
+        if before_frame:
+            for s, (o, c) in enumerate(zip(oracles, cases)):
+                before_frame(o, g, s, c, t)
         g.make_keyframe_lite(np.stack([c.frame(t) for c in cases]))
         for o, c in zip(oracles, cases):
             o.frame_begin(c.frame(t))
@@ -39,10 +43,14 @@ def run_group(cases, patch, after_fine_pose=None):
             for s, (o, c) in enumerate(zip(oracles, cases)):
                 o.search_stage(stage)
                 assert_stage_exact(o, g, s, "%s, %dx%d patches, frame %d, search %d" % (c.name, patch, patch, t, stage))
+                if after_stage:
+                    after_stage(o, g, s, "%s, %dx%d patches, frame %d, search %d" % (c.name, patch, patch, t, stage))
             g.pose_update(stage)
             for s, (o, c) in enumerate(zip(oracles, cases)):
                 o.pose_stage(stage)
                 assert_stage_exact(o, g, s, "%s, %dx%d patches, frame %d, pose %d" % (c.name, patch, patch, t, stage))
+                if after_stage:
+                    after_stage(o, g, s, "%s, %dx%d patches, frame %d, pose %d" % (c.name, patch, patch, t, stage))
         g.finish_frame()
         for s, (o, c) in enumerate(zip(oracles, cases)):
             o.frame_end()

@@ -172,3 +172,18 @@ def test_epipolar_exits_and_refind_behind(patch):
     cases = gc.groups(patch)["e: epipolar exits"]
     bits = run_group(cases, patch, never_retry=True)
     assert len(bits) == len(cases) == 5 + len(gc.TIES) and min(bits.values()) >= gc.BEHIND, bits
+
+
+@pytest.mark.parametrize("patch", [8, 11])
+def test_refind_templates_that_leave_their_source_image(patch):
+    """Group f, five streams on a map whose points keep patch // 2 level pixels from the borders of their source images.  Three (the full
+    map at zooms 1.0, 0.8 and 0.6, the tracker capped at 100 patches): dozens of templates that refind_common makes anew sample outside
+    the source -- warp_sample gives 0 and counts, one pixel per lane, the template is bad, the pair gets its never-retry bit and no
+    measurement.  Two (every 4th point, two map keyframes that see the new keyframe from 78 or 75 degrees to the side, a fraction of a
+    degree apart): new points whose template leaves the new keyframe's image in the first of the two and is kept, with its verdict, by
+    the second (RefindCache::prev_bad from nOutside, where group b's comes from the scale).  A verdict taken the other way shows as a
+    measurement row or a missing never-retry bit: both are compared after the keyframe and after every idle job, and the second frame's
+    tracker state after that."""
+    cases = gc.groups(patch)["f: border map"]
+    bits = run_group(cases, patch, never_retry=True)
+    assert len(bits) == len(cases) == 5 and min(bits.values()) >= 100, bits

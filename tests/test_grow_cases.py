@@ -15,6 +15,10 @@ calls of which a few are accepted (a camera zoomed out and tilted) and with a sm
 degrees and ahead of it); ReFind_Common's return "behind".  Its returns "outside radius" and "outside image" are reached by group b, in the new keyframe and in the
 map's keyframes (the oracle's re-find log records the calls that return before the template as outcomes of their own).
 
+Group f: templates that sample outside their source image (nOutside != 0), made anew in ReFindInSingleKeyFrame on a map whose points keep
+half a patch from the borders of their source images, and kept with that verdict in ReFindNewlyMade by map keyframes that see the new
+keyframe from far to the side.
+
 Not reached: at 8x8 a winner scored in the third or fourth step of its ballot (test_group_a prints the steps).  Not reached, and asserted to be
 absent so that a change that reaches one is noticed: stage 3, an equal-ZMSSD tie at the minimum and the start-depth clip outside group e,
 stage 4; of ReFind_Common's returns, the invalid projection and a search window outside the rows of its level (the module docstring of
@@ -69,7 +73,12 @@ def records(group, patch, verbose=True):
     for c, r in out:                                             # every stream with a map tracks both frames; the growing ones add one keyframe
         assert (r.kf_added, r.kf_added1, r.n_keyframes - r.kf0) == (int(c.grows), 0, int(c.grows)), c.name
         assert r.quality0 == r.quality1 == 2 and r.n_points1 == r.n_points, c.name
-        assert r.idle["new_queue"] == 0 and r.idle["failure_queue"] <= 8192, (c.name, r.idle)
+        if c.border is not None and r.idle["ba_all"] == 0:
+            # group f at 8x8 and zoom 0.8: the recent bundle adjustment ends its job unconverged, so the full one and both re-find jobs find
+            # their gate shut (MapMaker::run, jni/MapMaker.cc:97-112) and the new points wait in their queue: the gate's other answer
+            assert r.idle["ba_recent_idle"] == 1 and r.idle["refound_new"] == r.idle["refound_failed"] == 0 and r.idle["new_queue"] == r.n_points - r.n0, (c.name, r.idle)
+        else:
+            assert r.idle["new_queue"] == 0 and r.idle["failure_queue"] <= 8192, (c.name, r.idle)
         for k in (3, 4):                                         # the unreached stages stay unreached (stage 3: outside group e's turned targets)
             if not (k == 3 and c.turned_kf is not None):
                 assert r.stages().get(k, 0) == 0, (c.name, r.stages())
@@ -225,6 +234,30 @@ def test_group_e_reaches_stage_3_and_the_early_return_behind(patch):
     # the rivals of a tie: in two steps of one ballot, in two ballots, and (8x8) in one step
     assert any(a != b and same for a, b, same in steps) and any(not same for _a, _b, same in steps), steps
     assert any(a == b == 0 and same for a, b, same in steps) and (patch == 8 or any(a == b == 1 and same for a, b, same in steps)), steps   # one step: the first, and (11x11) a later one
+
+
+@pytest.mark.parametrize("patch", [8, 11])
+def test_group_f_makes_and_keeps_templates_that_leave_their_source(patch):
+    """the border map: templates made anew (hit == 0) that end "template bad" -- the verdict of nOutside alone, a template made anew
+    replaces what the scale said (jni/PatchFinder.cc:105-117) -- and kept templates (hit == 1) whose bad verdict is the one nOutside gave
+    when the template was made"""
+    recs = records("f: border map", patch)
+    assert len(recs) == len(gc.F_ZOOMS) + len(gc.F_OBLIQUE) and all(c.border == patch // 2 and c.pkw == gc.B_PKW for c, _r in recs)
+    bad = OUTCOME["template bad"]
+    made, kept, total = {}, {}, [0, 0]
+    for c, r in recs:
+        rf = r.refind
+        made[c.name] = {name: int(((rf["job"] == j) & (rf["hit"] == 0) & (rf["outcome"] == bad)).sum()) for name, j in JOB.items()}
+        kept[c.name] = gc.kept_outside_verdicts(rf, bad)
+        total[0] += sum(made[c.name].values()); total[1] += kept[c.name]
+        print("      %s: templates made bad per job %s; kept with the bad verdict of nOutside %d (kept and bad in all %d)" % (
+            c.name, made[c.name], kept[c.name], int(((rf["hit"] == 1) & (rf["outcome"] == bad)).sum())))
+    assert total[0] >= 8 and total[1] >= 1, total
+    assert all(sum(made[c.name].values()) >= 8 for c, _r in recs[:len(gc.F_ZOOMS)]), made      # every zoom of the full border map on its own
+    assert all(kept[c.name] >= 1 for c, _r in recs[len(gc.F_ZOOMS):]), kept                   # both streams with the keyframes to the side
+    # without the narrow border the same streams never leave the source in ReFindInSingleKeyFrame: the branch is the border's
+    plain = gc.record(gc.Case("border 10", None, gc.B_PKW, zoom=gc.F_ZOOMS[0]), patch).refind
+    assert ((plain["job"] == JOB["single keyframe"]) & (plain["outcome"] == bad)).sum() < made[recs[0][0].name]["single keyframe"]
 
 
 def test_refind_window_never_lies_outside_its_level():
